@@ -3,15 +3,19 @@
 
 Workload c3 (default, the config BASELINE.json's metric is quoted on): 256 batched channels x 2^19 complex
 samples through the 16384-pt CFastFIR overlap-save on one MI355X, inputs and outputs resident in HBM.  One
-"step" = one pass of all channels through the filter.  The same run also reports, as secondary objects of the
-one JSON line: the distinct-filter variant of C3 (every channel its own H: +16 B/sample of filter traffic), a
-post-timing parity spot check of the buffer that was just timed against the oracle, and the other BASELINE
+"step" = one pass of all channels through the filter.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the result
+line; nothing else.  `--dump-outputs DIR` also writes what the last timed step computed (dump_outputs()).  `--full`
+adds everything else, as secondary objects of the one JSON line: the fp64 CPU baseline, the counter traffic of
+live_traffic(), power and clock, the distinct-filter variant of C3 (every channel its own H: +16 B/sample of filter
+traffic), a post-timing parity spot check of the buffer that was just timed against the oracle, and the other BASELINE
 configurations, each with the oracle's fp64 CPU path timed beside it on one host core (rank 0, N = 1, a bounded
 sample): `chain_c4` (the per-GPU share of C4: 256 mixed AM/FM/USB receivers x 2^21 raw samples through the whole
 CDemodulator chain, pipelined AND strict mode), `spectrum_c1` (4096-pt CFft display spectrum), `chain_c2` (one
 receiver through the 16384-pt filter and the FM chain), `chain_c5` (one 10 MSPS receiver to 48 kHz audio), and the two
 input-rate kernels alone: `downconv_k2`, `blanker_k6`.
-Workload c4 makes the chain the primary metric instead.
+Workload c4 makes the chain the primary metric instead (`--full`: with the S-meter / audio gather).
 
 Multi-GPU: channels are independent, so every rank owns its own channels (contiguous channel ranges, weak
 scaling) and the data path has no collective; torch.distributed carries the barrier, the MAX-reduce of the
@@ -47,6 +51,8 @@ K1_SOURCES = ("cutesdr_amd/csrc/fastfir2_kernels.hip", "cutesdr_amd/csrc/fastfir
               "cutesdr_amd/csrc/fastfir_dev.hpp", "cutesdr_amd/csrc/fft_core.hpp", "cutesdr_amd/csrc/capi_fastfir.hip")
 C4_T = 1 << 21                    # raw samples per receiver and step of the chain workload
 C4_FS = 2e6
+DUMP_BYTES = 48 << 20             # what --dump-outputs writes at most, all arrays together
+DUMP_SEED = 0x5EED
 
 
 # ---------------------------------------------------------------- distributed plumbing
@@ -975,6 +981,29 @@ def timed_steps(torch, ctx, step, steps, warmup, prewarm=True):
     return elapsed, sum(a.elapsed_time(b) for a, b in ev) / steps
 
 
+def dump_outputs(torch, path, outputs):
+    """--dump-outputs DIR: what the last timed step handed its caller, as DIR/<name>.npy in float32.  `outputs` maps a
+    name to a device tensor whose first axis is the channel.  Together the files stay under DUMP_BYTES: an output larger
+    than its share is written as a fixed sample of whole channels (drawn by a generator seeded with DUMP_SEED, in channel
+    order), so that two runs with the same arguments write the same channels.  -> {name: shape written, channels sampled}"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // len(outputs)
+    written = {}
+    for name, t in outputs.items():
+        rows, row_bytes = t.shape[0], t[0].numel() * 4
+        keep = max(1, min(rows, share // row_bytes))
+        idx = np.arange(rows)
+        if keep < rows:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, keep, replace=False))
+        a = t[torch.as_tensor(idx, device=t.device)].float().cpu().numpy()
+        if a.nbytes > share:                              # one channel alone is over the share: its first samples
+            a = a.reshape(1, -1)[:, :share // 4]
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = {"shape": list(a.shape), "sampled_from_channels": rows}
+    return written
+
+
 def _read_power_w(pci=None):
     """socket power in watts of the device at PCI address `pci` ("dddd:bb:dd.f"): its amdgpu hwmon node (no process
     started), else one rocm-smi call (a host shows every card's node: the first one found is not ours)"""
@@ -1537,18 +1566,20 @@ def run_rank(args):
     if args.workload == "c3":
         w = C3Workload(torch, ca, ctx, args.channels, args.blocks_per_wg)
         elapsed, kern_ms = timed_steps(torch, ctx, w.step, args.steps, args.warmup)
-        if ctx.rank == 0 and not args.no_check:
+        if ctx.rank == 0 and args.dump_outputs:
+            extra["outputs_dumped"] = dump_outputs(torch, args.dump_outputs, {"fastfir_out": w.y})
+        if args.full and ctx.rank == 0 and not args.no_check:
             extra["parity_checked"] = w.parity_check()
-        if ctx.rank == 0 and ctx.world == 1 and not args.no_secondary:
+        if args.full and ctx.rank == 0 and ctx.world == 1 and not args.no_secondary:
             extra["power_clock"] = power_and_clock(torch, ca, ctx, w.step)
-        if ctx.rank == 0 and not args.no_secondary:
+        if args.full and ctx.rank == 0 and not args.no_secondary:
             extra["distinct_filters"] = w.distinct_filters(ctx)
             if ctx.world == 1:
                 extra["fastfir_sizes"] = w.other_sizes(ctx, check=not args.no_check)
         chans, samples = w.C, w.T
         del w
         torch.cuda.empty_cache()
-        if not args.no_secondary:
+        if args.full and not args.no_secondary:
             with_cpu = ctx.world == 1 and not args.no_cpu       # CPU legs: rank 0 at N = 1 only
             c4 = C4Workload(torch, ca, ctx, CHANNELS)
             s = c4.summary(ctx, 30, 15, with_cpu, check=not args.no_check)
@@ -1570,9 +1601,15 @@ def run_rank(args):
     else:
         w = C4Workload(torch, ca, ctx, args.channels)
         elapsed, kern_ms = timed_steps(torch, ctx, w.step, args.steps, args.warmup)
-        g = w.gather()
+        if ctx.rank == 0 and args.dump_outputs:
+            # the audio every receiver is guaranteed to have written in one step (the chain carries its state across
+            # steps, and the pre-warm runs for a time, not a count: the words follow how many steps ran before)
+            extra["outputs_dumped"] = dump_outputs(torch, args.dump_outputs, {"chain_audio": w.aud[:, :w.T // 32]})
+        if args.full:
+            g = w.gather()
+            if ctx.rank == 0:
+                extra["gather"] = g
         if ctx.rank == 0:
-            extra["gather"] = g
             extra["chain_mode"] = w.mode
         chans, samples = w.C, w.T
         del w
@@ -1583,7 +1620,8 @@ def run_rank(args):
     if ctx.rank == 0:
         traffic = None
         if args.workload == "c3":
-            live = live_traffic() if (ctx.world == 1 and not args.no_secondary and not os.environ.get("CSDR_BENCH_NO_PMC")) else None
+            live = live_traffic() if (args.full and ctx.world == 1 and not args.no_secondary and
+                                      not os.environ.get("CSDR_BENCH_NO_PMC")) else None
             if live and live.get("k1"):
                 traffic = live["k1"]["bytes"]
                 extra["traffic_measured"] = dict({k: v for k, v in live["k1"].items() if k != "bytes"}, source=live["source"])
@@ -1604,7 +1642,7 @@ def run_rank(args):
             else:
                 traffic = profiled_traffic()
                 extra["traffic_measured"] = {"source": "profiles/traffic_latest.json (same kernel sources: hash checked)" if traffic else None}
-        cpu = cpu_baseline() if (ctx.world == 1 and not args.no_cpu) else None
+        cpu = cpu_baseline() if (args.full and ctx.world == 1 and not args.no_cpu) else None
         print(json.dumps(result_line(ctx, chans, samples, args.steps, args.warmup, elapsed, kern_ms, traffic, cpu,
                                      args.workload, extra)), flush=True)
     dist_finish(ctx)
@@ -1619,9 +1657,13 @@ def main(argv=None):
     ap.add_argument("--workload", choices=("c3", "c4"), default="c3")
     ap.add_argument("--channels", type=int, default=CHANNELS, help="channels per GPU")
     ap.add_argument("--blocks-per-wg", type=int, default=0)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-check", action="store_true", help="skip the post-timing parity spot check")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the distinct-filter and chain measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the parity spot checks, the counter traffic and the secondary measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, a seeded sample of channels)")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg (--full)")
+    ap.add_argument("--no-check", action="store_true", help="skip the post-timing parity spot check (--full)")
+    ap.add_argument("--no-secondary", action="store_true", help="skip the distinct-filter and chain measurements (--full)")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)     # tests: CPU stand-in workload, gloo
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)  # the counter passes of live_traffic()
     args = ap.parse_args(argv)

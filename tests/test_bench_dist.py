@@ -122,7 +122,7 @@ def test_two_ranks_rehearsed_on_one_gpu():
     host two RCCL ranks).  Started by bench.py's own --gpus spawn path."""
     env = dict(_clean_env(), CSDR_BENCH_ONE_GPU="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                        "--no-cpu"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--full", "--no-cpu"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
     assert len(lines) == 1
@@ -131,7 +131,7 @@ def test_two_ranks_rehearsed_on_one_gpu():
     g = line["chain_c4"]["gather"]
     assert g["bytes_to_rank0"] == 256 * (1 + (1 << 21) // 32) * 4 and g["ms"] > 0
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "c4", "--steps", "3",
-                        "--warmup", "2", "--no-cpu"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--warmup", "2", "--full", "--no-cpu"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = _json_lines(r.stdout)[0]
     assert line["n_gpus"] == 2 and "C4" in line["config"]["workload"] and line["gather"]["ms"] > 0
@@ -146,7 +146,7 @@ def test_one_rank_through_rccl():
     8-GPU run executes.  N > 1 over xGMI stays unmeasured (no multi-GPU box is available to the builder)."""
     env = dict(_clean_env(), CSDR_BENCH_FORCE_DIST="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c4", "--steps", "3", "--warmup", "2",
-                        "--no-cpu"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--full", "--no-cpu"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = _json_lines(r.stdout)[0]
     assert line["n_gpus"] == 1 and "C4" in line["config"]["workload"] and line["value"] > 0
@@ -154,7 +154,8 @@ def test_one_rank_through_rccl():
     assert line["ranks"]["ranks"][0]["device"] == 0
     g = line["gather"]
     assert g["backend"] == "nccl" and g["ms"] > 0 and g["messages_per_step"] == 4 and g["bytes_to_rank0"] == 0
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--no-cpu", "--no-secondary"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--full", "--no-cpu",
+                        "--no-secondary"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = _json_lines(r.stdout)[0]

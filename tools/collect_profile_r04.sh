@@ -12,6 +12,6 @@ rm -rf gpurun_out/prof_tl
 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/prof_tl -o t -- python3 tools/bench_c4_strict.py > gpurun_out/tl.log 2>&1
 python3 tools/trace_timeline.py gpurun_out/prof_tl 2 > profiles/r04_chain_timeline.txt 2>&1
 rm -rf gpurun_out/prof_tl
-python3 bench.py --steps 100 --warmup 20 > profiles/r04_bench_builder_run.json 2> gpurun_out/bench_r04.err
+python3 bench.py --full --steps 100 --warmup 20 > profiles/r04_bench_builder_run.json
 cp profiles/r04_* profiles/traffic_latest.json gpurun_out/ 2>/dev/null
 tail -c 600 profiles/r04_bench_builder_run.json

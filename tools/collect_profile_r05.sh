@@ -28,6 +28,6 @@ if rows:
         w = csv.DictWriter(f, fieldnames=list(rows[0].keys())); w.writeheader(); w.writerows(rows)
 PY
 rm -rf gpurun_out/prof_ffs
-python3 bench.py --steps 100 --warmup 20 > profiles/r05_bench_builder_run.json 2> gpurun_out/bench_r05.err
+python3 bench.py --full --steps 100 --warmup 20 > profiles/r05_bench_builder_run.json
 cp profiles/r05_* profiles/traffic_latest.json gpurun_out/ 2>/dev/null
 tail -c 600 profiles/r05_bench_builder_run.json

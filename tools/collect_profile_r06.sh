@@ -29,7 +29,7 @@ if rows:
         w = csv.DictWriter(f, fieldnames=list(rows[0].keys())); w.writeheader(); w.writerows(rows)
 PY
 rm -rf gpurun_out/prof_ffs
-python3 bench.py --steps 100 --warmup 20 > profiles/r06_bench_builder_run.json 2> gpurun_out/bench_r06.err
+python3 bench.py --full --steps 100 --warmup 20 > profiles/r06_bench_builder_run.json
 # one strict step drawn workgroup by workgroup (tools/wg_trace.py; the traced copy of the library is built by `python tools/wg_trace.py build`)
 if [ -f cutesdr_amd/_var/trace/libcutesdr_mi_trace.so ]; then
   CSDR_LIB_PATH=cutesdr_amd/_var/trace/libcutesdr_mi_trace.so python3 tools/wg_trace.py run strict profiles/r06_wgtrace_strict.json > gpurun_out/wgtrace_r06.log 2>&1
