@@ -131,7 +131,7 @@ struct csdr_resampler_batch {
     std::vector<double> times;
 };
 
-static int rs_build_sinc(float **d_sinc)
+int rs_build_sinc(float **d_sinc)
 {
     std::vector<float> tab(RS_LEN);
     for (int i = 0; i < RS_LEN; i++) {

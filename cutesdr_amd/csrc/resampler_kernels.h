@@ -33,3 +33,7 @@ struct ResampleBatchArgs {
 hipError_t resample_batch_launch(const ResampleBatchArgs &a, hipStream_t s);
 
 }  // namespace csdr
+
+// the 280001-entry windowed-sinc table on the current device (CFractResampler::Init, fractresampler.cpp:85-135);
+// capi_resampler.hip, shared with the batch sound sink
+int rs_build_sinc(float **d_sinc);

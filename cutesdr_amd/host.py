@@ -1059,3 +1059,70 @@ class CSoundOut(_Obj):
 
     def ppm_error(self):
         return lib().csdr_soundsink_get_ppm_error(self.h)
+
+
+class SoundSinkBatch(_Obj):
+    """C independent CSoundOut sinks (interface/soundout.cpp, non-blocking mode) behind the batched chain: every
+    receiver has its own user rate, volume, resampler state, queue and rate loop; PutOutQueue resamples every
+    receiver at its own rate in one device launch.  No blocking mode, no shard form."""
+    _destroy = "csdr_soundsink_batch_destroy"
+
+    def __init__(self, channels, stereo=False, device=0):
+        self.channels, self.stereo, self.device = int(channels), bool(stereo), device
+        self.h = check_ptr(lib().csdr_soundsink_batch_create(device, self.channels, int(stereo)),
+                           "csdr_soundsink_batch_create")
+        self._din = None
+
+    def ChangeUserDataRate(self, channel, UsrDataRate):
+        """channel < 0: every receiver"""
+        check(lib().csdr_soundsink_batch_change_user_data_rate(self.h, channel, UsrDataRate))
+
+    def SetVolume(self, channel, vol):
+        """channel < 0: every receiver"""
+        check(lib().csdr_soundsink_batch_set_volume(self.h, channel, vol))
+
+    def put_ptr(self, d_in, in_stride, counts, stream=None):
+        """d_in: device [channels][in_stride] fp32 (complex fp32 when stereo); returns the resampled counts"""
+        n = np.ascontiguousarray(counts, dtype=np.int32)
+        assert n.shape == (self.channels,)
+        k = np.zeros(self.channels, dtype=np.int32)
+        check(lib().csdr_soundsink_batch_put(self.h, C.c_void_p(d_in) if d_in else None, in_stride, _vp(n), _vp(k),
+                                             C.c_void_p(stream) if stream else None), "csdr_soundsink_batch_put")
+        return k
+
+    def PutOutQueue(self, rows, counts):
+        """rows: numpy [channels, T] (float mono, complex stereo) or a device tensor of that shape (complex64, or
+        float32 [channels, T, 2] for stereo); counts: the valid samples of each row.  Returns the resampled counts."""
+        if isinstance(rows, np.ndarray):
+            a = np.ascontiguousarray(rows, dtype=np.complex64 if self.stereo else np.float32)
+            assert a.shape[0] == self.channels
+            if self._din is None or self._din.nbytes < max(a.nbytes, 8):
+                self._din = DeviceBuffer(max(a.nbytes, 8), self.device)
+            self._din.upload(a)
+            return self.put_ptr(self._din.ptr, a.shape[1], counts)
+        import torch
+        assert rows.is_cuda and rows.shape[0] == self.channels
+        if self.stereo and not rows.is_complex():
+            assert rows.dtype == torch.float32 and rows.shape[-1] == 2 and rows.stride(-1) == 1 and rows.stride(1) == 2
+            stride = rows.stride(0) // 2
+        else:
+            assert rows.dtype == (torch.complex64 if self.stereo else torch.float32) and rows.stride(1) == 1
+            stride = rows.stride(0)
+        return self.put_ptr(rows.data_ptr(), stride, counts, torch.cuda.current_stream(rows.device).cuda_stream)
+
+    def GetOutQueue(self, channel, n):
+        out = np.zeros((n, 2) if self.stereo else n, dtype=np.int16)
+        check(lib().csdr_soundsink_batch_get(self.h, channel, n, _vp(out)), "csdr_soundsink_batch_get")
+        return out
+
+    def rate_correction(self, channel):
+        return lib().csdr_soundsink_batch_get_rate_correction(self.h, channel)
+
+    def ave_level(self, channel):
+        return lib().csdr_soundsink_batch_get_ave_level(self.h, channel)
+
+    def level(self, channel):
+        return check(lib().csdr_soundsink_batch_get_level(self.h, channel))
+
+    def ppm_error(self, channel):
+        return lib().csdr_soundsink_batch_get_ppm_error(self.h, channel)

@@ -509,6 +509,41 @@ int csdr_soundsink_get_level(csdr_soundsink *s);                             /* 
 int csdr_soundsink_get_ppm_error(csdr_soundsink *s);                         /* m_PpmError */
 
 /* ----------------------------------------------------------------------------------------
+ * Batch sound sink: C independent CSoundOut sinks (non-blocking mode) behind the batched chain, the last step from
+ * "rows of audio at group rates on the device" to "48 kHz int16 per listener".  Every receiver has its own user
+ * rate (m_OutRatio), volume, resampler state (m_FloatTime and the 28-sample history), 16384-entry queue and rate
+ * loop, with the single sink's rules; put resamples every receiver at its own rate in one launch.
+ * Threads: one producer calls put; any number of consumers call get and the accessors, at most one per receiver at a
+ * time.  Each receiver has its own mutex; put reads each receiver's rate and gain under it.  Nothing here waits on
+ * the whole device: put waits on `stream` only.
+ * Left out: blocking mode (Start(..., BlockingMode)) -- in a batch one full queue would stall every receiver -- and a
+ * shard form (a shard host makes one sink batch per shard device).
+ * -------------------------------------------------------------------------------------- */
+typedef struct csdr_soundsink_batch csdr_soundsink_batch;
+/* NULL without a HIP device (no CPU fallback) */
+csdr_soundsink_batch *csdr_soundsink_batch_create(int device, int channels, int stereo);
+void csdr_soundsink_batch_destroy(csdr_soundsink_batch *s);
+/* channel < 0: every receiver.  Clears only that receiver's queue; its resampler state is kept (soundout.cpp:155-175) */
+int csdr_soundsink_batch_change_user_data_rate(csdr_soundsink_batch *s, int channel, double rate);
+int csdr_soundsink_batch_set_volume(csdr_soundsink_batch *s, int channel, int vol);       /* :180-189; channel < 0: every receiver */
+/* PutOutQueue (:196-305, non-blocking branch) for every receiver at once.
+ * d_in:   device [channels][in_stride] fp32 mono rows, or complex fp32 rows of a stereo sink (in_stride in samples of
+ *         the row): the output of csdr_demod_batch_process / _process_stereo.
+ * n_in:   host array of per-receiver counts, each 0..8192 (csdr_demod_batch_out_count of each channel); a row with 0
+ *         produces nothing and changes nothing.
+ * n_out:  optional host array, receives the resampled count of each receiver.
+ * CSDR_EINVAL before any state changes if a row breaks a rule (n_in <= 8192, n_in / rate + 8 <= 16384).  Ordered
+ * behind `stream`; returns when every queue holds its new samples. */
+int csdr_soundsink_batch_put(csdr_soundsink_batch *s, const float *d_in, long long in_stride, const int *n_in,
+                             int *n_out, void *stream);
+/* GetOutQueue (:311-445) of one receiver: n samples, or n L/R pairs of a stereo sink; returns n */
+int csdr_soundsink_batch_get(csdr_soundsink_batch *s, int channel, int n, short *out);
+double csdr_soundsink_batch_get_rate_correction(csdr_soundsink_batch *s, int channel);    /* m_RateCorrection */
+double csdr_soundsink_batch_get_ave_level(csdr_soundsink_batch *s, int channel);          /* m_AveOutQLevel */
+int csdr_soundsink_batch_get_level(csdr_soundsink_batch *s, int channel);                 /* m_OutQLevel */
+int csdr_soundsink_batch_get_ppm_error(csdr_soundsink_batch *s, int channel);             /* m_PpmError */
+
+/* ----------------------------------------------------------------------------------------
  * Input-rate stages in front of the down-converter
  *
  * CNoiseProc (dsp/noiseproc.h:23-58): impulse blanker.  setup = SetupBlanker (noiseproc.cpp:78-119,
