@@ -1,7 +1,10 @@
 // capi_fft.hip -- C ABI for CFft (dsp/fft.h:24-85): display spectrum + plain transforms.
 #include "capi_common.hpp"
 #include "spectrum_kernels.h"
+#include "display_stream_kernels.h"
+#include "display_plan.hpp"
 #include "host_math.hpp"
+#include <cstdint>
 #include <cstring>
 #include <vector>
 
@@ -31,6 +34,12 @@ struct csdr_fft_batch {
     // the readers (GetScreenIntegerFFTData from the GUI thread, fft.cpp:308-410) wait for THIS object's last
     // PutInDisplayFFT only -- the copy rides on that call's stream -- not for whatever else the device is running
     hipStream_t last_stream = nullptr; bool have_stream = false;
+    // the display stream of ProcessIQData (sdrinterface.cpp:889-907): frame position, skip counter and gate, one set for
+    // every channel (each call brings the same samples to every row); the partial frame itself stays on the device
+    DisplayState ds;
+    double disp_fs = 0; int disp_rate = 0;       // m_SampleRate and m_MaxDisplayRate (set_params re-derives the skip value)
+    float *d_carry = nullptr;                    // [channels][N] complex: m_DataBuf of each channel, DC-corrected
+    float *d_stage = nullptr; size_t stage_cap = 0;   // [channels][used frames][N] complex: the frames a call uses
 };
 
 // device -> host behind the object's own work: on the stream of its last put_display (until round 5: hipDeviceSynchronize)
@@ -44,7 +53,7 @@ static int fft_read(csdr_fft_batch *f, void *dst, const void *src, size_t bytes)
 
 static void fft_free_dev(csdr_fft_batch *f)
 {
-    float **ps[] = {&f->d_win, &f->d_tw1, &f->d_tw2, &f->d_sum, &f->d_pwr, &f->d_ave, &f->d_work};
+    float **ps[] = {&f->d_win, &f->d_tw1, &f->d_tw2, &f->d_sum, &f->d_pwr, &f->d_ave, &f->d_work, &f->d_carry};
     for (auto p : ps) { if (*p) (void)hipFree(*p); *p = nullptr; }
 }
 
@@ -77,6 +86,7 @@ static int fft_set_params(csdr_fft_batch *f, int size, int invert, double db_com
         CSDR_HIP(hipMalloc((void **)&f->d_sum, nb));
         CSDR_HIP(hipMalloc((void **)&f->d_pwr, nb));
         CSDR_HIP(hipMalloc((void **)&f->d_ave, nb));
+        CSDR_HIP(hipMalloc((void **)&f->d_carry, nb * 2));
         if (l2 < 11 || l2 > 14) CSDR_HIP(hipMalloc((void **)&f->d_work, nb * 4));   // [2][channels][N] complex
         CSDR_HIP(hipMemset(f->d_pwr, 0, nb));
         f->kb = f->db_comp - 20 * std::log10((double)n * refc::FFT_K_AMPMAX / 2.0);
@@ -129,13 +139,21 @@ void csdr_fft_batch_destroy(csdr_fft_batch *f)
     if (f->d_over) (void)hipFree(f->d_over);
     if (f->d_scr) (void)hipFree(f->d_scr);
     if (f->d_part) (void)hipFree(f->d_part);
+    if (f->d_stage) (void)hipFree(f->d_stage);
     delete f;
 }
 int csdr_fft_batch_set_params(csdr_fft_batch *f, int size, int invert, double db_comp, double fs)
 {
     if (!f) return fail(CSDR_EINVAL, "bad handle");
     if (!device_ok(f->device)) return CSDR_EHIP;
-    return fft_set_params(f, size, invert, db_comp, fs);
+    const int rc = fft_set_params(f, size, invert, db_comp, fs);
+    if (rc) return rc;
+    // CSdrInterface::SetFftSize (sdrinterface.cpp:709-718): m_FftBufPos = 0, then SetMaxDisplayRate for the new size at
+    // m_SampleRate -- the rate SetFFTParams is given too, so fs here
+    f->ds.pos = 0;
+    if (fs > 0) f->disp_fs = fs;
+    if (f->disp_rate > 0) { f->ds.skip = display_skip_value(f->disp_fs, f->size, f->disp_rate); f->ds.counter = 0; }
+    return CSDR_OK;
 }
 int csdr_fft_batch_set_ave(csdr_fft_batch *f, int ave)
 {   // CFft::SetFFTAve (fft.cpp:103-113)
@@ -152,14 +170,23 @@ int csdr_fft_batch_reset(csdr_fft_batch *f)
 }
 int csdr_fft_batch_size(csdr_fft_batch *f) { return f ? f->size : fail(CSDR_EINVAL, "bad handle"); }
 
-/* nframes frames of `size` samples per channel, back to back in each row; asynchronous */
-int csdr_fft_batch_put_display(csdr_fft_batch *f, const float *d_in, long long in_stride, int nframes, void *stream)
+// where the frames of a display-stream launch come from (spectrum_stream_launch, 2048 ... 8192 points): frame f at
+// sample start + f step of the call, DC subtracted, from fp32 rows or from datagrams (pk)
+struct FrameSrc {
+    long long start, step;
+    const double *dc;
+    const unsigned char *pk; long pk_stride; int pkt_len;
+};
+
+// PutInDisplayFFT of nframes frames of `size` samples per channel, back to back in each row (src == nullptr), or as src
+// says; asynchronous.  clear_over = false: a later launch of the same call -- the overload flag stays what the call's
+// earlier frames left.
+static int fft_put_frames(csdr_fft_batch *f, const float *d_in, long long in_stride, int nframes, void *stream,
+                          const FrameSrc *src = nullptr, bool clear_over = true)
 {
-    if (!f || !d_in || nframes < 0) return fail(CSDR_EINVAL, "bad argument");
-    if (nframes == 0) return CSDR_OK;
-    if (!device_ok(f->device)) return CSDR_EHIP;
     f->last_stream = (hipStream_t)stream; f->have_stream = true;
-    CSDR_HIP(hipMemsetAsync(f->d_over, 0, sizeof(int) * f->channels, (hipStream_t)stream));   // m_Overload = FALSE
+    if (clear_over)
+        CSDR_HIP(hipMemsetAsync(f->d_over, 0, sizeof(int) * f->channels, (hipStream_t)stream));   // m_Overload = FALSE
     SpectrumArgs a;
     a.in = d_in; a.in_stride = in_stride; a.win = f->d_win; a.tw1 = f->d_tw1; a.tw2 = f->d_tw2;
     a.sum = f->d_sum; a.pwr = f->d_pwr; a.ave = f->d_ave; a.counters = f->d_cnt; a.overload = f->d_over;
@@ -190,10 +217,117 @@ int csdr_fft_batch_put_display(csdr_fft_batch *f, const float *d_in, long long i
         }
     }
     a.kc = (float)f->kc; a.kb = f->kb;
+    a.frame_start = src ? src->start : 0; a.frame_step = src ? src->step : f->size;
+    a.dc = src ? src->dc : nullptr;
+    a.pk = src ? src->pk : nullptr; a.pk_stride = src ? src->pk_stride : 0;
     const int l2 = log2_of(f->size);
-    if (l2 >= 11 && l2 <= 14) CSDR_HIP(spectrum_launch(l2, a, (hipStream_t)stream));
+    if (src) CSDR_HIP(spectrum_stream_launch(l2, a, src->pkt_len, (hipStream_t)stream));
+    else if (l2 >= 11 && l2 <= 14) CSDR_HIP(spectrum_launch(l2, a, (hipStream_t)stream));
     else CSDR_HIP(spectrum_generic_launch(l2, a, f->d_work, (hipStream_t)stream));
     return CSDR_OK;
+}
+/* nframes frames of `size` samples per channel, back to back in each row; asynchronous */
+int csdr_fft_batch_put_display(csdr_fft_batch *f, const float *d_in, long long in_stride, int nframes, void *stream)
+{
+    if (!f || !d_in || nframes < 0) return fail(CSDR_EINVAL, "bad argument");
+    if (nframes == 0) return CSDR_OK;
+    if (!device_ok(f->device)) return CSDR_EHIP;
+    return fft_put_frames(f, d_in, in_stride, nframes, stream);
+}
+
+/* ---- the display stream (ProcessIQData, sdrinterface.cpp:886-907) ---- */
+// n samples of every row (fp32 rows d_in, or the datagrams of `wire`) appended to the stream.  The frames the plan uses
+// are read where they lie: at 2048 ... 8192 points by the spectrum kernels' stream loaders (datagrams decoded and DC
+// subtracted in the frame load); plain fp32 rows without DC whose used frames lie back to back, at every size, by the
+// plain launch in place.  The rest is gathered, DC-corrected, into the staging rows first: the frame that begins in the
+// carried partial frame, and at the other sizes (16384, where the stream loaders spill, and the multi-launch sizes) every
+// used frame.  The partial frame at the end stays in d_carry.
+static int fft_put_stream(csdr_fft_batch *f, const float *d_in, long long in_stride, const WireIn &wire, long long n,
+                          const double *d_dc, void *stream)
+{
+    if (n == 0) return 0;
+    if (!device_ok(f->device)) return CSDR_EHIP;
+    const int N = f->size, l2 = log2_of(N);
+    const bool loaders = l2 >= 11 && l2 <= 13;
+    const DisplayPlan p = display_plan(f->ds, n, N);
+    hipStream_t st = (hipStream_t)stream;
+    StreamSrc a;
+    a.in = d_in; a.in_stride = (long)in_stride; a.wire = wire; a.dc = d_dc;
+    a.carry = f->d_carry; a.pos = f->ds.pos; a.carry_stride = N; a.channels = f->channels;
+    long long start = p.start;
+    int left = p.count;
+    bool clear_over = true;
+    auto in_place = [&](int k) { return !wire.pk && !d_dc && start >= 0 && (k == 1 || p.step == N); };
+    if (left > 0 && !in_place(left) && (start < 0 || !loaders)) {
+        const int ng = loaders ? 1 : left;
+        const size_t need = (size_t)f->channels * ng * N * 2;
+        if (need > f->stage_cap) {
+            CSDR_HIP(hipStreamSynchronize(st));
+            if (f->d_stage) (void)hipFree(f->d_stage);
+            f->d_stage = nullptr; f->stage_cap = 0;
+            CSDR_HIP(hipMalloc((void **)&f->d_stage, need * 4));
+            f->stage_cap = need;
+        }
+        CSDR_HIP(display_gather_launch(a, start, p.step, ng, N, f->d_stage, st));
+        const int rc = fft_put_frames(f, f->d_stage, (long long)ng * N, ng, stream);
+        if (rc) return rc;
+        clear_over = false; start += (long long)ng * p.step; left -= ng;
+    }
+    if (left > 0) {
+        int rc;
+        if (in_place(left)) rc = fft_put_frames(f, d_in + 2 * start, in_stride, left, stream, nullptr, clear_over);
+        else {
+            const FrameSrc src{start, p.step, d_dc, wire.pk, wire.chan_stride, wire.pkt_len};
+            rc = fft_put_frames(f, d_in, in_stride, left, stream, &src, clear_over);
+        }
+        if (rc) return rc;
+    }
+    // m_DataBuf after the call: the call's samples appended when no frame completed, else the last next.pos of them
+    if (f->ds.pos + n < N) CSDR_HIP(display_carry_launch(a, f->d_carry, f->ds.pos, 0, (int)n, st));
+    else CSDR_HIP(display_carry_launch(a, f->d_carry, 0, n - p.next.pos, p.next.pos, st));
+    f->ds = p.next;
+    return p.count;
+}
+
+int csdr_fft_batch_set_display_rate(csdr_fft_batch *f, double sample_rate, int max_display_rate, int gated)
+{   // CSdrInterface::SetMaxDisplayRate (sdrinterface.h:112-114), and the m_ScreenUpateFinished handshake on or off
+    if (!f) return fail(CSDR_EINVAL, "bad handle");
+    if (!(sample_rate > 0) || max_display_rate < 1) return fail(CSDR_EINVAL, "sample rate > 0, display rate >= 1");
+    f->disp_fs = sample_rate; f->disp_rate = max_display_rate;
+    f->ds.skip = display_skip_value(sample_rate, f->size, max_display_rate);
+    f->ds.counter = 0;
+    f->ds.gated = gated != 0;
+    return CSDR_OK;
+}
+int csdr_fft_batch_screen_update_done(csdr_fft_batch *f)
+{   // CSdrInterface::ScreenUpdateDone (sdrinterface.h:67)
+    if (!f) return fail(CSDR_EINVAL, "bad handle");
+    f->ds.ready = 1;
+    return CSDR_OK;
+}
+int csdr_fft_batch_stream_reset(csdr_fft_batch *f)
+{   // CSdrInterface::StartSdr (sdrinterface.cpp:512, 591): m_FftBufPos = 0, m_ScreenUpateFinished = TRUE
+    if (!f) return fail(CSDR_EINVAL, "bad handle");
+    f->ds.pos = 0; f->ds.ready = 1;
+    return CSDR_OK;
+}
+int csdr_fft_batch_put_display_stream(csdr_fft_batch *f, const float *d_in, long long in_stride, int n,
+                                      const double *d_dc, void *stream)
+{
+    if (!f || !d_in || n < 0 || in_stride < n) return fail(CSDR_EINVAL, "bad argument");
+    if ((uintptr_t)d_in & 7) return fail(CSDR_EINVAL, "d_in must be 8-byte aligned");
+    return fft_put_stream(f, d_in, in_stride, WireIn{nullptr, 0, 0, 0}, n, d_dc, stream);
+}
+int csdr_fft_batch_put_display_packets(csdr_fft_batch *f, const void *d_packets, int npackets, int pkt_len,
+                                       const double *d_dc, void *stream)
+{   // the datagram rules of csdr_demod_batch_process_packets
+    if (!f || !d_packets || npackets < 0) return fail(CSDR_EINVAL, "bad argument");
+    if (pkt_len != 1028 && pkt_len != 1444) return fail(CSDR_EINVAL, "packet length %d", pkt_len);
+    if ((long)npackets * pkt_len >= (1l << 31)) return fail(CSDR_EINVAL, "a channel's datagrams of one call must stay below 2 GiB");
+    if ((uintptr_t)d_packets & 3) return fail(CSDR_EINVAL, "datagram buffer must be 4-byte aligned");
+    const int per = pkt_len == 1444 ? 240 : 256;
+    return fft_put_stream(f, nullptr, 0, WireIn{(const unsigned char *)d_packets, (long)npackets * pkt_len, pkt_len, per},
+                          (long long)npackets * per, d_dc, stream);
 }
 /* copy of m_pFFTAveBuf of one channel (bels, display order), synchronises */
 int csdr_fft_batch_get_ave(csdr_fft_batch *f, int channel, float *out)

@@ -294,6 +294,18 @@ int csdr_ingest_spurcal(int device, const float *d_iq, long long in_stride, int 
     CSDR_HIP(spurcal_launch(d_iq, in_stride, channels, n, d_dc, (hipStream_t)stream));
     return CSDR_OK;
 }
+/* NcoSpurCalibrate on datagrams: spurcal_kernel with the samples decoded in its loads, no fp32 copy of the call */
+int csdr_ingest_spurcal_packets(int device, const void *d_packets, int channels, int npackets, int pkt_len, double *d_dc,
+                                void *stream)
+{
+    if (!d_packets || !d_dc || channels < 1 || npackets < 0) return fail(CSDR_EINVAL, "bad argument");
+    if (pkt_len != 1028 && pkt_len != 1444) return fail(CSDR_EINVAL, "packet length %d", pkt_len);
+    if ((long)npackets * pkt_len >= (1l << 31)) return fail(CSDR_EINVAL, "a channel's datagrams of one call must stay below 2 GiB");
+    if ((uintptr_t)d_packets & 3) return fail(CSDR_EINVAL, "datagram buffer must be 4-byte aligned");
+    if (!device_ok(device)) return CSDR_EHIP;
+    CSDR_HIP(spurcal_packets_launch((const unsigned char *)d_packets, channels, npackets, pkt_len, d_dc, (hipStream_t)stream));
+    return CSDR_OK;
+}
 int csdr_ingest_spurcal_host(int device, int n, const double *in_iq, double *dc_iq)
 {
     if (!in_iq || !dc_iq || n < 0) return fail(CSDR_EINVAL, "bad argument");

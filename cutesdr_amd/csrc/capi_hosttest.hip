@@ -5,6 +5,7 @@
 #include "host_math.hpp"
 #include "dc_host.hpp"
 #include "pc_host.hpp"
+#include "display_plan.hpp"
 #include "fastfir_kernels.h"
 #include <cstring>
 
@@ -73,6 +74,21 @@ void csdr__host_agc_params(int on, int hang, int thresh, int manual, int slope, 
     out12[0] = d.knee; out12[1] = d.gain_slope; out12[2] = d.fixed_gain; out12[3] = d.manual_gain;
     out12[4] = d.att_rise; out12[5] = d.att_fall; out12[6] = d.dec_rise; out12[7] = d.dec_fall;
     out12[8] = d.dly_n; out12[9] = d.win_n; out12[10] = d.hang_time; out12[11] = 0;
+}
+
+// the display stream's frame planner (display_plan.hpp): state in = {pos, skip, counter, gated, ready};
+// out = {start, step, count, pos, skip, counter, gated, ready}
+void csdr__host_display_plan(const int *state5, long long n, int N, long long *out8)
+{
+    DisplayState s;
+    s.pos = state5[0]; s.skip = state5[1]; s.counter = state5[2]; s.gated = state5[3]; s.ready = state5[4];
+    const DisplayPlan p = display_plan(s, n, N);
+    out8[0] = p.start; out8[1] = p.step; out8[2] = p.count;
+    out8[3] = p.next.pos; out8[4] = p.next.skip; out8[5] = p.next.counter; out8[6] = p.next.gated; out8[7] = p.next.ready;
+}
+int csdr__host_display_skip_value(double sample_rate, int fft_size, int max_display_rate)
+{
+    return display_skip_value(sample_rate, fft_size, max_display_rate);
 }
 
 }  // extern "C"

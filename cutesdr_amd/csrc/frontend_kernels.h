@@ -49,5 +49,8 @@ hipError_t unpack_launch(const unsigned char *pk, long chan_stride_bytes, int ch
                          float *out, long out_stride, const double *dc, hipStream_t stream);
 // dc[ch] <- running means of I and Q over n more samples, alpha = 1e-5 (sdrinterface.cpp:829-848)
 hipError_t spurcal_launch(const float *iq, long in_stride, int channels, int n, double *dc, hipStream_t stream);
+// the same over the samples of [channels][npackets][pkt_len] datagrams, decoded in the load (wire_format.hpp)
+hipError_t spurcal_packets_launch(const unsigned char *pk, int channels, int npackets, int pkt_len, double *dc,
+                                  hipStream_t stream);
 
 }  // namespace csdr

@@ -777,18 +777,19 @@ hipError_t unpack_launch(const unsigned char *pk, long chan_stride_bytes, int ch
 }
 
 // ---------------- NCO spur (DC) estimate ----------------
-// y_n = (1-a)^n y_0 + a * sum_k (1-a)^(n-1-k) x_k : a weighted reduction, one workgroup per channel
-__global__ __launch_bounds__(256)
-void spurcal_kernel(const float *iq, long in_stride, int n, double *dc)
+// y_n = (1-a)^n y_0 + a * sum_k (1-a)^(n-1-k) x_k : a weighted reduction, one workgroup per channel.
+// The sample source is a template input: fp32 rows (spurcal_kernel) or datagrams decoded in the load
+// (spurcal_packets_kernel); a decoded value is exact in fp32, so both give the same doubles for the same samples.
+template <class Load>
+__device__ __forceinline__ void spurcal_body(Load x, int n, double *dc)
 {
     __shared__ double red[2][256];
     const int ch = blockIdx.x, t = threadIdx.x;
-    const f2 *x = reinterpret_cast<const f2 *>(iq) + (long)ch * in_stride;
     const double a = 1.0 / 100000.0, l1 = log1p(-a);
     double si = 0.0, sq = 0.0;
     for (long k = t; k < n; k += 256) {
         const double wgt = exp(l1 * (double)(n - 1 - k));
-        const f2 v = x[k];
+        const f2 v = x(k);
         si += wgt * (double)v.x; sq += wgt * (double)v.y;
     }
     red[0][t] = si; red[1][t] = sq;
@@ -803,11 +804,33 @@ void spurcal_kernel(const float *iq, long in_stride, int n, double *dc)
         dc[2 * ch + 1] = decay * dc[2 * ch + 1] + a * red[1][0];
     }
 }
+__global__ __launch_bounds__(256)
+void spurcal_kernel(const float *iq, long in_stride, int n, double *dc)
+{
+    const f2 *x = reinterpret_cast<const f2 *>(iq) + (long)blockIdx.x * in_stride;
+    spurcal_body([&](long k) { return x[k]; }, n, dc);
+}
+__global__ __launch_bounds__(256)
+void spurcal_packets_kernel(WireIn w, int n, double *dc)
+{
+    const unsigned char *chan = w.pk + (long)blockIdx.x * w.chan_stride;
+    spurcal_body([&](long k) { const wf2 v = wire_sample(chan, w.pkt_len, k); return f2{v.x, v.y}; }, n, dc);
+}
 
 hipError_t spurcal_launch(const float *iq, long in_stride, int channels, int n, double *dc, hipStream_t stream)
 {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(spurcal_kernel, dim3(channels), dim3(256), 0, stream, iq, in_stride, n, dc);
+    return hipGetLastError();
+}
+hipError_t spurcal_packets_launch(const unsigned char *pk, int channels, int npackets, int pkt_len, double *dc,
+                                  hipStream_t stream)
+{
+    const int per = pkt_len == 1444 ? 240 : 256;
+    const int n = npackets * per;
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(spurcal_packets_kernel, dim3(channels), dim3(256), 0, stream,
+                       WireIn{pk, (long)npackets * pkt_len, pkt_len, per}, n, dc);
     return hipGetLastError();
 }
 

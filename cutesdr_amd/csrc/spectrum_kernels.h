@@ -17,8 +17,16 @@ struct SpectrumArgs {
     float *part;                        // [channels][nparts][N] partial sums, nparts > 1 only
     float *alpha;                       // [channels][nparts] group weights + [channels] average count after the call (nparts > 1)
     float kc; double kb;
+    // the display stream's loaders (spectrum_stream_launch only; the plain launch reads frame f at in + f N):
+    // frame f of a channel is stream samples frame_start + f frame_step + i (frame_start >= 0), minus dc
+    long frame_start, frame_step;
+    const double *dc;                   // optional [channels][2] (I, Q), subtracted as unpack_kernel does
+    const unsigned char *pk; long pk_stride;   // datagrams [channels][pk_stride] bytes (wire_format.hpp), or nullptr: `in`
 };
 hipError_t spectrum_launch(int log2n, const SpectrumArgs &a, hipStream_t stream);
+// 2048 ... 8192 points with the frame load of the display stream: fp32 rows (a.pk == nullptr) or datagrams of
+// pkt_len 1028 / 1444 decoded in the load, frames at frame_start + f frame_step, DC subtracted
+hipError_t spectrum_stream_launch(int log2n, const SpectrumArgs &a, int pkt_len, hipStream_t stream);
 
 // plain transform of one N-point block: sign=+1 CFft::FwdFFT, -1 RevFFT; natural order in/out
 hipError_t fft_plain_launch(int log2n, int sign, const float *in, float *out, const float *tw1,

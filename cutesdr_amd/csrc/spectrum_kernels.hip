@@ -10,6 +10,7 @@
 #define CSDR_FMA_BFLY 1          // FMA-form decimation-in-time butterflies (fft_core.hpp)
 #define CSDR_PLAIN_CONST_FMA 1
 #include "launch_once.hpp"
+#include <type_traits>
 #include "fft_core.hpp"
 #include "spectrum_kernels.h"
 #include "ref_constants.hpp"
@@ -17,6 +18,66 @@
 namespace csdr {
 
 #define K3_SB() __builtin_amdgcn_sched_barrier(0)
+
+// ---- frame loaders: where sample i of a channel's frame f comes from.  fetch() issues the load and returns the raw
+// value, decode() turns it into the complex sample where it is consumed (a prefetched frame's decode must not make the
+// prefetch wait for its own loads).
+struct RowLoad {                          // csdr_fft_batch_put_display: frames back to back from the row's start
+    typedef v2f Raw;
+    const v2f *in;
+    __device__ __forceinline__ RowLoad(const SpectrumArgs &a, int ch)
+        : in(reinterpret_cast<const v2f *>(a.in) + (long)ch * a.in_stride) {}
+    template <int N> __device__ __forceinline__ Raw fetch(int f, int i) const { return in[(long)f * N + i]; }
+    __device__ __forceinline__ v2f decode(Raw r) const { return r; }
+};
+// the display stream (sdrinterface.cpp:889-894): frame f at sample frame_start + f frame_step of the call, minus the DC
+// offset with unpack_kernel's arithmetic (a missing dc subtracts 0.0: the same words)
+struct StreamDc {
+    double di, dq;
+    __device__ __forceinline__ StreamDc(const SpectrumArgs &a, int ch)
+        : di(a.dc ? a.dc[2 * ch] : 0.0), dq(a.dc ? a.dc[2 * ch + 1] : 0.0) {}
+    // (opaque: the transform gets the sample as it gets a loaded one -- left visible, the decode changed which of the
+    // first butterflies' multiplies and adds the compiler fused, and the words differed from the fp32-row forms)
+    __device__ __forceinline__ v2f sub(float x, float y) const { return opaque(v2f{(float)((double)x - di), (float)((double)y - dq)}); }
+};
+struct RowDcLoad {                        // fp32 rows
+    typedef v2f Raw;
+    const v2f *in; long start, step; StreamDc dc;
+    __device__ __forceinline__ RowDcLoad(const SpectrumArgs &a, int ch)
+        : in(reinterpret_cast<const v2f *>(a.in) + (long)ch * a.in_stride), start(a.frame_start), step(a.frame_step), dc(a, ch) {}
+    template <int N> __device__ __forceinline__ Raw fetch(int f, int i) const { return in[start + (long)f * step + i]; }
+    __device__ __forceinline__ v2f decode(Raw r) const { return dc.sub(r.x, r.y); }
+};
+struct Raw24 { unsigned h0, h1, h2; };
+template <int PKT>                        // datagrams (wire_format.hpp): 1028 = 256 x 16 bit, 1444 = 240 x 24 bit
+struct WireLoad {
+    typedef typename std::conditional<PKT == 1444, Raw24, unsigned>::type Raw;
+    const unsigned char *chan; long start, step; StreamDc dc;
+    __device__ __forceinline__ WireLoad(const SpectrumArgs &a, int ch)
+        : chan(a.pk + (long)ch * a.pk_stride), start(a.frame_start), step(a.frame_step), dc(a, ch) {}
+    template <int N> __device__ __forceinline__ Raw fetch(int f, int i) const
+    {
+        const unsigned s = (unsigned)(start + (long)f * step) + (unsigned)i;      // < 2^31: a call stays below 2 GiB
+        if constexpr (PKT == 1444) {
+            const unsigned q = s / 240u, j = s - q * 240u;
+            const unsigned short *h = reinterpret_cast<const unsigned short *>(chan + (q * 1444u + 4u + 6u * j));
+            return Raw24{h[0], h[1], h[2]};
+        } else {
+            const unsigned q = s >> 8, j = s & 255u;
+            return *reinterpret_cast<const unsigned *>(chan + (q * 1028u + 4u + 4u * j));
+        }
+    }
+    __device__ __forceinline__ v2f decode(Raw r) const
+    {
+        if constexpr (PKT == 1444) {              // wire_sample: value << 8 in an int32, / 65536 (exact)
+            const int vi = (int)((r.h0 << 8) | ((r.h1 & 0xffu) << 24));
+            const int vq = (int)(((r.h1 >> 8) << 8) | (r.h2 << 16));
+            return dc.sub((float)vi * (1.0f / 65536.0f), (float)vq * (1.0f / 65536.0f));
+        } else {
+            return dc.sub((float)(short)(r & 0xffffu), (float)(short)(r >> 16));
+        }
+    }
+};
 
 template <int LOG2N>
 struct SpecCfg {
@@ -141,7 +202,7 @@ __device__ __forceinline__ void fft_fwd_passes(v2f (&x)[32], v2f *lds, const v2f
 #ifndef CSDR_SPEC_WAVES
 #define CSDR_SPEC_WAVES 1
 #endif
-template <int LOG2N>
+template <int LOG2N, class Ld = RowLoad>
 __global__ __launch_bounds__(SpecCfg<LOG2N>::T) __attribute__((amdgpu_waves_per_eu(CSDR_SPEC_WAVES)))
 void spectrum_kernel(SpectrumArgs a)
 {
@@ -159,7 +220,7 @@ void spectrum_kernel(SpectrumArgs a)
     v2f w1[G];
 #pragma unroll
     for (int e = 0; e < G; e++) w1[e] = reinterpret_cast<const v2f *>(a.tw1)[Cfg::col(t, e)];
-    const v2f *in = reinterpret_cast<const v2f *>(a.in) + (long)ch * a.in_stride;
+    const Ld ld(a, ch);
     float *sum = a.sum + (long)ch * N, *pwr = a.pwr + (long)ch * N, *ave = a.ave + (long)ch * N;
     int ave_count = a.counters[2 * ch], total = a.counters[2 * ch + 1];
     total += f0;                                              // counters at this group's first frame
@@ -182,14 +243,13 @@ void spectrum_kernel(SpectrumArgs a)
     // with the prefetched frame on top of the points and the running sums the kernel spilled 80 of them -- 324 bytes
     // of scratch per lane -- and ran at 1.5 TB/s; the second wave of the SIMD hides the loads instead: round 4)
     constexpr bool PREFETCH = LOG2N < 14;
-    v2f nxt[PREFETCH ? 32 : 1];
+    typename Ld::Raw nxt[PREFETCH ? 32 : 1];
     auto fetch = [&](int f) {
         if constexpr (PREFETCH) {
-            const v2f *src = in + (long)f * N;
 #pragma unroll
             for (int e = 0; e < G; e++)
 #pragma unroll
-                for (int n1 = 0; n1 < R0; n1++) nxt[e * R0 + n1] = src[1024 * n1 + Cfg::col(t, e)];
+                for (int n1 = 0; n1 < R0; n1++) nxt[e * R0 + n1] = ld.template fetch<N>(f, 1024 * n1 + Cfg::col(t, e));
         }
     };
     if (f0 < f1) fetch(f0);
@@ -201,7 +261,7 @@ void spectrum_kernel(SpectrumArgs a)
             for (int n1 = 0; n1 < R0; n1++) {
                 const int i = 1024 * n1 + Cfg::col(t, e);
                 v2f s;
-                if constexpr (PREFETCH) s = nxt[e * R0 + n1]; else s = in[(long)f * N + i];
+                if constexpr (PREFETCH) s = ld.decode(nxt[e * R0 + n1]); else s = ld.decode(ld.template fetch<N>(f, i));
                 const float w = a.win[i];
                 if (s.x > refc::FFT_OVER_LIMIT_F) over = 1;                     // OVER_LIMIT, fft.cpp:30,275
                 x[e * R0 + n1] = v2f{w * s.y, w * s.x};           // I/Q swapped, fft.cpp:280-281
@@ -253,6 +313,7 @@ constexpr int SPEC16_LDS = (4096 + 2 * 256) * 8;
 #ifndef CSDR_SPEC16_WAVES
 #define CSDR_SPEC16_WAVES 1
 #endif
+template <class Ld = RowLoad>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CSDR_SPEC16_WAVES)))
 void spectrum16_kernel(SpectrumArgs a)
 {
@@ -263,7 +324,7 @@ void spectrum16_kernel(SpectrumArgs a)
     const int f0 = (int)((long)a.nframes * part / a.nparts), f1 = (int)((long)a.nframes * (part + 1) / a.nparts);
     const v2f *tw1 = reinterpret_cast<const v2f *>(a.tw1);           // W_N^n, n < 1024
     const v2f wA = tw1[t], wB = tw1[16 * (t & 15)];                  // W_N^t and W_256^c
-    const v2f *in = reinterpret_cast<const v2f *>(a.in) + (long)ch * a.in_stride;
+    const Ld ld(a, ch);
     float *sum = a.sum + (long)ch * N, *pwr = a.pwr + (long)ch * N, *ave = a.ave + (long)ch * N;
     int ave_count = a.counters[2 * ch], total = a.counters[2 * ch + 1];
     total += f0;                                              // counters at this group's first frame
@@ -280,18 +341,17 @@ void spectrum16_kernel(SpectrumArgs a)
     });
     v2f pwA[16];                              // W_N^{t ka}: resident (30 registers; pass B's are recomputed per frame)
     twiddle_powers<16>(wA, pwA);
-    v2f nxt[16];
+    typename Ld::Raw nxt[16];
     auto fetch = [&](int f) {
-        const v2f *src = in + (long)f * N + t;
 #pragma unroll
-        for (int q = 0; q < 16; q++) nxt[q] = src[256 * q];
+        for (int q = 0; q < 16; q++) nxt[q] = ld.template fetch<N>(f, t + 256 * q);
     };
     if (f0 < f1) fetch(f0);
     for (int f = f0; f < f1; f++) {
         v2f x[16];
         static_for<0, 16>([&](auto Q) {
             constexpr int q = Q.value;
-            const v2f s_ = nxt[q];
+            const v2f s_ = ld.decode(nxt[q]);
             if (s_.x > refc::FFT_OVER_LIMIT_F) over = 1;                        // OVER_LIMIT, fft.cpp:30,275
             x[bitrev<16>(q)] = v2f{wn[q] * s_.y, wn[q] * s_.x};    // I/Q swapped, fft.cpp:280-281
         });
@@ -358,6 +418,7 @@ void spectrum16_kernel(SpectrumArgs a)
 // eight points b of a COLUMN PAIR per thread (thread (ka, c pair): 2 x 8 points, twiddle W_128^{c kb}), pass C the 16
 // consecutive points of row t = 8 ka + kb -> bin ka + 16 kb + 128 kc.  B -> C inside the eight threads that own ka.
 constexpr int SPEC8_LDS = (2048 + 2 * 128) * 8;
+template <class Ld = RowLoad>
 __global__ __launch_bounds__(128)
 void spectrum8_kernel(SpectrumArgs a)
 {
@@ -369,7 +430,7 @@ void spectrum8_kernel(SpectrumArgs a)
     const v2f *tw1 = reinterpret_cast<const v2f *>(a.tw1);           // W_N^n, n < 1024
     const int cp = t & 7;                                             // pass B: columns 2 cp, 2 cp + 1 of ka = t >> 3
     const v2f wA = tw1[t], wB0 = tw1[16 * (2 * cp)], wB1 = tw1[16 * (2 * cp + 1)];   // W_N^t; W_128^c = W_N^{16 c}
-    const v2f *in = reinterpret_cast<const v2f *>(a.in) + (long)ch * a.in_stride;
+    const Ld ld(a, ch);
     float *sum = a.sum + (long)ch * N, *pwr = a.pwr + (long)ch * N, *ave = a.ave + (long)ch * N;
     int ave_count = a.counters[2 * ch], total = a.counters[2 * ch + 1];
     total += f0;                                              // counters at this group's first frame
@@ -386,18 +447,17 @@ void spectrum8_kernel(SpectrumArgs a)
     });
     v2f pwA[16];
     twiddle_powers<16>(wA, pwA);
-    v2f nxt[16];
+    typename Ld::Raw nxt[16];
     auto fetch = [&](int f) {
-        const v2f *src = in + (long)f * N + t;
 #pragma unroll
-        for (int q = 0; q < 16; q++) nxt[q] = src[128 * q];
+        for (int q = 0; q < 16; q++) nxt[q] = ld.template fetch<N>(f, t + 128 * q);
     };
     if (f0 < f1) fetch(f0);
     for (int f = f0; f < f1; f++) {
         v2f x[16];
         static_for<0, 16>([&](auto Q) {
             constexpr int q = Q.value;
-            const v2f s_ = nxt[q];
+            const v2f s_ = ld.decode(nxt[q]);
             if (s_.x > refc::FFT_OVER_LIMIT_F) over = 1;                        // OVER_LIMIT, fft.cpp:30,275
             x[bitrev<16>(q)] = v2f{wn[q] * s_.y, wn[q] * s_.x};    // I/Q swapped, fft.cpp:280-281
         });
@@ -483,6 +543,7 @@ __device__ __forceinline__ v2f pair_swap(v2f v)           // the value of lane t
     return v2f{__int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v.x), 0xB1, 0xf, 0xf, false)),
                __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v.y), 0xB1, 0xf, 0xf, false))};
 }
+template <class Ld = RowLoad>
 __global__ __launch_bounds__(512)
 void spectrum32_kernel(SpectrumArgs a)
 {
@@ -506,7 +567,7 @@ void spectrum32_kernel(SpectrumArgs a)
         else if (o == 2) wH = v2f{-v.y, v.x};
         else wH = v2f{-r * (v.x + v.y), r * (v.x - v.y)};
     }
-    const v2f *in = reinterpret_cast<const v2f *>(a.in) + (long)ch * a.in_stride;
+    const Ld ld(a, ch);
     float *sum = a.sum + (long)ch * N, *pwr = a.pwr + (long)ch * N, *ave = a.ave + (long)ch * N;
     int ave_count = a.counters[2 * ch], total = a.counters[2 * ch + 1];
     total += f0;                                              // counters at this group's first frame
@@ -521,18 +582,17 @@ void spectrum32_kernel(SpectrumArgs a)
         sm[r] = a.nparts == 1 ? sum[((kbin + 512 * r) + N / 2) & (N - 1)] : 0.f;   // display order, fft.cpp:564-589
         wn[r] = a.win[512 * r + t];
     });
-    v2f nxt[16];
+    typename Ld::Raw nxt[16];
     auto fetch = [&](int f) {
-        const v2f *src = in + (long)f * N + t;
 #pragma unroll
-        for (int q = 0; q < 16; q++) nxt[q] = src[512 * q];
+        for (int q = 0; q < 16; q++) nxt[q] = ld.template fetch<N>(f, t + 512 * q);
     };
     if (f0 < f1) fetch(f0);
     for (int f = f0; f < f1; f++) {
         v2f x[16];
         static_for<0, 16>([&](auto Q) {
             constexpr int q = Q.value;
-            const v2f s_ = nxt[q];
+            const v2f s_ = ld.decode(nxt[q]);
             if (s_.x > refc::FFT_OVER_LIMIT_F) over = 1;                        // OVER_LIMIT, fft.cpp:30,275
             x[bitrev<16>(q)] = v2f{wn[q] * s_.y, wn[q] * s_.x};    // I/Q swapped, fft.cpp:280-281
         });
@@ -694,22 +754,30 @@ __global__ void spectrum_combine_kernel(SpectrumArgs a, int n)
     a.sum[(long)ch * n + j] = sm; a.pwr[(long)ch * n + j] = m;
     a.ave[(long)ch * n + j] = (float)((double)log10f(m + a.kc) + a.kb);
 }
-template <int LOG2N>
+template <int LOG2N, class Ld = RowLoad>
 static hipError_t spec_launch_one(const SpectrumArgs &a, hipStream_t s)
 {
     using Cfg = SpecCfg<LOG2N>;
-    hipError_t e = CSDR_MAX_LDS_ONCE((&spectrum_kernel<LOG2N>), Cfg::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    static const bool wide = !(getenv("CSDR_SPEC16") && atoi(getenv("CSDR_SPEC16")) == 0);
-    if (LOG2N == 12 && wide)
-        hipLaunchKernelGGL(spectrum16_kernel, dim3(a.channels * a.nparts), dim3(256), SPEC16_LDS, s, a);
-    else if (LOG2N == 11 && wide)
-        hipLaunchKernelGGL(spectrum8_kernel, dim3(a.channels * a.nparts), dim3(128), SPEC8_LDS, s, a);
-    else if (LOG2N == 13 && wide) {
-        e = CSDR_MAX_LDS_ONCE((&spectrum32_kernel), SPEC32_LDS);
+    // The display stream's loaders (Ld != RowLoad) run in the wide kernels only, 2048 ... 8192 points: at 16384 points
+    // (spectrum_kernel<14>, 512 threads, at most 256 registers) the datagram loaders spilled 164 / 236 bytes and the
+    // DC row loader 12 bytes of scratch per lane -- that size gathers its frames instead (capi_fft.hip).
+    constexpr bool plain = std::is_same<Ld, RowLoad>::value;
+    static_assert(plain || LOG2N < 14, "the stream loaders have no 16384-point form");
+    hipError_t e = hipSuccess;
+    if constexpr (plain) {
+        e = CSDR_MAX_LDS_ONCE((&spectrum_kernel<LOG2N>), Cfg::LDS_BYTES);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(spectrum32_kernel, dim3(a.channels * a.nparts), dim3(512), SPEC32_LDS, s, a);
-    } else
+    }
+    static const bool wide = !plain || !(getenv("CSDR_SPEC16") && atoi(getenv("CSDR_SPEC16")) == 0);
+    if (LOG2N == 12 && wide)
+        hipLaunchKernelGGL(spectrum16_kernel<Ld>, dim3(a.channels * a.nparts), dim3(256), SPEC16_LDS, s, a);
+    else if (LOG2N == 11 && wide)
+        hipLaunchKernelGGL(spectrum8_kernel<Ld>, dim3(a.channels * a.nparts), dim3(128), SPEC8_LDS, s, a);
+    else if (LOG2N == 13 && wide) {
+        e = CSDR_MAX_LDS_ONCE((&spectrum32_kernel<Ld>), SPEC32_LDS);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(spectrum32_kernel<Ld>, dim3(a.channels * a.nparts), dim3(512), SPEC32_LDS, s, a);
+    } else if constexpr (plain)
         hipLaunchKernelGGL(spectrum_kernel<LOG2N>, dim3(a.channels * a.nparts), dim3(Cfg::T), Cfg::LDS_BYTES, s, a);
     if (a.nparts > 1) {
         hipLaunchKernelGGL(spectrum_alpha_kernel, dim3(a.channels), dim3(64), 0, s, a);
@@ -737,6 +805,23 @@ hipError_t spectrum_launch(int log2n, const SpectrumArgs &a, hipStream_t stream)
     case 14: return spec_launch_one<14>(a, stream);
     default: return hipErrorInvalidValue;
     }
+}
+template <class Ld>
+static hipError_t spectrum_stream_one(int log2n, const SpectrumArgs &a, hipStream_t stream)
+{
+    switch (log2n) {
+    case 11: return spec_launch_one<11, Ld>(a, stream);
+    case 12: return spec_launch_one<12, Ld>(a, stream);
+    case 13: return spec_launch_one<13, Ld>(a, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+hipError_t spectrum_stream_launch(int log2n, const SpectrumArgs &a, int pkt_len, hipStream_t stream)
+{
+    if (!a.pk) return spectrum_stream_one<RowDcLoad>(log2n, a, stream);
+    if (pkt_len == 1444) return spectrum_stream_one<WireLoad<1444>>(log2n, a, stream);
+    if (pkt_len == 1028) return spectrum_stream_one<WireLoad<1028>>(log2n, a, stream);
+    return hipErrorInvalidValue;
 }
 hipError_t fft_plain_launch(int log2n, int sign, const float *in, float *out, const float *tw1,
                             const float *tw2, hipStream_t stream)

@@ -343,6 +343,30 @@ def unpack_packets_batch(raw, pkt_len, dc=None, device=0):
     return do.download(np.complex64, ch * npk * per).reshape(ch, npk * per)
 
 
+def _dc_buffer(dc, channels, device):
+    if dc is None:
+        return None
+    d = DeviceBuffer(channels * 16, device)
+    d.upload(np.ascontiguousarray(dc, dtype=np.float64).reshape(channels, 2))
+    return d
+
+
+def spurcal_packets_batch(raw, pkt_len, dc, device=0):
+    """NcoSpurCalibrate over datagrams raw uint8 [channels, npackets, pkt_len], decoded on the device; dc [channels, 2]
+    -> the new [channels, 2] running means (csdr_ingest_spurcal_packets)"""
+    raw = np.ascontiguousarray(raw, dtype=np.uint8)
+    ch, npk = raw.shape[0], raw.shape[1]
+    dp = DeviceBuffer(max(raw.nbytes, 4), device)
+    dp.upload(raw)
+    ddc = _dc_buffer(dc, ch, device)
+    check(lib().csdr_ingest_spurcal_packets(device, C.c_void_p(dp.ptr), ch, npk, pkt_len, C.c_void_p(ddc.ptr), C.c_void_p(0)),
+          "csdr_ingest_spurcal_packets")
+    sync(device)
+    out = ddc.download(np.float64, 2 * ch).reshape(ch, 2)
+    dp.free(); ddc.free()
+    return out
+
+
 def spurcal(dc, x, device=0):
     """NcoSpurCalibrate running I/Q means (interface/sdrinterface.cpp:829-848); returns the new [I, Q]"""
     a = _c128(x); d = np.ascontiguousarray(dc, dtype=np.float64).copy()
@@ -958,6 +982,56 @@ class FftBatch(_Obj):
 
     def total_count(self, channel):
         return check(lib().csdr_fft_batch_get_total_count(self.h, channel))
+
+    # ---- the display stream: ProcessIQData's frame carry, skip counter and screen gate (sdrinterface.cpp:886-907)
+    def set_display_rate(self, sample_rate, max_display_rate, gated=False):
+        """SetMaxDisplayRate: skip value (int)(sample_rate / (size * max_display_rate)); gated: ScreenUpdateDone handshake"""
+        check(lib().csdr_fft_batch_set_display_rate(self.h, float(sample_rate), int(max_display_rate), int(bool(gated))),
+              "csdr_fft_batch_set_display_rate")
+
+    def screen_update_done(self):
+        check(lib().csdr_fft_batch_screen_update_done(self.h), "csdr_fft_batch_screen_update_done")
+
+    def stream_reset(self):
+        check(lib().csdr_fft_batch_stream_reset(self.h), "csdr_fft_batch_stream_reset")
+
+    def put_display_stream_ptr(self, d_in, in_stride, n, d_dc=None, stream=None):
+        """n samples of every row appended to the display stream; returns the frames that entered the average"""
+        return check(lib().csdr_fft_batch_put_display_stream(self.h, C.c_void_p(d_in), in_stride, n, C.c_void_p(d_dc or 0),
+                                                             C.c_void_p(stream) if stream else None),
+                     "csdr_fft_batch_put_display_stream")
+
+    def put_display_stream(self, x, dc=None):
+        """x complex [channels, n] (host); dc: optional [channels, 2] offsets -> frames used"""
+        x = np.ascontiguousarray(x, dtype=np.complex64)
+        din = DeviceBuffer(max(x.nbytes, 8), self.device)
+        din.upload(x)
+        ddc = _dc_buffer(dc, self.channels, self.device)
+        k = self.put_display_stream_ptr(din.ptr, x.shape[1], x.shape[1], ddc.ptr if ddc else None)
+        sync(self.device)
+        din.free()
+        if ddc:
+            ddc.free()
+        return k
+
+    def put_display_packets_ptr(self, d_packets, npackets, pkt_len, d_dc=None, stream=None):
+        """the datagrams [channels][npackets][pkt_len] appended to the display stream; returns the frames used"""
+        return check(lib().csdr_fft_batch_put_display_packets(self.h, C.c_void_p(d_packets), npackets, pkt_len,
+                                                              C.c_void_p(d_dc or 0), C.c_void_p(stream) if stream else None),
+                     "csdr_fft_batch_put_display_packets")
+
+    def put_display_packets(self, raw, pkt_len, dc=None):
+        """raw uint8 [channels, npackets, pkt_len] (host); dc: optional [channels, 2] offsets -> frames used"""
+        raw = np.ascontiguousarray(raw, dtype=np.uint8)
+        dp = DeviceBuffer(max(raw.nbytes, 4), self.device)
+        dp.upload(raw)
+        ddc = _dc_buffer(dc, self.channels, self.device)
+        k = self.put_display_packets_ptr(dp.ptr, raw.shape[1], pkt_len, ddc.ptr if ddc else None)
+        sync(self.device)
+        dp.free()
+        if ddc:
+            ddc.free()
+        return k
 
 
 class CFractResampler(_Obj):

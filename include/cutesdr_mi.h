@@ -458,6 +458,39 @@ int csdr_fft_batch_get_waterfall_all(csdr_fft_batch *f, int max_w, double max_db
                                      int stop_hz, unsigned int *d_rgb, long long out_stride, int *d_overload,
                                      void *stream);
 
+/* The display path of CSdrInterface::ProcessIQData (interface/sdrinterface.cpp:878-907) on the device: each call
+ * appends n samples of every row to the display stream.  Each sample has the channel's DC offset subtracted
+ * (:889-894) and goes into the frame being filled (m_DataBuf, kept per channel on the device across calls).  When a
+ * frame of `size` samples completes, the skip counter (:898-900) and, if enabled, the screen gate (:901-906) decide
+ * whether it reaches PutInDisplayFFT.  The frame position, skip value, skip counter and gate are ONE set per object:
+ * every row gets the same sample count per call.  Used frames go through exactly the averaging, log and overload code
+ * of csdr_fft_batch_put_display, so get_ave / get_total_count / get_screen_all / get_waterfall_all work unchanged.
+ * Out of scope: a blanked display (run csdr_noiseproc_batch_process into fp32 rows, then put_display_stream); the
+ * SPUR_CAL_MAXSAMPLES bookkeeping of NcoSpurCalibrate (the host keeps m_NcoSpurCalCount); shard forms. */
+/* SetMaxDisplayRate (sdrinterface.h:112-114): skip value = (int)(sample_rate / (size * max_display_rate)), counter 0.
+ * gated != 0 turns on the m_ScreenUpateFinished handshake: after a used frame, none is used until
+ * csdr_fft_batch_screen_update_done.  Until this is called the skip value is 0 (every frame) and the gate is off.
+ * csdr_fft_batch_set_params sets the frame position to 0 and, once a display rate is set, re-derives the skip value
+ * from its own size and fs with the last max_display_rate, as SetFftSize does (:709-718). */
+int csdr_fft_batch_set_display_rate(csdr_fft_batch *f, double sample_rate, int max_display_rate, int gated);
+/* ScreenUpdateDone() (sdrinterface.h:67) */
+int csdr_fft_batch_screen_update_done(csdr_fft_batch *f);
+/* StartSdr (:512, :591): frame position 0, gate open */
+int csdr_fft_batch_stream_reset(csdr_fft_batch *f);
+/* n samples of every row of d_in ([channels][in_stride] complex fp32, 8-byte aligned) appended to the display stream;
+ * returns the number of frames that entered the average in this call (each one an emit NewFftData()), >= 0, or CSDR_E*.
+ * d_dc: optional [channels][2] doubles (I, Q), subtracted as csdr_ingest_unpack does, (float)((double)v - dc); read on
+ * `stream`, so a csdr_ingest_spurcal* issued before it on the same stream is seen (:886 runs before :889).  A call that
+ * uses no frame launches no spectrum work and leaves average, counters and overload flags as they were; it still
+ * updates the partial frame.  Asynchronous on `stream`. */
+int csdr_fft_batch_put_display_stream(csdr_fft_batch *f, const float *d_in, long long in_stride, int n,
+                                      const double *d_dc, void *stream);
+/* the same on datagrams: d_packets [channels][npackets][pkt_len] bytes on the device, decoded in the spectrum kernels'
+ * frame load (2048 ... 8192 points; a frame that begins in the carry, and the other sizes, through a gather) --
+ * the rules of csdr_demod_batch_process_packets (pkt_len 1028 or 1444, 4-byte aligned, below 2 GiB per channel) */
+int csdr_fft_batch_put_display_packets(csdr_fft_batch *f, const void *d_packets, int npackets, int pkt_len,
+                                       const double *d_dc, void *stream);
+
 /* ----------------------------------------------------------------------------------------
  * CFractResampler (dsp/fractresampler.h:17-33)
  * -------------------------------------------------------------------------------------- */
@@ -584,6 +617,10 @@ int csdr_ingest_unpack_host(int device, const void *packets, int npackets, int p
 int csdr_ingest_spurcal(int device, const float *d_iq, long long in_stride, int channels, int n, double *d_dc,
                         void *stream);
 int csdr_ingest_spurcal_host(int device, int n, const double *in_iq, double *dc_iq);
+/* the same over datagrams ([channels][npackets][pkt_len] bytes on the device, the rules of csdr_ingest_unpack), decoded
+ * in the kernel's loads: d_dc equals, bit for bit, csdr_ingest_unpack (no DC) followed by csdr_ingest_spurcal */
+int csdr_ingest_spurcal_packets(int device, const void *d_packets, int channels, int npackets, int pkt_len, double *d_dc,
+                                void *stream);
 
 #ifdef __cplusplus
 }
