@@ -389,12 +389,14 @@ int apply_set_demod(ChainCore &k, int r, ChanCfg &c, double in_rate, int mode, c
     c.info = info;
     int rc;
     if (c.mode != mode) {
+        // pull() first: it waits for the device, so that the down-converter's history reset below (on the null stream)
+        // and the queued patches it flushes land behind every call still in flight (a pipelined batch's), not inside it
+        if ((rc = k.pc.pull(r))) return rc;
         c.mode = mode;
         if (mode == PC_MODE_LSB || mode == PC_MODE_CWL) c.want_bw = -info.LowCutmin;
         else c.want_bw = info.HiCutmax;
         c.out_rate = csdr_downconvert_batch_set_data_rate(k.dc, r, in_rate, c.want_bw);
         if (c.out_rate < 0) return CSDR_EHIP;
-        if ((rc = k.pc.pull(r))) return rc;
         PcChannel &h = k.pc.h[r];
         h.mode = mode;
         c.demod_rate = c.out_rate;
@@ -490,7 +492,7 @@ struct csdr_demod_batch {
     bool chained = false;                             // ... its chained form (ChainCore::step_split): the cores stay plain
     std::vector<hipStream_t> post_streams;            // chained pipeline: core -> its post-chain's stream
     bool have_last_dc = false;                        // chained pipeline: dc_done[order.back()] holds the previous call's record
-    int taps = 0;                                     // csdr_demod_batch_set_taps (new groups inherit it)
+    int taps = 0;                                     // csdr_demod_batch_set_taps (new groups inherit it: batch_move_row)
     bool rate_change_failed = false;                  // csdr_demod_batch_set_input_rate stopped half way: no processing until one succeeds
     std::vector<int> prev_post;                       // pipelined: per core, the post-chain event of the previous call
     std::vector<char> prev_join;                      // pipelined: per core, joins[] of the previous call not yet waited for
@@ -635,7 +637,10 @@ static int batch_move_row(csdr_demod_batch *b, int channel, int new_stages, Appl
     if (kb < 0) {
         S = new ChainCore();
         rc = S->init(b->device, 1, b->fft_n);
-        if (rc == CSDR_OK && b->pipelined) rc = S->pipelined_init();
+        S->taps = b->taps; S->tap1_n = 0;              // the batch's stage taps hold for its new groups too
+        // the chained form's cores stay plain (its post-chain streams grow in demod_batch_run); only the three-stage form
+        // gives a new group its own filter and post-chain streams
+        if (rc == CSDR_OK && b->pipelined && !b->chained) rc = S->pipelined_init();
         if (rc == CSDR_OK) rc = S->ensure((long)A.pending + 1);
         if (rc == CSDR_OK) { hip(hipMalloc((void **)&dr, sizeof(int))) && hip(hipMalloc((void **)&dor, sizeof(int))); }
         if (rc == CSDR_OK) rc = batch_plumbing_reserve(b, b->cores.size() + 1);
@@ -1166,6 +1171,7 @@ int csdr_demod_batch_set_pipelined(csdr_demod_batch *b, int on)
 {
     if (!b) return fail(CSDR_EINVAL, "bad handle");
     if (b->cores.empty()) return fail(CSDR_ESTATE, "commit first");
+    if (on && b->taps) return fail(CSDR_ESTATE, "stage taps need the strict mode (csdr_demod_batch_set_taps(b, 0) first)");
     if (!device_ok(b->device)) return CSDR_EHIP;
     CSDR_HIP(hipDeviceSynchronize());
     if (on) {                                          // a single plan group normally runs on the caller's stream
@@ -1544,6 +1550,15 @@ extern "C" int csdr__demod_batch_probe(csdr_demod_batch *b, double *us_out, doub
     }
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     return n;
+}
+/* internal (tests): the batch's pipelined form -- bit 0 pipelined, bit 1 the chained form, bit 2 some plan group has the
+ * three-stage form's own filter and post-chain streams (then every call runs the three-stage schedule) */
+extern "C" int csdr__demod_batch_form(csdr_demod_batch *b)
+{
+    if (!b) return fail(CSDR_EINVAL, "bad handle");
+    bool three = false;
+    for (auto *k : b->cores) three = three || k->s_post;
+    return (b->pipelined ? 1 : 0) | (b->chained ? 2 : 0) | (three ? 4 : 0);
 }
 /* stage taps of a batch's receivers: see include/cutesdr_mi.h */
 int csdr_demod_batch_set_taps(csdr_demod_batch *b, int mask)

@@ -102,14 +102,17 @@ struct PcUnit {
     int pull(int c)      // device -> host mirror (state advances on the device); rows that MOVE and new demodulator objects only
     {
         CSDR_HIP(hipSetDevice(device));
-        { const int rcp = patches.flush(nullptr); if (rcp) return rcp; }     // nothing queued may be lost to the copy below
+        // the wait comes FIRST: the library's streams do not block on the null stream, so a queue flushed there before it
+        // could land inside a walk still in flight (a pipelined batch's call k) -- words that belong to call k+1
         CSDR_HIP(hipDeviceSynchronize());
+        { const int rcp = patches.flush(nullptr); if (rcp) return rcp; }     // nothing queued may be lost to the copy below
         CSDR_HIP(hipMemcpy(&h[c], d_chan + c, sizeof(PcChannel), hipMemcpyDeviceToHost));
         return CSDR_OK;
     }
     int push(int c)
     {
         CSDR_HIP(hipSetDevice(device));
+        CSDR_HIP(hipDeviceSynchronize());                                      // (as in pull: behind every walk in flight)
         { const int rcp = patches.flush(nullptr); if (rcp) return rcp; }     // older queued words must not land on top of these
         CSDR_HIP(hipMemcpy(d_chan + c, &h[c], sizeof(PcChannel), hipMemcpyHostToDevice));
         return CSDR_OK;
@@ -129,6 +132,9 @@ struct PcUnit {
         if (rc) return rc;
         h[c] = src.h[sc]; hagc[c] = src.hagc[sc];
         fir_am[c] = src.fir_am[sc]; fir_sam[c] = src.fir_sam[sc]; fir_fm[c] = src.fir_fm[sc];
+        // this unit's queue may hold ring fills of row c (an AGC rate change of the receiver that left it): they go out
+        // BEFORE the imported rings, not on top of them (the device is idle: src.pull waited)
+        { const int rcp = patches.flush(nullptr); if (rcp) return rcp; }
         CSDR_HIP(hipMemcpy(d_dly + (size_t)c * 2 * PC_AGC_RING, src.d_dly + (size_t)sc * 2 * PC_AGC_RING,
                            sizeof(float) * 2 * PC_AGC_RING, hipMemcpyDeviceToDevice));
         CSDR_HIP(hipMemcpy(d_mag + (size_t)c * PC_AGC_RING, src.d_mag + (size_t)sc * PC_AGC_RING,

@@ -319,7 +319,9 @@ int csdr_demod_batch_process(csdr_demod_batch *b, const float *d_in, long long i
  * CSDR_PIPE_KIND=3 in the environment): the three-stage form of rounds 3-5 -- every group's down-converter at once,
  * filter and post-chain on two more streams per group over double buffers; it wants more than HIP's default four
  * hardware queues (GPU_MAX_HW_QUEUES=8 or more) and is the slower one (1.75-1.80 against 1.65-1.68 ms per call on 256
- * mixed receivers; the strict mode: 1.60-1.65). */
+ * mixed receivers; the strict mode: 1.60-1.65).  The form holds for the object's life: plan groups that a later SetDemod
+ * or csdr_demod_batch_set_input_rate opens take the batch's form.  CSDR_ESTATE while stage taps are on
+ * (csdr_demod_batch_set_taps(b, 0) first). */
 int csdr_demod_batch_set_pipelined(csdr_demod_batch *b, int on);
 int csdr_demod_batch_flush(csdr_demod_batch *b, void *stream);
 /* the stereo overload (dsp/demodulator.cpp:221-273: AM/FM duplicate the audio into both halves, SAM splits the
@@ -332,7 +334,9 @@ int csdr_demod_batch_out_count(csdr_demod_batch *b, int channel);
  * LAST call's down-converter output, filter output and AGC output in device memory (the AGC's through a split launch,
  * as above); csdr_demod_batch_get_tap copies receiver `channel`'s samples of that call to host memory -- PROFILE_1 ..
  * 3: interleaved fp32 I/Q, PROFILE_1 counts the samples the down-converter appended in that call, 2 and 3 the samples
- * the filter released -- and returns the number of floats (synchronous; PROFILE_4 is the caller's own output row). */
+ * the filter released -- and returns the number of floats (synchronous; PROFILE_4 is the caller's own output row).
+ * The mask holds for every receiver, also for one that a mode or input-rate change moves into a new plan group.  Both
+ * orders are refused with CSDR_ESTATE: set_taps on a pipelined batch, set_pipelined on a batch with taps on. */
 int csdr_demod_batch_set_taps(csdr_demod_batch *b, int mask);
 int csdr_demod_batch_get_tap(csdr_demod_batch *b, int channel, int profile, float *out, int cap);
 /* Diagnostics: the number of plan groups the batch runs per call (rows that share one decimation; every group is one
