@@ -50,6 +50,16 @@ inline bool device_ok(int device)
     return hipSetDevice(device) == hipSuccess;
 }
 
+// true when any GPU is present (entry points that must answer CSDR_EHIP before they look at a handle)
+inline bool have_device()
+{
+    int n = 0;
+    const hipError_t e = hipGetDeviceCount(&n);
+    if (e == hipSuccess && n > 0) return true;
+    fail(CSDR_EHIP, "no HIP device available (%s); libcutesdr_mi has no CPU fallback", e == hipSuccess ? "count 0" : hipGetErrorString(e));
+    return false;
+}
+
 // Host staging of the drop-in classes' double* buffers ("host double* -> pinned staging -> HBM fp32"): a
 // page-locked fp32 buffer the DMA engines read and write directly (a pageable source goes through the runtime's own
 // bounce buffer first), grown on demand with its contents kept, and the two conversions at the boundary as plain

@@ -383,8 +383,35 @@ struct ChanCfg {
                                         // set (amdemod.cpp:50, fmdemod.cpp:62); an input-rate change does not touch it
 };
 
-// CDemodulator::SetDemod (dsp/demodulator.cpp:107-157) for row r of core k
-int apply_set_demod(ChainCore &k, int r, ChanCfg &c, double in_rate, int mode, const DemodInfo &info)
+// The filter set-ups of one csdr_demod_batch_set_demod_many call, gathered per filter object (= plan group) so that each
+// object gets ONE csdr_fastfir_batch_setup_many -- its filters are then designed on the device, not on the caller's thread.
+struct FilterDefer {
+    struct Group { csdr_fastfir_batch *ff; std::vector<int> ch; std::vector<double> flo, fhi, off, fs; };
+    std::vector<Group> groups;
+    std::vector<int> status;
+    void add(csdr_fastfir_batch *ff, int channel, double flo, double fhi, double off, double fs)
+    {
+        Group *g = nullptr;
+        for (Group &q : groups) if (q.ff == ff) g = &q;
+        if (!g) { groups.push_back(Group{ff, {}, {}, {}, {}, {}}); g = &groups.back(); }
+        g->ch.push_back(channel); g->flo.push_back(flo); g->fhi.push_back(fhi); g->off.push_back(off); g->fs.push_back(fs);
+    }
+    int flush()          // (a rejected entry keeps its old taps, like the reference's "parameter error")
+    {
+        int err = CSDR_OK;
+        for (Group &g : groups) {
+            status.resize(g.ch.size());
+            const int rc = csdr_fastfir_batch_setup_many(g.ff, (int)g.ch.size(), g.ch.data(), g.flo.data(), g.fhi.data(),
+                                                         g.off.data(), g.fs.data(), status.data());
+            if (rc < 0 && !err) err = rc;
+        }
+        groups.clear();
+        return err;
+    }
+};
+
+// CDemodulator::SetDemod (dsp/demodulator.cpp:107-157) for row r of core k; defer: the filter goes to the gather above
+int apply_set_demod(ChainCore &k, int r, ChanCfg &c, double in_rate, int mode, const DemodInfo &info, FilterDefer *defer = nullptr)
 {
     c.info = info;
     int rc;
@@ -410,8 +437,11 @@ int apply_set_demod(ChainCore &k, int r, ChanCfg &c, double in_rate, int mode, c
     }
     c.cw_off = info.Offset;
     csdr_downconvert_batch_set_cw_offset(k.dc, r, c.cw_off);
-    rc = csdr_fastfir_batch_setup(k.ff, k.rows == 1 ? -1 : r, info.LowCut, info.HiCut, c.cw_off, c.out_rate);
-    if (rc < 0 && rc != CSDR_EINVAL) return rc;      // EINVAL = reference's "parameter error": keep old taps
+    if (defer) defer->add(k.ff, k.rows == 1 ? -1 : r, info.LowCut, info.HiCut, c.cw_off, c.out_rate);
+    else {
+        rc = csdr_fastfir_batch_setup(k.ff, k.rows == 1 ? -1 : r, info.LowCut, info.HiCut, c.cw_off, c.out_rate);
+        if (rc < 0 && rc != CSDR_EINVAL) return rc;      // EINVAL = reference's "parameter error": keep old taps
+    }
     rc = k.pc.agc_set(r, info.AgcOn, info.AgcHangOn, info.AgcThresh, info.AgcManualGain, info.AgcSlope,
                       info.AgcDecay, c.out_rate);
     if (rc) return rc;
@@ -1090,6 +1120,39 @@ int csdr_demod_batch_set_demod(csdr_demod_batch *b, int channel, int mode, const
     c.pending = mode;                    // applied at commit
     c.want_bw = (mode == PC_MODE_LSB || mode == PC_MODE_CWL) ? -c.info.LowCutmin : c.info.HiCutmax;
     return CSDR_OK;
+}
+/* csdr_demod_batch_set_demod for each entry, in array order (include/cutesdr_mi.h).  Same-mode entries on a committed
+ * batch gather their filters per plan group; an entry that takes the one-receiver path (a new mode, or any entry before
+ * the commit) first sends the gather out, so that the filter objects see the calls in array order as well -- a mover's
+ * copy_row and a later host design of a slot both find the earlier entries' jobs queued. */
+int csdr_demod_batch_set_demod_many(csdr_demod_batch *b, int n, const int *channel, const int *mode,
+                                    const csdr_demod_info *info, int *status)
+{
+    if (!have_device()) return CSDR_EHIP;
+    if (!b || n < 0 || (n > 0 && (!channel || !mode || !info))) return fail(CSDR_EINVAL, "bad handle, negative count or null array");
+    for (int i = 0; i < n; i++)
+        if (channel[i] < 0 || channel[i] >= b->channels || mode[i] < 0 || mode[i] > 6)
+            return fail(CSDR_EINVAL, "entry %d: channel %d, mode %d", i, channel[i], mode[i]);
+    if (n == 0) return CSDR_OK;
+    if (!device_ok(b->device)) return CSDR_EHIP;
+    FilterDefer defer;
+    int err = CSDR_OK;
+    for (int i = 0; i < n; i++) {
+        const int c = channel[i];
+        ChanCfg &cfg = b->cfg[c];
+        int rc;
+        if (b->core_of[c] >= 0 && cfg.mode == mode[i]) {
+            DemodInfo di; memcpy(&di, &info[i], sizeof(di));
+            rc = apply_set_demod(*b->cores[b->core_of[c]], b->row_of[c], cfg, b->in_rate, mode[i], di, &defer);
+        } else {
+            rc = defer.flush();
+            if (rc == CSDR_OK) rc = csdr_demod_batch_set_demod(b, c, mode[i], &info[i]);
+        }
+        if (status) status[i] = rc;
+        if (rc < 0 && !err) err = rc;
+    }
+    const int rc = defer.flush();
+    return err ? err : rc;
 }
 // device copies of every group's input-row list, from members[] and in_row[]
 static int batch_upload_input_rows(csdr_demod_batch *b)

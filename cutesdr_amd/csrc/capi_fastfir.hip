@@ -2,6 +2,7 @@
 #include "capi_common.hpp"
 #include <algorithm>
 #include "fastfir_kernels.h"
+#include "fastfir_design_kernels.h"
 #include "host_math.hpp"
 #include "patch_queue.hpp"
 #include <cmath>
@@ -38,7 +39,101 @@ struct csdr_fastfir_batch {
     // of both kernel orders as patches; the NEXT process call applies them on its own stream in front of its launch
     // (patch_queue.hpp) -- in stream order behind every earlier call's reads of H, so one buffer per filter suffices.
     PatchQueue patches;
+    // csdr_fastfir_batch_setup_many designs on the DEVICE instead (fastfir_design_kernels.hip): a job per slot -- two
+    // doubles -- queued beside the patches and launched right behind the patch kernel of the same flush, on the same
+    // stream.  At most one job per slot: a later job replaces it, a later host design (a patch of the slot's rows) cancels
+    // it; a job queued behind a patch of its slot wins, because its launch follows the patch kernel.  resp[slot] is then
+    // older than the device's fp64 row (stale[slot]) until a reader asks for it (fetch_mirror).
+    std::vector<DesignJob> jobs;
+    std::vector<int> job_of;          // slot -> index into jobs, or -1
+    std::vector<char> stale;          // slot -> resp[slot] has to be fetched from d_resp
+    double *d_win = nullptr, *d_tw = nullptr;     // the host's window and twiddle tables (host_math.hpp), fp64
+    int *d_perm = nullptr, *d_perm2 = nullptr;    // perm / perm2
+    double *d_resp = nullptr;         // [channels][n] complex fp64, natural order; all five allocated by the first setup_many
+    hipEvent_t ev_design = nullptr;   // behind the last design launch
 };
+
+static void cancel_job(csdr_fastfir_batch *b, int slot)
+{
+    const int i = b->job_of[slot];
+    if (i < 0) return;
+    b->job_of[slot] = -1;
+    if ((size_t)i + 1 != b->jobs.size()) { b->jobs[i] = b->jobs.back(); b->job_of[b->jobs[i].slot] = i; }
+    b->jobs.pop_back();
+}
+
+static void queue_job(csdr_fastfir_batch *b, int slot, double nfc, double nfs)
+{
+    const DesignJob j{slot, 0, nfc, nfs};
+    if (b->job_of[slot] >= 0) b->jobs[b->job_of[slot]] = j;
+    else { b->job_of[slot] = (int)b->jobs.size(); b->jobs.push_back(j); }
+    b->stale[slot] = 1;
+}
+
+// the queued patches, then the queued design jobs, in `s`'s order (both queues are empty afterwards)
+static int flush_control(csdr_fastfir_batch *b, hipStream_t s)
+{
+    if (b->jobs.empty()) return b->patches.flush(s);
+    unsigned char *h = nullptr, *d = nullptr;
+    int rc = b->patches.take(b->jobs.size() * sizeof(DesignJob), &h, &d);
+    if (rc) return rc;
+    memcpy(h, b->jobs.data(), b->jobs.size() * sizeof(DesignJob));
+    // (launch() takes its own descriptor block from the same arena; take() adds a chunk when one is full)
+    rc = b->patches.launch(s);
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        DesignArgs a;
+        a.jobs = (const DesignJob *)d; a.win = b->d_win; a.tw = b->d_tw; a.perm = b->d_perm; a.perm2 = b->d_perm2;
+        a.h = b->d_h; a.h2 = b->d_h2; a.resp = b->d_resp;
+        e = fastfir_design_launch(b->log2n, a, (int)b->jobs.size(), s);
+        if (e == hipSuccess) {
+            for (const DesignJob &j : b->jobs) b->job_of[j.slot] = -1;
+            b->jobs.clear();
+            if (!b->ev_design) e = hipEventCreateWithFlags(&b->ev_design, hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventRecord(b->ev_design, s);
+        }
+    }
+    // on every path: the arena closes behind whatever of this flush did get launched
+    const int rr = b->patches.retire(s);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(CSDR_EHIP, "filter design launch: %s", hipGetErrorString(e));
+    return rr;
+}
+
+// resp[slot] as the device has it: a slot designed on the device is fetched when somebody reads it (get_response, a
+// receiver that takes its response to another plan group) -- the queue goes out on the object's last stream, in its order.
+// The wait on ev_design comes before the copy on every path: at N = 16384 the kernel transforms inside the d_resp row.
+static int fetch_mirror(csdr_fastfir_batch *b, int slot)
+{
+    if (!b->stale[slot]) return CSDR_OK;
+    const int rc = flush_control(b, b->last_stream);
+    if (rc) return rc;
+    if (b->ev_design) CSDR_HIP(hipEventSynchronize(b->ev_design));
+    CSDR_HIP(hipMemcpy(b->resp[slot].data(), b->d_resp + (size_t)slot * 2 * b->n, sizeof(cd) * (size_t)b->n, hipMemcpyDeviceToHost));
+    b->stale[slot] = 0;
+    return CSDR_OK;
+}
+
+// tables and rows of the device-side design, once in an object's life (the first setup_many: blocking allocations and
+// copies, the only part of that call that waits).  d_resp has a row per CHANNEL from the start, so the later switch from
+// a shared filter to per-channel filters has nothing to reallocate here.
+static int design_state(csdr_fastfir_batch *b)
+{
+    if (b->d_resp) return CSDR_OK;
+    const size_t n = (size_t)b->n, p = n / 2 + 1;
+    const auto win = fastfir_window((int)p);
+    const auto tw = host_twiddles(n);
+    if (!b->d_win) CSDR_HIP(hipMalloc((void **)&b->d_win, p * sizeof(double)));
+    if (!b->d_tw) CSDR_HIP(hipMalloc((void **)&b->d_tw, n * sizeof(double)));
+    if (!b->d_perm) CSDR_HIP(hipMalloc((void **)&b->d_perm, n * sizeof(int)));
+    if (!b->d_perm2) CSDR_HIP(hipMalloc((void **)&b->d_perm2, n * sizeof(int)));
+    CSDR_HIP(hipMemcpy(b->d_win, win->data(), p * sizeof(double), hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemcpy(b->d_tw, tw->data(), n * sizeof(double), hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemcpy(b->d_perm, b->perm.data(), n * sizeof(int), hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemcpy(b->d_perm2, b->perm2.data(), n * sizeof(int), hipMemcpyHostToDevice));
+    CSDR_HIP(hipMalloc((void **)&b->d_resp, (size_t)b->channels * n * sizeof(cd)));
+    return CSDR_OK;
+}
 
 static void build_perm(csdr_fastfir_batch *b)
 {
@@ -73,6 +168,18 @@ static int upload_response(csdr_fastfir_batch *b, int slot, const std::vector<cd
         const int rc = b->patches.add(dst + (size_t)slot * 2 * b->n, dev.data(), dev.size() * sizeof(float));
         if (rc) return rc;
     }
+    return CSDR_OK;
+}
+
+// a response designed on the HOST becomes slot `slot`'s: its words queued as patches, the mirror current, a design job
+// still queued for the slot cancelled (the later call wins)
+static int set_response(csdr_fastfir_batch *b, int slot, const std::vector<cd> &H)
+{
+    cancel_job(b, slot);
+    const int rc = upload_response(b, slot, H);
+    if (rc) return rc;
+    b->resp[slot] = H;
+    b->stale[slot] = 0;
     return CSDR_OK;
 }
 
@@ -130,6 +237,8 @@ csdr_fastfir_batch *csdr_fastfir_batch_create(int device, int channels, int fft_
         return nullptr;
     }
     b->resp.assign(1, std::vector<cd>(fft_size, cd(0, 0)));
+    b->job_of.assign(channels, -1);          // (slot 0 alone while the filter is shared)
+    b->stale.assign(channels, 0);
     return b;
 }
 
@@ -142,6 +251,12 @@ void csdr_fastfir_batch_destroy(csdr_fastfir_batch *b)
     if (b->d_hist) (void)hipFree(b->d_hist);
     if (b->d_tw1) (void)hipFree(b->d_tw1);
     if (b->d_tw2) (void)hipFree(b->d_tw2);
+    if (b->ev_design) { (void)hipEventSynchronize(b->ev_design); (void)hipEventDestroy(b->ev_design); }
+    if (b->d_win) (void)hipFree(b->d_win);
+    if (b->d_tw) (void)hipFree(b->d_tw);
+    if (b->d_perm) (void)hipFree(b->d_perm);
+    if (b->d_perm2) (void)hipFree(b->d_perm2);
+    if (b->d_resp) (void)hipFree(b->d_resp);
     delete b;
 }
 
@@ -160,8 +275,10 @@ int csdr_fastfir_batch_setup(csdr_fastfir_batch *b, int channel, double flo, dou
         return fail(CSDR_EINVAL, "filter parameter error (reference keeps the previous taps)");
     if (channel >= 0 && !b->per_channel) {
         // switch to one filter per channel, seeded with the shared one: a reallocation, once in an object's life -- the
-        // only part of a set-up that waits (for this handle's queued patches and whatever still reads the old buffer)
-        { const int rcp = b->patches.flush(b->last_stream); if (rcp) return rcp; }
+        // only part of a set-up that waits (for this handle's queued patches and design jobs and whatever still reads the
+        // old buffer; a shared response that was designed on the device is fetched first: it seeds every mirror row)
+        { const int rcm = fetch_mirror(b, 0); if (rcm) return rcm; }
+        { const int rcp = flush_control(b, b->last_stream); if (rcp) return rcp; }
         CSDR_HIP(hipDeviceSynchronize());
         float *nh = nullptr;
         const size_t one = (size_t)b->n * 8;
@@ -183,17 +300,50 @@ int csdr_fastfir_batch_setup(csdr_fastfir_batch *b, int channel, double flo, dou
     }
     if (channel < 0 && b->per_channel) {
         for (int c = 0; c < b->channels; c++) {
-            int rc = upload_response(b, c, H);
+            int rc = set_response(b, c, H);
             if (rc) return rc;
-            b->resp[c] = H;
         }
     } else {
-        const int slot = channel < 0 ? 0 : channel;
-        int rc = upload_response(b, slot, H);
+        int rc = set_response(b, channel < 0 ? 0 : channel, H);
         if (rc) return rc;
-        b->resp[slot] = H;
     }
     return 1;
+}
+
+/* CFastFIR::SetupParameters for many filters of the object at once, designed on the DEVICE: per entry the host does the
+ * reference's sanity check and two divisions and queues a job; the next process call launches all of them right behind
+ * its patch kernel (see include/cutesdr_mi.h). */
+int csdr_fastfir_batch_setup_many(csdr_fastfir_batch *b, int n, const int *channel, const double *flo, const double *fhi,
+                                  const double *offset, const double *fs, int *status)
+{
+    if (!have_device()) return CSDR_EHIP;
+    if (!b || n < 0 || (n > 0 && (!channel || !flo || !fhi || !offset || !fs || !status)))
+        return fail(CSDR_EINVAL, "bad handle, negative count or null array");
+    for (int i = 0; i < n; i++)
+        if (channel[i] < -1 || channel[i] >= b->channels) return fail(CSDR_EINVAL, "entry %d: channel %d", i, channel[i]);
+    if (n == 0) return CSDR_OK;
+    if (!device_ok(b->device)) return CSDR_EHIP;
+    { const int rc = design_state(b); if (rc) return rc; }
+    for (int i = 0; i < n; i++) {
+        const int ch = channel[i];
+        if (ch < 0) {
+            // shared filter: same early-out as the reference (fastfir.cpp:182-186)
+            if (!b->per_channel && flo[i] == b->flo && fhi[i] == b->fhi && offset[i] == b->off && fs[i] == b->fs) { status[i] = 0; continue; }
+            b->flo = flo[i]; b->fhi = fhi[i]; b->off = offset[i]; b->fs = fs[i];
+        }
+        double nfc, nfs;
+        if (!fastfir_design_job(flo[i], fhi[i], offset[i], fs[i], nfc, nfs)) { status[i] = CSDR_EINVAL; continue; }   // old taps kept
+        if (ch >= 0 && !b->per_channel) {
+            // the object turns per-channel by the one-filter call's reallocation path (once in its life: that call
+            // designs this entry on the host and waits for the device); the job queued below gives the same filter
+            const int rc = csdr_fastfir_batch_setup(b, ch, flo[i], fhi[i], offset[i], fs[i]);
+            if (rc < 0) { for (int j = i; j < n; j++) status[j] = rc; return rc; }
+        }
+        if (ch < 0 && b->per_channel) for (int c = 0; c < b->channels; c++) queue_job(b, c, nfc, nfs);
+        else queue_job(b, ch < 0 ? 0 : ch, nfc, nfs);
+        status[i] = 1;
+    }
+    return CSDR_OK;
 }
 
 int csdr_fastfir_batch_reset(csdr_fastfir_batch *b)
@@ -207,7 +357,13 @@ int csdr_fastfir_batch_reset(csdr_fastfir_batch *b)
 int csdr_fastfir_batch_get_response(csdr_fastfir_batch *b, int channel, double *h_out)
 {
     if (!b || !h_out || channel < 0 || channel >= b->channels) return fail(CSDR_EINVAL, "bad argument");
-    const std::vector<cd> &H = b->resp[b->per_channel ? channel : 0];
+    const int slot = b->per_channel ? channel : 0;
+    if (b->stale[slot]) {                  // designed on the device: flush, wait for the object's stream, fetch
+        if (!device_ok(b->device)) return CSDR_EHIP;
+        const int rc = fetch_mirror(b, slot);
+        if (rc) return rc;
+    }
+    const std::vector<cd> &H = b->resp[slot];
     memcpy(h_out, H.data(), sizeof(cd) * H.size());
     return CSDR_OK;
 }
@@ -230,7 +386,7 @@ int csdr_fastfir_batch_process(csdr_fastfir_batch *b, const float *d_in, long lo
     if (!device_ok(b->device)) return CSDR_EHIP;
     hipStream_t s = (hipStream_t)stream;
     b->last_stream = s;
-    { const int rcp = b->patches.flush(s); if (rcp) return rcp; }      // responses set up since the last call
+    { const int rcp = flush_control(b, s); if (rcp) return rcp; }      // responses set up since the last call: patches, then designs
     FastFirArgs a;
     const size_t hist_half = (size_t)b->channels * L * 2;      // floats
     a.in = (const v2f_h *)d_in; a.out = (v2f_h *)d_out;
@@ -284,12 +440,13 @@ int csdr__fastfir_batch_copy_row(csdr_fastfir_batch *dst, int dr, csdr_fastfir_b
     const size_t shalf = (size_t)src->channels * L * 2, dhalf = (size_t)dst->channels * L * 2;
     CSDR_HIP(hipMemcpy(dst->d_hist + dst->hist_cur * dhalf + (size_t)dr * L * 2,
                        src->d_hist + src->hist_cur * shalf + (size_t)sr * L * 2, (size_t)L * 8, hipMemcpyDeviceToDevice));
-    const std::vector<cd> &H = src->resp[src->per_channel ? sr : 0];
+    const int sslot = src->per_channel ? sr : 0;
+    { const int rcm = fetch_mirror(src, sslot); if (rcm) return rcm; }      // the response in use may exist on the device only
+    const std::vector<cd> &H = src->resp[sslot];
     if (dst->channels > 1 && !dst->per_channel) return fail(CSDR_ESTATE, "destination rows share one filter");
     const int slot = dst->per_channel ? dr : 0;
-    int rc = upload_response(dst, slot, H);
+    int rc = set_response(dst, slot, H);
     if (rc) return rc;
-    dst->resp[slot] = H;
     dst->flo = dst->fhi = dst->off = dst->fs = std::nan("");      // parameters unknown: the next setup always designs
     return CSDR_OK;
 }

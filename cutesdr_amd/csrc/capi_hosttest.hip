@@ -20,6 +20,11 @@ int csdr__host_fastfir_design(int n, double flo, double fhi, double off, double 
     memcpy(h_out, H.data(), sizeof(cd) * n);
     return 0;
 }
+// what csdr_fastfir_batch_setup_many does per entry on the host: 0 and the two doubles of the design job, or -1 (rejected)
+int csdr__host_design_job(double flo, double fhi, double off, double fs, double *nfc, double *nfs)
+{
+    return fastfir_design_job(flo, fhi, off, fs, *nfc, *nfs) ? 0 : -1;
+}
 int csdr__host_fastfir_bin_of(int log2n, int t, int r) { return fastfir_bin_of(log2n, t, r); }
 
 int csdr__host_dc_plan(double in_rate, double bw, int *codes, double *out_rate, int *warmup)

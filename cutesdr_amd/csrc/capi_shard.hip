@@ -105,6 +105,32 @@ int csdr_demod_shard_set_demod(csdr_demod_shard *S, int channel, int mode, const
     SHARD_OF(S, channel, s);
     return csdr_demod_batch_set_demod(S->b[s], channel - S->first[s], mode, info);
 }
+/* csdr_demod_batch_set_demod_many with global channel ids: every shard gets its entries, in array order, in one call */
+int csdr_demod_shard_set_demod_many(csdr_demod_shard *S, int n, const int *channel, const int *mode,
+                                    const csdr_demod_info *info, int *status)
+{
+    if (!have_device()) return CSDR_EHIP;
+    if (!S || n < 0 || (n > 0 && (!channel || !mode || !info))) return fail(CSDR_EINVAL, "bad handle, negative count or null array");
+    for (int i = 0; i < n; i++)
+        if (channel[i] < 0 || channel[i] >= S->channels || mode[i] < 0 || mode[i] > 6)
+            return fail(CSDR_EINVAL, "entry %d: channel %d, mode %d", i, channel[i], mode[i]);
+    int err = CSDR_OK;
+    std::vector<int> idx, ch, md, st;
+    std::vector<csdr_demod_info> inf;
+    for (size_t s = 0; s < S->b.size(); s++) {
+        idx.clear(); ch.clear(); md.clear(); inf.clear();
+        for (int i = 0; i < n; i++)
+            if (channel[i] >= S->first[s] && channel[i] < S->first[s] + S->count[s]) {
+                idx.push_back(i); ch.push_back(channel[i] - S->first[s]); md.push_back(mode[i]); inf.push_back(info[i]);
+            }
+        if (idx.empty()) continue;
+        st.assign(idx.size(), 0);
+        const int rc = csdr_demod_batch_set_demod_many(S->b[s], (int)idx.size(), ch.data(), md.data(), inf.data(), st.data());
+        if (rc < 0 && !err) err = rc;
+        if (status) for (size_t q = 0; q < idx.size(); q++) status[idx[q]] = st[q];
+    }
+    return err;
+}
 int csdr_demod_shard_set_freq(csdr_demod_shard *S, int channel, double freq)
 {
     SHARD_OF(S, channel, s);

@@ -76,6 +76,21 @@ inline void host_fft(std::vector<cd> &a, int sign)
     }
 }
 
+// The host half of a design that runs on the device (fastfir_design_kernels.hip): the reference's sanity check on the
+// edges (fastfir.cpp:195-203; false = rejected, the old taps stay) and the two normalised doubles everything else follows
+// from; fastfir_design below starts with the same call.
+inline bool fastfir_design_job(double flo, double fhi, double offset, double fs, double &nfc, double &nfs)
+{
+    flo += offset;
+    fhi += offset;
+    if (flo >= fhi || flo >= fs / 2.0 || flo <= -fs / 2.0 || fhi >= fs / 2.0 || fhi <= -fs / 2.0)
+        return false;
+    const double nfl = flo / fs, nfh = fhi / fs;
+    nfc = (nfh - nfl) / 2.0;
+    nfs = kTwoPi * (nfh + nfl) / 2.0;
+    return true;
+}
+
 // CFastFIR::SetupParameters (dsp/fastfir.cpp:178-259) with FFT size n, taps n/2+1:
 // Blackman-Nuttall windowed sinc (window :93-101), shifted to the pass-band centre, scaled by
 // 1/n, zero padded and forward transformed.  Returns false when the reference's sanity check
@@ -83,12 +98,8 @@ inline void host_fft(std::vector<cd> &a, int sign)
 inline bool fastfir_design(int n, double flo, double fhi, double offset, double fs, std::vector<cd> &H)
 {
     const int p = n / 2 + 1;
-    flo += offset;
-    fhi += offset;
-    if (flo >= fhi || flo >= fs / 2.0 || flo <= -fs / 2.0 || fhi >= fs / 2.0 || fhi <= -fs / 2.0)
-        return false;
-    const double nfl = flo / fs, nfh = fhi / fs;
-    const double nfc = (nfh - nfl) / 2.0, nfs = kTwoPi * (nfh + nfl) / 2.0;
+    double nfc, nfs;
+    if (!fastfir_design_job(flo, fhi, offset, fs, nfc, nfs)) return false;
     const double centre = 0.5 * (double)(p - 1);
     H.assign(n, cd(0.0, 0.0));
     const auto win = fastfir_window(p);

@@ -107,16 +107,29 @@ struct PatchQueue {
     int flush(hipStream_t s)
     {
         if (list.empty()) return CSDR_OK;
+        const int rc = launch(s);
+        return rc ? rc : retire(s);
+    }
+    // The two halves of flush(), for an owner whose own kernel reads memory it took from the current arena (the filter's
+    // design jobs, capi_fastfir.hip): launch() applies the queue, the owner launches its kernel on `s`, retire() closes
+    // the arena behind both -- it is rewritten only when everything that read it has finished.
+    int launch(hipStream_t s)
+    {
+        if (list.empty()) return CSDR_OK;
         unsigned char *h = nullptr, *d = nullptr;
         int rc = take(list.size() * sizeof(PatchDesc), &h, &d);
         if (rc) return rc;
         memcpy(h, list.data(), list.size() * sizeof(PatchDesc));
         CSDR_HIP(patch_apply_launch((const PatchDesc *)d, (int)list.size(), s));
+        list.clear(); host_of.clear();
+        return CSDR_OK;
+    }
+    int retire(hipStream_t s)
+    {
         Arena &a = arena[cur];
         if (!a.done) CSDR_HIP(hipEventCreateWithFlags(&a.done, hipEventDisableTiming));
         CSDR_HIP(hipEventRecord(a.done, s));
         a.in_flight = true;
-        list.clear(); host_of.clear();
         cur ^= 1;
         return CSDR_OK;
     }

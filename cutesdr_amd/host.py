@@ -94,6 +94,17 @@ class FastFirBatch:
     def setup(self, flo, fhi, offset, fs, channel=-1):
         return check(lib().csdr_fastfir_batch_setup(self.h, channel, flo, fhi, offset, fs), "batch_setup")
 
+    def setup_many(self, channels, flo, fhi, offset, fs):
+        """SetupParameters of many channels in one call, designed on the device (csdr_fastfir_batch_setup_many): arrays
+        (scalars are broadcast) -> status per entry (1 designed, 0 unchanged, CSDR_EINVAL rejected: old taps kept)"""
+        ch = np.ascontiguousarray(channels, dtype=np.int32)
+        n = len(ch)
+        a = [np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (n,))) for v in (flo, fhi, offset, fs)]
+        status = np.zeros(n, dtype=np.int32)
+        check(lib().csdr_fastfir_batch_setup_many(self.h, n, _vp(ch), _vp(a[0]), _vp(a[1]), _vp(a[2]), _vp(a[3]), _vp(status)),
+              "batch_setup_many")
+        return status
+
     def reset(self):
         check(lib().csdr_fastfir_batch_reset(self.h), "batch_reset")
 
@@ -537,6 +548,17 @@ def fm_defaults():
                      AgcOn=1, AgcHangOn=0, Symetric=1)
 
 
+def _set_demod_many(fn, handle, channels, modes, infos, what):
+    ch = np.ascontiguousarray(channels, dtype=np.int32)
+    md = np.ascontiguousarray(modes, dtype=np.int32)
+    n = len(ch)
+    assert len(md) == n and len(infos) == n
+    arr = infos if isinstance(infos, C.Array) else (DemodInfo * n)(*infos)
+    status = np.zeros(n, dtype=np.int32)
+    check(fn(handle, n, _vp(ch), _vp(md), arr, _vp(status)), what)
+    return status
+
+
 class CDemodulator(_Obj):
     """dsp/demodulator.h:56-100 -- the whole chain, host double buffers, reference call semantics."""
     _destroy = "csdr_demod_destroy"
@@ -637,6 +659,11 @@ class DemodBatch(_Obj):
 
     def set_demod(self, channel, mode, info):
         check(lib().csdr_demod_batch_set_demod(self.h, channel, mode, C.byref(info)), "batch_set_demod")
+
+    def set_demod_many(self, channels, modes, infos):
+        """set_demod for every entry, in order, in one call; same-mode entries on a committed batch have their filters
+        designed on the device.  infos: a sequence of DemodInfo or a ctypes array of them -> status per entry"""
+        return _set_demod_many(lib().csdr_demod_batch_set_demod_many, self.h, channels, modes, infos, "batch_set_demod_many")
 
     def commit(self):
         check(lib().csdr_demod_batch_commit(self.h), "batch_commit")
@@ -759,6 +786,10 @@ class ShardedDemodBatch(_Obj):
 
     def set_demod(self, channel, mode, info):
         check(lib().csdr_demod_shard_set_demod(self.h, channel, mode, C.byref(info)), "shard_set_demod")
+
+    def set_demod_many(self, channels, modes, infos):
+        """DemodBatch.set_demod_many with global channel ids"""
+        return _set_demod_many(lib().csdr_demod_shard_set_demod_many, self.h, channels, modes, infos, "shard_set_demod_many")
 
     def commit(self):
         check(lib().csdr_demod_shard_commit(self.h), "shard_commit")

@@ -74,6 +74,18 @@ void csdr_fastfir_batch_destroy(csdr_fastfir_batch *b);
 /* channel = -1: one filter shared by every channel; otherwise that channel's own filter */
 int csdr_fastfir_batch_setup(csdr_fastfir_batch *b, int channel, double flo, double fhi,
                              double offset, double fs);
+/* The same for n filters in one call, designed ON THE DEVICE (fp64, one workgroup per filter): per entry the host does
+ * the reference's sanity check and queues a job of two doubles; the next csdr_fastfir_batch_process launches all queued
+ * jobs on its stream right behind its patch kernel -- behind everything in flight on that stream, in front of the filter
+ * launch, nobody else waited for.  Entries apply in array order: a later entry for a channel replaces an earlier one, a
+ * later csdr_fastfir_batch_setup of that channel cancels its queued job, a job queued after a csdr_fastfir_batch_setup of
+ * the channel wins.  channel[i] = -1: the shared filter (early-out as above) or, on a per-channel object, every channel;
+ * the first entry that names a channel turns a shared-filter object per-channel (that one step waits for the device).
+ * status[i]: 1 designed, 0 unchanged, CSDR_EINVAL rejected by the sanity check (old taps kept, the other entries still
+ * apply).  Returns CSDR_OK or the first hard error; bad arguments (null arrays, n < 0, a channel out of range) return
+ * CSDR_EINVAL and change nothing.  csdr_fastfir_batch_get_response of such a channel waits for the object's stream. */
+int csdr_fastfir_batch_setup_many(csdr_fastfir_batch *b, int n, const int *channel, const double *flo, const double *fhi,
+                                  const double *offset, const double *fs, int *status);
 /* clears the overlap history (as a freshly constructed CFastFIR) */
 int csdr_fastfir_batch_reset(csdr_fastfir_batch *b);
 /* d_in/d_out: device pointers, interleaved fp32 I/Q, [channels][stride] (strides in complex
@@ -282,6 +294,16 @@ int csdr_demod_batch_set_input_rate(csdr_demod_batch *b, double rate);
  * AGC, S-meter; new demodulator, decimator from zero histories); nothing else of the batch is disturbed.  The call
  * synchronises the device. */
 int csdr_demod_batch_set_demod(csdr_demod_batch *b, int channel, int mode, const csdr_demod_info *info);
+/* csdr_demod_batch_set_demod for each of n entries, in array order (a channel named twice ends with its last entry).
+ * An entry that keeps its receiver's mode on a committed batch does not design its filter on the caller's thread: CW
+ * offset, AGC constants, S-meter rate, squelch / FM high-pass and AM low-pass are queued as patches as in the one-receiver
+ * call, the frequency response goes to the filter object's device-side design queue -- one
+ * csdr_fastfir_batch_setup_many per plan group -- and nothing waits.  An entry that changes the mode, and every entry
+ * before commit(), runs the one-receiver call unchanged.  status (may be NULL): per entry what the one-receiver call
+ * would have returned.  Returns CSDR_OK or the first error; bad arguments (null arrays, n < 0, a channel or mode out of
+ * range) return CSDR_EINVAL and change nothing. */
+int csdr_demod_batch_set_demod_many(csdr_demod_batch *b, int n, const int *channel, const int *mode,
+                                    const csdr_demod_info *info, int *status);
 int csdr_demod_batch_commit(csdr_demod_batch *b);
 /* Receivers cut from shared streams (one radio, many receivers: SURVEY 8e "if channels are cut from one stream"):
  * receiver c reads row input_row[c] of d_in (or datagram stream input_row[c]) instead of row c; several receivers
@@ -360,6 +382,9 @@ int csdr_demod_shard_count(csdr_demod_shard *s);
 int csdr_demod_shard_range(csdr_demod_shard *s, int shard, int *first, int *count, int *device);
 int csdr_demod_shard_set_input_rate(csdr_demod_shard *s, double rate);   /* every shard's batch; before or after commit */
 int csdr_demod_shard_set_demod(csdr_demod_shard *s, int channel, int mode, const csdr_demod_info *info);
+/* csdr_demod_batch_set_demod_many with GLOBAL channel ids: entries routed to the owning shards, one call per shard */
+int csdr_demod_shard_set_demod_many(csdr_demod_shard *s, int n, const int *channel, const int *mode,
+                                    const csdr_demod_info *info, int *status);
 int csdr_demod_shard_commit(csdr_demod_shard *s);
 int csdr_demod_shard_set_freq(csdr_demod_shard *s, int channel, double freq);
 double csdr_demod_shard_get_output_rate(csdr_demod_shard *s, int channel);
