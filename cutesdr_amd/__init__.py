@@ -8,4 +8,5 @@ it is plumbing over the C ABI and contains no signal processing of its own.
 from . import _capi  # noqa: F401
 from .host import *  # noqa: F401,F403
 from .host import SoundSinkBatch  # noqa: F401
+from .host import TestGenBatch  # noqa: F401
 

@@ -6,6 +6,7 @@
 #include "dc_host.hpp"
 #include "pc_host.hpp"
 #include "display_plan.hpp"
+#include "testgen_host.hpp"
 #include "fastfir_kernels.h"
 #include <cstring>
 
@@ -94,6 +95,68 @@ void csdr__host_display_plan(const int *state5, long long n, int N, long long *o
 int csdr__host_display_skip_value(double sample_rate, int fft_size, int max_display_rate)
 {
     return display_skip_value(sample_rate, fft_size, max_display_rate);
+}
+
+// the batch signal generator's host logic (testgen_host.hpp): the crossing helper, the pulse pattern, and one
+// generator's state machine evaluated on the CPU with the kernel's integer formulas
+unsigned long long csdr__host_tg_first_crossing(double x0, double d, double limit, int strict, double *value)
+{
+    return tg::first_crossing(x0, d, limit, strict != 0, value);
+}
+double csdr__host_tg_value_at(double x0, double d, unsigned long long index) { return tg::value_at(x0, d, index); }
+void csdr__host_tg_pulse_pattern(double fs, double period, double width, unsigned long long *K, unsigned long long *W)
+{
+    tg::Gen g;
+    g.fs = fs; g.period = period; g.width = width;
+    g.pulse_pattern();
+    *K = g.K; *W = g.W;
+}
+void *csdr__host_tg_create(void) { tg::Gen *g = new tg::Gen(); g->reset(); g->on = true; return g; }
+void csdr__host_tg_destroy(void *h) { delete (tg::Gen *)h; }
+// what: 0 start, 1 stop, 2 rate, 3 width, 4 period, 5 signal power, 6 noise power, 7 reset
+void csdr__host_tg_slot(void *h, int what, double v)
+{
+    tg::Gen &g = *(tg::Gen *)h;
+    switch (what) {
+    case 0: g.on_sweep_start(v); break;
+    case 1: g.on_sweep_stop(v); break;
+    case 2: g.on_sweep_rate(v); break;
+    case 3: g.on_pulse_width(v); break;
+    case 4: g.on_pulse_period(v); break;
+    case 5: g.on_signal_pwr(v); break;
+    case 6: g.on_noise_pwr(v); break;
+    default: g.reset(); break;
+    }
+}
+// n samples at rate fs: phase[j] (top 64 bits of the turn fraction) and gate[j] of every sample, as the kernel
+// evaluates them; returns the launches the call would take
+int csdr__host_tg_run(void *h, int n, double fs, unsigned long long *phase, int *gate)
+{
+    tg::Gen &g = *(tg::Gen *)h;
+    if (g.fs != fs) { g.fs = fs; g.pulse_valid = false; g.reset(); }
+    tg::ChanParam p;
+    g.pulse((uint32_t)n, p);
+    uint32_t done = 0;
+    int launches = 0;
+    while (done < (uint32_t)n) {
+        p.nseg = 0;
+        const uint32_t lo = done;
+        done += g.advance(done, (uint32_t)n - done, p);
+        launches++;
+        for (uint32_t j = lo; j < done; j++) {
+            uint32_t s = 0;
+            for (uint32_t k = 1; k < p.nseg; k++) s += p.seg_start[k] <= j;
+            const uint64_t t = j - p.seg_start[s];
+            const tg::u128 P = (((tg::u128)p.seg_p[s][1] << 64) | p.seg_p[s][0])
+                + (((tg::u128)p.seg_d[s][1] << 64) | p.seg_d[s][0]) * (tg::u128)t
+                + (((tg::u128)p.seg_d2[s][1] << 64) | p.seg_d2[s][0]) * (tg::u128)(t * (t - 1) / 2);
+            phase[j] = (uint64_t)(P >> 64);
+            const uint64_t m = (uint64_t)j + 1;
+            const uint64_t pos = m < p.wrap1 ? p.pos0 + m : (m - p.wrap1) % p.period;
+            gate[j] = !p.gate_on || pos < p.width;
+        }
+    }
+    return launches;
 }
 
 }  // extern "C"

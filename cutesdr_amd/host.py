@@ -1231,3 +1231,60 @@ class SoundSinkBatch(_Obj):
 
     def ppm_error(self, channel):
         return lib().csdr_soundsink_batch_get_ppm_error(self.h, channel)
+
+
+class TestGenBatch(_Obj):
+    """C independent CTestBench generators (gui/testbench.cpp:352-517: sweep, pulse, noise), one per receiver, writing
+    the batch chain's fp32 input rows on the device.  Setters as the reference's slots, in Hz, Hz/s, seconds and dB;
+    channel < 0: every receiver.  A receiver whose generator is off leaves its row untouched."""
+    _destroy = "csdr_testgen_batch_destroy"
+    __test__ = False                     # (not a test class, whatever the name says)
+
+    def __init__(self, channels, device=0):
+        self.channels, self.device = int(channels), device
+        self.h = check_ptr(lib().csdr_testgen_batch_create(device, self.channels), "csdr_testgen_batch_create")
+
+    def OnGenOn(self, On, channel=-1):
+        check(lib().csdr_testgen_batch_set_on(self.h, channel, int(bool(On))), "csdr_testgen_batch_set_on")
+
+    def OnSweepStart(self, hz, channel=-1):
+        check(lib().csdr_testgen_batch_set_sweep_start(self.h, channel, hz), "csdr_testgen_batch_set_sweep_start")
+
+    def OnSweepStop(self, hz, channel=-1):
+        check(lib().csdr_testgen_batch_set_sweep_stop(self.h, channel, hz), "csdr_testgen_batch_set_sweep_stop")
+
+    def OnSweepRate(self, hz_per_s, channel=-1):
+        check(lib().csdr_testgen_batch_set_sweep_rate(self.h, channel, hz_per_s), "csdr_testgen_batch_set_sweep_rate")
+
+    def OnPulseWidth(self, seconds, channel=-1):
+        check(lib().csdr_testgen_batch_set_pulse_width(self.h, channel, seconds), "csdr_testgen_batch_set_pulse_width")
+
+    def OnPulsePeriod(self, seconds, channel=-1):
+        check(lib().csdr_testgen_batch_set_pulse_period(self.h, channel, seconds), "csdr_testgen_batch_set_pulse_period")
+
+    def OnSignalPwr(self, db, channel=-1):
+        check(lib().csdr_testgen_batch_set_signal_power(self.h, channel, db), "csdr_testgen_batch_set_signal_power")
+
+    def OnNoisePwr(self, db, channel=-1):
+        check(lib().csdr_testgen_batch_set_noise_power(self.h, channel, db), "csdr_testgen_batch_set_noise_power")
+
+    def Reset(self, channel=-1):
+        check(lib().csdr_testgen_batch_reset(self.h, channel), "csdr_testgen_batch_reset")
+
+    def SetSeed(self, seed):
+        check(lib().csdr_testgen_batch_set_seed(self.h, seed), "csdr_testgen_batch_set_seed")
+
+    def generate_ptr(self, d_out, stride, n, samplerate, stream=None, real=False):
+        """d_out: device [channels][stride] complex fp32 (fp32 mono when real); asynchronous on stream"""
+        fn = lib().csdr_testgen_batch_generate_real if real else lib().csdr_testgen_batch_generate
+        check(fn(self.h, C.c_void_p(d_out), stride, n, samplerate, C.c_void_p(stream) if stream else None),
+              "csdr_testgen_batch_generate")
+
+    def CreateGeneratorSamples(self, rows, length, samplerate, offset=0):
+        """rows: device tensor [channels, T], complex64 or float32 (the real overload); writes samples
+        offset..offset+length-1 of every row whose generator is on, on the tensor's current stream"""
+        import torch
+        assert rows.is_cuda and rows.shape[0] == self.channels and rows.stride(1) == 1
+        assert rows.dtype in (torch.complex64, torch.float32) and offset + length <= rows.shape[1]
+        self.generate_ptr(rows.data_ptr() + offset * rows.element_size(), rows.stride(0), length, samplerate,
+                          torch.cuda.current_stream(rows.device).cuda_stream, real=rows.dtype == torch.float32)

@@ -651,6 +651,75 @@ int csdr_ingest_spurcal_host(int device, int n, const double *in_iq, double *dc_
 int csdr_ingest_spurcal_packets(int device, const void *d_packets, int channels, int npackets, int pkt_len, double *d_dc,
                                 void *stream);
 
+/* ----------------------------------------------------------------------------------------
+ * Batch signal generator: C independent CTestBench generators (gui/testbench.cpp:352-517: swept complex tone, pulse
+ * gating, additive Gaussian noise), one per receiver, writing the batch chain's fp32 input rows on the device -- the
+ * first step of CSdrInterface::ProcessIQData (sdrinterface.cpp:883), where the generator REPLACES the live IQ.
+ *
+ * State.  Every receiver has the reference's members: sweep start / stop (Hz), sweep rate (Hz/s), pulse width /
+ * period (s), signal / noise power (dB; amplitude 32767 * 10^(dB/20)), on/off, generator sample rate.  Defaults as the
+ * constructor's (:90-121): off, width 0.01 s, period 0.5 s, sample rate 1; the members the constructor leaves to the
+ * GUI start as: start = stop = 0 Hz, rate 0 Hz/s, signal 0 dB, noise -160 dB.  Each setter has exactly the state
+ * effect of its slot: set_sweep_start (:225-230) and set_sweep_stop (:232-237) put the frequency back to start and
+ * the phase to 0; set_sweep_rate (:239-244) puts the phase to 0 and the per-sample increment to rate / sample rate
+ * (which re-arms a finished sweep for one step); the pulse and power setters (:312-332) change their member only;
+ * reset is the generator part of Reset() (:527-532, :575: frequency <- start, phase <- 0, increment <- rate / sample
+ * rate, amplitudes, pulse timer <- 0).  channel < 0: every receiver.  All state is on the host: a setter waits for
+ * nothing.  Setters and generate of one object exclude each other (one mutex).
+ *
+ * What is exact.  The frequency sequence f <- fl(f + inc) with its end of sweep (first f >= stop, :424-427) and the
+ * pulse timer t <- fl(t + 1/Fs) with its restart (t > period) and gate (off while t > width, :399-406) are the
+ * reference's fp64 recurrences bit for bit.  The phase is the exact sum of that frequency sequence over Fs, in turns
+ * modulo 1 (128-bit fixed point; the reference's own fp64 accumulator with one fmod per call drifts by about 1.5e-15
+ * rad per sample from it in 256-sample calls), and does not depend on how the stream is cut into calls: generate(n)
+ * once and generate(n/k) k times write the same words -- complex and real, sweep, pulse and noise alike.
+ *
+ * Noise (:433-444) keeps Marsaglia's polar method and replaces libc rand() by a counter-based generator, all
+ * arithmetic on unsigned 64-bit words modulo 2^64:
+ *     mix(z):  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^ (z >> 31)
+ *     key(c)    = mix(seed + 0x9E3779B97F4A7C15 * (c + 1))                    c = receiver index, seed 0 until set_seed
+ *     h(c,i,a)  = mix(key(c) + 0x9E3779B97F4A7C15 * (32 * i + a))             a = attempt 0..31
+ *     k1 = h >> 33,  k2 = (h >> 2) & 0x7FFFFFFF                               the two 31-bit draws
+ *     u1 = 1 - 2 * k1 / 2147483647,  u2 = 1 - 2 * k2 / 2147483647,  r = u1 * u1 + u2 * u2      (fp64, no fused multiply-add)
+ * The first attempt with neither r >= 1 nor r == 0 is taken: rad = sqrt(-2 ln(r) / r) in fp64, I += noise amplitude *
+ * u1 * rad, Q += noise amplitude * u2 * rad (the real form adds the I term only); 32 rejections in a row (probability
+ * 4e-22) add nothing.  i counts the samples the receiver has generated since the object's creation or the last
+ * set_seed -- every sample of every call while it is on, with or without noise; a reset does not touch it.  Noise is
+ * added only while noise power > -160 dB (:433).  signal + noise is summed in fp64 and rounded to fp32 once.
+ *
+ * Deliberate deviations: a sample rate different from the last call's resets the receiver BEFORE the call's first
+ * sample (the reference queues a Qt signal whose arrival time is undefined, :361-365); own generator instead of rand().
+ * Out of scope: a drop-in CTestBench class (it is a QDialog), the DisplayData scope / FFT view, the USE_FILE playback
+ * kludge, a generator that emits datagrams, fusing the generator into the down-converter's loads, a shard form (a
+ * shard host makes one generator per device, as for the batch sound sink).
+ * -------------------------------------------------------------------------------------- */
+typedef struct csdr_testgen_batch csdr_testgen_batch;
+/* NULL without a HIP device (no CPU fallback) */
+csdr_testgen_batch *csdr_testgen_batch_create(int device, int channels);
+void csdr_testgen_batch_destroy(csdr_testgen_batch *t);
+int csdr_testgen_batch_set_on(csdr_testgen_batch *t, int channel, int on);                        /* OnGenOn :307-310 */
+int csdr_testgen_batch_set_sweep_start(csdr_testgen_batch *t, int channel, double hz);            /* OnSweepStart :225-230 */
+int csdr_testgen_batch_set_sweep_stop(csdr_testgen_batch *t, int channel, double hz);             /* OnSweepStop :232-237 */
+int csdr_testgen_batch_set_sweep_rate(csdr_testgen_batch *t, int channel, double hz_per_s);       /* OnSweepRate :239-244 */
+int csdr_testgen_batch_set_pulse_width(csdr_testgen_batch *t, int channel, double seconds);       /* OnPulseWidth :312-315; <= 0: no gating */
+int csdr_testgen_batch_set_pulse_period(csdr_testgen_batch *t, int channel, double seconds);      /* OnPulsePeriod :317-320 */
+int csdr_testgen_batch_set_signal_power(csdr_testgen_batch *t, int channel, double db);           /* OnSignalPwr :322-326 */
+int csdr_testgen_batch_set_noise_power(csdr_testgen_batch *t, int channel, double db);            /* OnNoisePwr :328-332 */
+int csdr_testgen_batch_reset(csdr_testgen_batch *t, int channel);                                 /* Reset :527-532, :575 */
+/* seed of the noise of every receiver; puts every receiver's sample counter i back to 0 */
+int csdr_testgen_batch_set_seed(csdr_testgen_batch *t, unsigned long long seed);
+/* CreateGeneratorSamples(int, TYPECPX*, double) (:352-447) of every receiver: n complex fp32 samples into the front of
+ * every row of d_iq = device [channels][stride] complex fp32, asynchronous on `stream`.  A receiver whose generator is
+ * off leaves its row untouched and its state as it is (:359-360).  d_iq 16-byte aligned, stride even and >= n, n <=
+ * 2^30, sample_rate > 0; CSDR_EINVAL before any state changes otherwise.  One launch per call, except that a receiver
+ * whose sweep passes more than 8 binades of fp64 inside the call (a sweep through 0 Hz in a very long call) adds
+ * launches for the rest.  Queued calls need not be waited for: the words of a launch travel in a ring of 16 pinned
+ * buffers, and a call waits (on that launch's event only) when the launch 16 before it has not finished. */
+int csdr_testgen_batch_generate(csdr_testgen_batch *t, float *d_iq, long long stride, int n, double sample_rate, void *stream);
+/* the TYPEREAL overload (:454-517): 3 * amplitude * cos(phase), the noise's I term; fp32 mono rows, stride a multiple of 4 */
+int csdr_testgen_batch_generate_real(csdr_testgen_batch *t, float *d_out, long long stride, int n, double sample_rate,
+                                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif
