@@ -60,6 +60,17 @@ inline bool have_device()
     return false;
 }
 
+// An event that only orders streams (hipEventDisableTiming), made on demand and destroyed with its owner.
+struct Event {
+    hipEvent_t e = nullptr;
+    hipError_t create() { return e ? hipSuccess : hipEventCreateWithFlags(&e, hipEventDisableTiming); }
+    operator hipEvent_t() const { return e; }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+};
+
 // Host staging of the drop-in classes' double* buffers ("host double* -> pinned staging -> HBM fp32"): a
 // page-locked fp32 buffer the DMA engines read and write directly (a pageable source goes through the runtime's own
 // bounce buffer first), grown on demand with its contents kept, and the two conversions at the boundary as plain

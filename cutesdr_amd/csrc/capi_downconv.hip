@@ -1,5 +1,6 @@
 // capi_downconv.hip -- C ABI for CDownConvert (single-channel host form + batched device form).
 #include "capi_common.hpp"
+#include "capi_internal.hpp"
 #include "downconv_kernels.h"
 #include "dc_host.hpp"
 #include "patch_queue.hpp"
@@ -98,17 +99,13 @@ extern "C" int csdr__downconvert_batch_copy_channel(csdr_downconvert_batch *dst,
 extern "C" int csdr__downconv_force_dynamic(int on) { return downconv_force_dynamic(on); }
 /* internal (the batch chain): how many one-wave workgroups the next launches of this handle are cut into; 0 = the
  * default, one round of the chip's 4096 slots.  A down-converter that starts while another group's walks hold part
- * of the chip is sized for what is left, so that it still runs as ONE round (capi_demod.hip). */
+ * of the chip is sized for what is left, so that it still runs as ONE round (capi_demod_batch.hip). */
 extern "C" int csdr__downconvert_batch_set_wgs(csdr_downconvert_batch *b, long wgs)
 {
     if (!b || wgs < 0) return fail(CSDR_EINVAL, "bad argument");
     b->wgs_hint = wgs;
     return CSDR_OK;
 }
-extern "C" int csdr__downconvert_batch_process_rows(csdr_downconvert_batch *b, const float *d_in, long long in_stride,
-                                                    const int *d_in_rows, int n_per_channel, float *d_out,
-                                                    long long out_stride, void *stream, const void *d_packets, int pkt_len,
-                                                    const csdr::DcBlank *blank);
 
 extern "C" {
 

@@ -1,5 +1,6 @@
 // capi_fastfir.hip -- C ABI for CFastFIR (single-channel host form and batched device form).
 #include "capi_common.hpp"
+#include "capi_internal.hpp"
 #include <algorithm>
 #include "fastfir_kernels.h"
 #include "fastfir_design_kernels.h"

@@ -2,6 +2,7 @@
 // CNoiseProc (dsp/noiseproc.h:23-58), wire-format unpack (interface/netiobase.cpp:479-527) and the
 // NCO-spur DC estimate (interface/sdrinterface.cpp:829-848).
 #include "capi_common.hpp"
+#include "capi_internal.hpp"
 #include "frontend_kernels.h"
 #include "ref_constants.hpp"
 #include <cmath>

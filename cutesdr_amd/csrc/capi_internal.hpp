@@ -1,0 +1,27 @@
+// capi_internal.hpp -- entry points one unit of the library offers to the others (csdr__*: exported for tests and
+// tools, not in the public header).  The defining and the using units both include this, so a signature that changes
+// on one side only does not compile.
+#pragma once
+#include "../../include/cutesdr_mi.h"
+
+namespace csdr { struct DcBlank; }                      // downconv_kernels.h
+
+extern "C" {
+/* capi_downconv.hip */
+int csdr__downconvert_batch_process_rows(csdr_downconvert_batch *b, const float *d_in, long long in_stride,
+                                         const int *d_in_rows, int n_per_channel, float *d_out, long long out_stride,
+                                         void *stream, const void *d_packets, int pkt_len, const csdr::DcBlank *blank);
+int csdr__downconvert_batch_set_wgs(csdr_downconvert_batch *b, long wgs);
+int csdr__downconvert_batch_copy_channel(csdr_downconvert_batch *dst, int dc, csdr_downconvert_batch *src, int sc);
+/* capi_fastfir.hip */
+int csdr__fastfir_batch_copy_row(csdr_fastfir_batch *dst, int dr, csdr_fastfir_batch *src, int sr);
+/* capi_frontend.hip */
+int csdr__noiseproc_batch_mask(csdr_noiseproc_batch *b, const float *d_in, long long in_stride, const void *d_packets,
+                               int npackets, int pkt_len, int n_per_channel, unsigned *d_mask, long long mask_stride,
+                               const void **d_state, const float **d_hist, void *stream);
+int csdr__noiseproc_batch_shape(csdr_noiseproc_batch *b, int *channels, int *device);
+int csdr__noiseproc_batch_process_packets(csdr_noiseproc_batch *b, const void *d_packets, int npackets, int pkt_len,
+                                          float *d_out, long long out_stride, void *stream);
+/* capi_demod_batch.hip */
+int csdr__demod_batch_wait_input_free(csdr_demod_batch *b, void *stream);
+}

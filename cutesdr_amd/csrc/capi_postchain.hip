@@ -1,6 +1,6 @@
 // capi_postchain.hip -- C ABI of the sample-rate leaf objects: CAgc, CSMeter, CFir, CIir and the
 // AM / SAM / FM / SSB demodulators (single-channel host forms), plus the shared PcUnit plumbing
-// used by the full CDemodulator chain (capi_demod.hip).
+// used by the full CDemodulator chain (chain_core.hpp).
 #include "capi_common.hpp"
 #include "pc_unit.hpp"
 

@@ -10,6 +10,7 @@
 // bench.py --gpus N keeps its one-process-per-GPU form (torch.distributed over RCCL): this object is for a host that
 // drives a whole node from one process, like the reference's single CSdrInterface.
 #include "capi_common.hpp"
+#include "capi_internal.hpp"
 #include <map>
 #include <vector>
 
@@ -260,7 +261,6 @@ int csdr_demod_shard_set_input_rows(csdr_demod_shard *S, const int *input_row, i
  * d_block[s] are single buffers: before refilling one, the shard's stream waits until the previous call's
  * down-converters have consumed it (csdr__demod_batch_wait_input_free) -- round-4 ADVICE: without that, pipelined call
  * k+1's copy could overwrite what call k was still reading. */
-extern "C" int csdr__demod_batch_wait_input_free(csdr_demod_batch *b, void *stream);
 int csdr_demod_shard_process_shared(csdr_demod_shard *S, const float *d_block, int src_device, void *src_stream,
                                     long long in_stride, int n_per_channel, float *const *d_out, long long out_stride)
 {

@@ -184,7 +184,7 @@ def test_the_retune_and_parameter_setters_hold_no_device_wide_synchronisation():
             if depth == 0:
                 return txt[j:k]
     clean = [("capi_downconv.hip", "int csdr_downconvert_batch_set_frequency("), ("capi_downconv.hip", "int csdr_downconvert_batch_set_cw_offset("),
-             ("capi_demod.hip", "int csdr_demod_batch_set_freq("), ("capi_demod.hip", "int csdr_demod_set_freq("),
+             ("capi_demod_batch.hip", "int csdr_demod_batch_set_freq("), ("capi_demod.hip", "int csdr_demod_set_freq("),
              ("pc_unit.hpp", "int agc_set("), ("pc_unit.hpp", "int smeter_rate_set("), ("pc_unit.hpp", "int fm_params_set("),
              ("pc_unit.hpp", "int am_bandwidth_set("), ("capi_fft.hip", "int csdr_fft_batch_get_ave("),
              ("capi_fft.hip", "int csdr_fft_batch_get_screen("), ("capi_fft.hip", "int csdr_fft_batch_get_total_count("),
@@ -194,7 +194,7 @@ def test_the_retune_and_parameter_setters_hold_no_device_wide_synchronisation():
     setup = body("capi_fastfir.hip", "int csdr_fastfir_batch_setup(")
     assert setup.count("hipDeviceSynchronize") == 1 and "switch to one filter per channel" in setup
     # the same-mode half of SetDemod: everything behind the `if (c.mode != mode)` block of apply_set_demod
-    asd = body("capi_demod.hip", "int apply_set_demod(")
+    asd = body("chain_core.hpp", "int apply_set_demod(")
     tail = asd[asd.index("c.cw_off = info.Offset;"):]
     assert "pull(" not in tail and "push(" not in tail and "hipDeviceSynchronize" not in tail
 

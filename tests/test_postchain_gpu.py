@@ -328,7 +328,7 @@ def test_demod_batch_mixed_modes(oracle, nfft):
 @pytest.mark.parametrize("pipeline", ["0", "1"])
 def test_batch_long_calls_fused_and_pipelined(oracle, pipeline, monkeypatch):
     """Long calls (>= 16 FastFIR hops) through the fused launch and through the optional stage
-    pipeline (S-meter | AGC | demodulator as concurrent launches over burst groups, capi_demod.hip
+    pipeline (S-meter | AGC | demodulator as concurrent launches over burst groups, chain_core.hpp
     ChainCore::post, CSDR_CHAIN_PIPELINE=1): same results as the oracle, every burst of both calls under
     the chain rule.  The switch is read once per process, so the
     pipelined case runs in a child interpreter."""
