@@ -48,7 +48,7 @@ struct csdr_fastfir_batch {
     std::vector<DesignJob> jobs;
     std::vector<int> job_of;          // slot -> index into jobs, or -1
     std::vector<char> stale;          // slot -> resp[slot] has to be fetched from d_resp
-    double *d_win = nullptr, *d_tw = nullptr;     // the host's window and twiddle tables (host_math.hpp), fp64
+    double *d_win = nullptr, *d_tw = nullptr;     // fastfir_window and design_twiddles (host_math.hpp), fp64
     int *d_perm = nullptr, *d_perm2 = nullptr;    // perm / perm2
     double *d_resp = nullptr;         // [channels][n] complex fp64, natural order; all five allocated by the first setup_many
     hipEvent_t ev_design = nullptr;   // behind the last design launch
@@ -123,13 +123,13 @@ static int design_state(csdr_fastfir_batch *b)
     if (b->d_resp) return CSDR_OK;
     const size_t n = (size_t)b->n, p = n / 2 + 1;
     const auto win = fastfir_window((int)p);
-    const auto tw = host_twiddles(n);
+    const auto tw = design_twiddles(n);
     if (!b->d_win) CSDR_HIP(hipMalloc((void **)&b->d_win, p * sizeof(double)));
     if (!b->d_tw) CSDR_HIP(hipMalloc((void **)&b->d_tw, n * sizeof(double)));
     if (!b->d_perm) CSDR_HIP(hipMalloc((void **)&b->d_perm, n * sizeof(int)));
     if (!b->d_perm2) CSDR_HIP(hipMalloc((void **)&b->d_perm2, n * sizeof(int)));
     CSDR_HIP(hipMemcpy(b->d_win, win->data(), p * sizeof(double), hipMemcpyHostToDevice));
-    CSDR_HIP(hipMemcpy(b->d_tw, tw->data(), n * sizeof(double), hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemcpy(b->d_tw, tw.data(), n * sizeof(double), hipMemcpyHostToDevice));
     CSDR_HIP(hipMemcpy(b->d_perm, b->perm.data(), n * sizeof(int), hipMemcpyHostToDevice));
     CSDR_HIP(hipMemcpy(b->d_perm2, b->perm2.data(), n * sizeof(int), hipMemcpyHostToDevice));
     CSDR_HIP(hipMalloc((void **)&b->d_resp, (size_t)b->channels * n * sizeof(cd)));

@@ -13,7 +13,7 @@ struct DesignJob {
 struct DesignArgs {
     const DesignJob *jobs;      // pinned, device mapped: one per workgroup
     const double *win;          // fastfir_window(N/2+1)
-    const double *tw;           // host_twiddles(N): [2j] = cos, [2j+1] = sin of 2 pi j / N, j < N/2
+    const double *tw;           // design_twiddles(N): [2j] = cos, [2j+1] = sin of 2 pi j / N, j < N/2, nearest doubles
     const int *perm, *perm2;    // device slot -> natural bin, generic / pipelined overlap-save kernel
     float *h, *h2;              // [filters][N] complex fp32 in those two orders
     double *resp;               // [filters][N] complex fp64, natural order (N = 16384: also the transform's work row)

@@ -4,7 +4,10 @@
 //   1. computes the N/2+1 taps -- windowed sinc times the pass-band shift, scaled by 1/N; the Blackman-Nuttall window
 //      comes from a table (the host's fastfir_window), so three transcendentals per tap are the device library's --
 //      and stores them zero padded in bit-reversed order,
-//   2. transforms them with host_fft's own network (radix-2 decimation in time, the host's twiddle table, sign +1),
+//   2. transforms them with host_fft's own network (radix-2 decimation in time, sign +1) and a twiddle table of nearest
+//      doubles (host_math.hpp: design_twiddles), every product and sum rounded on its own (no contraction into fused
+//      multiply-adds: the response is then the same words whatever the compiler, and a plain fp64 model of the network
+//      reproduces it),
 //   3. writes the fp32 response in the generic and in the pipelined overlap-save kernel's register order (permutation
 //      tables) and the fp64 response in natural order (the row get_response reads).
 // N = 2048 / 4096 / 8192: the transform lives in LDS as complex fp64 (32 / 64 / 128 KB); N = 16384 would need 256 KB, so
@@ -36,6 +39,7 @@ struct DesignCfg {
 template <int LOG2N>
 __global__ __launch_bounds__(DesignCfg<LOG2N>::T) void fastfir_design_kernel(DesignArgs a)
 {
+#pragma clang fp contract(off)
     using Cfg = DesignCfg<LOG2N>;
     constexpr int N = Cfg::N, T = Cfg::T, P = N / 2 + 1, CENTRE = N / 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char design_smem[];

@@ -34,6 +34,21 @@ inline std::shared_ptr<const std::vector<double>> host_twiddles(size_t n)
     cache[n] = t;
     return t;
 }
+// The same table with every entry the double NEAREST cos / sin(2 pi j / n): the angle is formed and the functions are
+// taken in long double, where host_twiddles rounds 2 pi j / n to a double first -- near pi that moves the angle by up to
+// 4e-16 rad and the entry with it (measured: 4.0e-16 at n = 2048), which is most of the 8e-16 * max|H| between a
+// response transformed with that table and the reference's (HISTORY.md).  For the device-side design only
+// (fastfir_design_kernels.hip): host_fft and the host design keep host_twiddles, and with it their words.
+inline std::vector<double> design_twiddles(size_t n)
+{
+    std::vector<double> t(n);
+    const long double two_pi = 2.0L * 3.14159265358979323846264338327950288L;
+    for (size_t j = 0; j < n / 2; j++) {
+        const long double ang = two_pi * (long double)j / (long double)n;
+        t[2 * j] = (double)cosl(ang); t[2 * j + 1] = (double)sinl(ang);
+    }
+    return t;
+}
 inline std::shared_ptr<const std::vector<double>> fastfir_window(int p)    // Blackman-Nuttall, dsp/fastfir.cpp:93-101
 {
     static std::mutex m;

@@ -6,15 +6,22 @@
  * cpu_baseline leg may load this library, and only as the checker / timed baseline.
  * Nothing under cutesdr_amd/ links, imports or calls it.
  *
- * PINNING STATUS (see DESIGN.md "Oracle"): the reference cannot be built in this image
- * (every dsp/ translation unit includes Qt headers -- <QMutex>, <QtGui/QApplication>,
- * <QDebug> -- and Qt is not installed; writing stand-ins for them is not allowed), and
- * the reference ships no tests, fixtures or golden vectors.  The
- * oracle is therefore pinned only by (i) the known-answer anchors that SURVEY.md
- * section 8c / App. A.9 recorded from a run of the reference, checked in
- * tests/test_oracle_anchors.py, and (ii) independent numpy/scipy restatements of the
- * published algorithms (DFT, windowed-sinc, Kaiser, RBJ biquad).  Where neither
- * reaches, parity is "unpinned" and says so in the test names.
+ * PINNING STATUS (see DESIGN.md "Oracle"): the reference's dsp/ code compiles unmodified
+ * against a few stand-in Qt headers (oracle/ref/, built by oracle/ref.py into oracle/_ref/,
+ * never committed), and this file is held to it: tests/test_oracle_vs_reference.py demands
+ * the same fp64 WORDS from both for every class without an FFT in it (down-converter,
+ * resampler, blanker, CFir / CIir, AGC, S-meter, the four demodulators), 1e-13 * max|x|
+ * behind the transforms (this file's radix-2 against the reference's Ooura radix-4) and
+ * 1e-9 of full scale on the whole CDemodulator, control calls in mid-stream included.
+ * tests/golden/reference_vectors.json keeps recorded outputs of the reference for where
+ * neither its tree nor its library is at hand.  Limits of that pinning: the reference's
+ * filter has 2048 points only, so the 4096 ... 16384-point forms of orc_fastfir stay tied
+ * to it through the `response` and word-equality tests; no sound sink, packet unpacking,
+ * spur calibration or plotter (they live outside dsp/); reference objects are constructed
+ * into zeroed storage, and one initial state differs on purpose (a down-converter before
+ * its first SetFrequency: HISTORY.md).  The older layers stay: the known-answer anchors of
+ * SURVEY.md section 8c / App. A.9 (tests/test_oracle_anchors.py) and the independent
+ * numpy / scipy restatements (tests/indep_ref.py).
  *
  * Every function cites the reference file:line it follows.
  */

@@ -54,8 +54,13 @@ D = C.c_double
 I = C.c_int
 
 
-def _declare(L):
+def _declare(L, prefix="orc_", optional=False):
+    """argument and result types of the orc_* surface; oracle/ref.py declares the reference library's ref_* entry points
+    with the same table (prefix="ref_", optional=True: the reference has no counterpart of some oracle-only calls)"""
     def f(name, res, *args):
+        name = prefix + name[4:]
+        if optional and not hasattr(L, name):
+            return
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = list(args)
@@ -166,11 +171,12 @@ def fft(x, sign=+1):
 class _Handle:
     _new = None
     _free = None
+    _lib = staticmethod(lib)        # oracle/ref.py's classes put the reference library here
 
     def __del__(self):
         h = getattr(self, "h", None)
         if h:
-            getattr(lib(), self._free)(h)
+            getattr(self._lib(), self._free)(h)
             self.h = None
 
 
@@ -185,24 +191,24 @@ class CFft(_Handle):
     _free = "orc_cfft_free"
 
     def __init__(self):
-        self.h = lib().orc_cfft_new()
+        self.h = self._lib().orc_cfft_new()
 
     def SetFFTParams(self, size, invert, db_comp, fs):
-        lib().orc_cfft_set_params(self.h, size, int(invert), db_comp, fs)
+        self._lib().orc_cfft_set_params(self.h, size, int(invert), db_comp, fs)
 
     def SetFFTAve(self, ave):
-        lib().orc_cfft_set_ave(self.h, ave)
+        self._lib().orc_cfft_set_ave(self.h, ave)
 
     def ResetFFT(self):
-        lib().orc_cfft_reset(self.h)
+        self._lib().orc_cfft_reset(self.h)
 
     def PutInDisplayFFT(self, x):
         a = _c128(x)
-        return lib().orc_cfft_put_display(self.h, len(a), _ptr(a))
+        return self._lib().orc_cfft_put_display(self.h, len(a), _ptr(a))
 
     def GetScreenIntegerFFTData(self, max_h, max_w, max_db, min_db, start_hz, stop_hz):
         out = np.zeros(max(max_w, 1) + 1, dtype=np.int32)     # the reference's loop writes OutBuf[MaxWidth] too
-        ov = lib().orc_cfft_get_screen(self.h, max_h, max_w, max_db, min_db, start_hz, stop_hz, _ptr(out))
+        ov = self._lib().orc_cfft_get_screen(self.h, max_h, max_w, max_db, min_db, start_hz, stop_hz, _ptr(out))
         return bool(ov), out[:max(max_w, 1)].copy()
 
     def WaterfallLine(self, max_w, max_db, min_db, start_hz, stop_hz, fill=0):
@@ -210,18 +216,18 @@ class CFft(_Handle):
         bin maps to come back as `fill`"""
         lv = np.full(max(max_w, 1) + 1, -1, dtype=np.int32)
         rgb = np.full(max(max_w, 1), fill, dtype=np.uint32)
-        ov = lib().orc_plotter_waterfall_line(self.h, max_w, max_db, min_db, start_hz, stop_hz, _ptr(lv), _ptr(rgb))
+        ov = self._lib().orc_plotter_waterfall_line(self.h, max_w, max_db, min_db, start_hz, stop_hz, _ptr(lv), _ptr(rgb))
         return bool(ov), rgb
 
     def FwdFFT(self, x):
-        a = _c128(x).copy(); lib().orc_cfft_fwd(self.h, _ptr(a)); return a
+        a = _c128(x).copy(); self._lib().orc_cfft_fwd(self.h, _ptr(a)); return a
 
     def RevFFT(self, x):
-        a = _c128(x).copy(); lib().orc_cfft_rev(self.h, _ptr(a)); return a
+        a = _c128(x).copy(); self._lib().orc_cfft_rev(self.h, _ptr(a)); return a
 
     def ave_buf(self):
-        n = lib().orc_cfft_size(self.h)
-        p = lib().orc_cfft_avebuf(self.h)
+        n = self._lib().orc_cfft_size(self.h)
+        p = self._lib().orc_cfft_avebuf(self.h)
         return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_double)), shape=(n,)).copy()
 
 
@@ -230,22 +236,22 @@ class CFastFIR(_Handle):
 
     def __init__(self, fft_size=2048):
         self.n = fft_size
-        self.h = lib().orc_fastfir_new(fft_size)
+        self.h = self._lib().orc_fastfir_new(fft_size)
 
     def set_faithful(self, on):
-        lib().orc_fastfir_set_faithful(self.h, int(on))
+        self._lib().orc_fastfir_set_faithful(self.h, int(on))
 
     def SetupParameters(self, flo, fhi, offset, fs):
-        return lib().orc_fastfir_setup(self.h, flo, fhi, offset, fs)
+        return self._lib().orc_fastfir_setup(self.h, flo, fhi, offset, fs)
 
     def ProcessData(self, x):
         a = _c128(x)
         out = np.zeros(len(a) + self.n, dtype=np.complex128)
-        k = lib().orc_fastfir_process(self.h, len(a), _ptr(a), _ptr(out))
+        k = self._lib().orc_fastfir_process(self.h, len(a), _ptr(a), _ptr(out))
         return out[:k]
 
     def coef(self):
-        p = lib().orc_fastfir_coef(self.h)
+        p = self._lib().orc_fastfir_coef(self.h)
         return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_double)), shape=(2 * self.n,)).copy().view(np.complex128)
 
 
@@ -253,63 +259,63 @@ class CDownConvert(_Handle):
     _free = "orc_downconv_free"
 
     def __init__(self):
-        self.h = lib().orc_downconv_new()
+        self.h = self._lib().orc_downconv_new()
 
     def SetCwOffset(self, off):
-        lib().orc_downconv_set_cw_offset(self.h, off)
+        self._lib().orc_downconv_set_cw_offset(self.h, off)
 
     def SetFrequency(self, f):
-        lib().orc_downconv_set_frequency(self.h, f)
+        self._lib().orc_downconv_set_frequency(self.h, f)
 
     def SetDataRate(self, in_rate, max_bw):
-        return lib().orc_downconv_set_data_rate(self.h, in_rate, max_bw)
+        return self._lib().orc_downconv_set_data_rate(self.h, in_rate, max_bw)
 
     def ProcessData(self, x):
         a = _c128(x).copy()
         out = np.zeros(len(a), dtype=np.complex128)
-        k = lib().orc_downconv_process(self.h, len(a), _ptr(a), _ptr(out))
+        k = self._lib().orc_downconv_process(self.h, len(a), _ptr(a), _ptr(out))
         return out[:k]
 
     def stages(self):
         codes = np.zeros(16, dtype=np.int32)
-        n = lib().orc_downconv_stages(self.h, _ptr(codes))
+        n = self._lib().orc_downconv_stages(self.h, _ptr(codes))
         return list(codes[:n])
 
     def nco_freq(self):
-        return lib().orc_downconv_nco_freq(self.h)
+        return self._lib().orc_downconv_nco_freq(self.h)
 
 
 class CFir(_Handle):
     _free = "orc_fir_free"
 
     def __init__(self):
-        self.h = lib().orc_fir_new()
+        self.h = self._lib().orc_fir_new()
 
     def InitConstFir(self, coef):
         c = np.ascontiguousarray(coef, dtype=np.float64)
-        lib().orc_fir_init_const(self.h, len(c), _ptr(c))
+        self._lib().orc_fir_init_const(self.h, len(c), _ptr(c))
 
     def InitLPFilter(self, scale, astop, fpass, fstop, fs):
-        return lib().orc_fir_init_lp(self.h, scale, astop, fpass, fstop, fs)
+        return self._lib().orc_fir_init_lp(self.h, scale, astop, fpass, fstop, fs)
 
     def InitHPFilter(self, scale, astop, fpass, fstop, fs):
-        return lib().orc_fir_init_hp(self.h, scale, astop, fpass, fstop, fs)
+        return self._lib().orc_fir_init_hp(self.h, scale, astop, fpass, fstop, fs)
 
     def GenerateHBFilter(self, off):
-        lib().orc_fir_gen_hilbert(self.h, off)
+        self._lib().orc_fir_gen_hilbert(self.h, off)
 
     def taps(self):
         c = np.zeros(75); i = np.zeros(75); q = np.zeros(75)
-        n = lib().orc_fir_taps(self.h, _ptr(c), _ptr(i), _ptr(q))
+        n = self._lib().orc_fir_taps(self.h, _ptr(c), _ptr(i), _ptr(q))
         return c[:n], i[:n], q[:n]
 
     def ProcessFilter(self, x):
         if np.iscomplexobj(x):
             a = _c128(x); out = np.zeros_like(a)
-            lib().orc_fir_process_cpx(self.h, len(a), _ptr(a), _ptr(out))
+            self._lib().orc_fir_process_cpx(self.h, len(a), _ptr(a), _ptr(out))
         else:
             a = np.ascontiguousarray(x, dtype=np.float64); out = np.zeros_like(a)
-            lib().orc_fir_process_real(self.h, len(a), _ptr(a), _ptr(out))
+            self._lib().orc_fir_process_real(self.h, len(a), _ptr(a), _ptr(out))
         return out
 
 
@@ -318,21 +324,21 @@ class CIir(_Handle):
     KIND = {"LP": 0, "HP": 1, "BP": 2, "BR": 3}
 
     def __init__(self):
-        self.h = lib().orc_iir_new()
+        self.h = self._lib().orc_iir_new()
 
     def Init(self, kind, f0, q, fs):
-        lib().orc_iir_init(self.h, self.KIND[kind], f0, q, fs)
+        self._lib().orc_iir_init(self.h, self.KIND[kind], f0, q, fs)
 
     def coefs(self):
-        c = np.zeros(5); lib().orc_iir_coefs(self.h, _ptr(c)); return c
+        c = np.zeros(5); self._lib().orc_iir_coefs(self.h, _ptr(c)); return c
 
     def ProcessFilter(self, x):
         if np.iscomplexobj(x):
             a = _c128(x); out = np.zeros_like(a)
-            lib().orc_iir_process_cpx(self.h, len(a), _ptr(a), _ptr(out))
+            self._lib().orc_iir_process_cpx(self.h, len(a), _ptr(a), _ptr(out))
         else:
             a = np.ascontiguousarray(x, dtype=np.float64); out = np.zeros_like(a)
-            lib().orc_iir_process_real(self.h, len(a), _ptr(a), _ptr(out))
+            self._lib().orc_iir_process_real(self.h, len(a), _ptr(a), _ptr(out))
         return out
 
 
@@ -340,18 +346,18 @@ class CAgc(_Handle):
     _free = "orc_agc_free"
 
     def __init__(self):
-        self.h = lib().orc_agc_new()
+        self.h = self._lib().orc_agc_new()
 
     def SetParameters(self, on, hang, thresh, manual, slope, decay, fs):
-        lib().orc_agc_set(self.h, int(on), int(hang), thresh, manual, slope, decay, fs)
+        self._lib().orc_agc_set(self.h, int(on), int(hang), thresh, manual, slope, decay, fs)
 
     def ProcessData(self, x):
         if np.iscomplexobj(x):
             a = _c128(x); out = np.zeros_like(a)
-            lib().orc_agc_process_cpx(self.h, len(a), _ptr(a), _ptr(out))
+            self._lib().orc_agc_process_cpx(self.h, len(a), _ptr(a), _ptr(out))
         else:
             a = np.ascontiguousarray(x, dtype=np.float64); out = np.zeros_like(a)
-            lib().orc_agc_process_real(self.h, len(a), _ptr(a), _ptr(out))
+            self._lib().orc_agc_process_real(self.h, len(a), _ptr(a), _ptr(out))
         return out
 
 
@@ -359,16 +365,16 @@ class CSMeter(_Handle):
     _free = "orc_smeter_free"
 
     def __init__(self):
-        self.h = lib().orc_smeter_new()
+        self.h = self._lib().orc_smeter_new()
 
     def ProcessData(self, x, fs):
-        a = _c128(x); lib().orc_smeter_process(self.h, len(a), _ptr(a), fs)
+        a = _c128(x); self._lib().orc_smeter_process(self.h, len(a), _ptr(a), fs)
 
     def GetPeak(self):
-        return lib().orc_smeter_peak(self.h)
+        return self._lib().orc_smeter_peak(self.h)
 
     def GetAve(self):
-        return lib().orc_smeter_ave(self.h)
+        return self._lib().orc_smeter_ave(self.h)
 
 
 class CNoiseProc(_Handle):
@@ -376,16 +382,16 @@ class CNoiseProc(_Handle):
     _free = "orc_noiseproc_free"
 
     def __init__(self):
-        self.h = lib().orc_noiseproc_new()
+        self.h = self._lib().orc_noiseproc_new()
 
     def SetupBlanker(self, On, Threshold, Width, SampleRate):
-        if lib().orc_noiseproc_setup(self.h, int(On), Threshold, Width, SampleRate) < 0:
+        if self._lib().orc_noiseproc_setup(self.h, int(On), Threshold, Width, SampleRate) < 0:
             raise ValueError("sample rate too high for the reference's 32768-entry average buffer")
 
     def ProcessBlanker(self, x):
         a = _c128(x)
         out = a.copy()                                   # off: the data passes untouched (in-place call)
-        lib().orc_noiseproc_process(self.h, len(a), _ptr(a), _ptr(out))
+        self._lib().orc_noiseproc_process(self.h, len(a), _ptr(a), _ptr(out))
         return out
 
 
@@ -412,17 +418,17 @@ class CAmDemod(_Handle):
     _free = "orc_amdemod_free"
 
     def __init__(self, fs):
-        self.h = lib().orc_amdemod_new(fs)
+        self.h = self._lib().orc_amdemod_new(fs)
 
     def SetBandwidth(self, bw):
-        lib().orc_amdemod_set_bandwidth(self.h, bw)
+        self._lib().orc_amdemod_set_bandwidth(self.h, bw)
 
     def ProcessData(self, x, stereo=False):
         a = _c128(x)
         if stereo:
-            out = np.zeros_like(a); lib().orc_amdemod_process_stereo(self.h, len(a), _ptr(a), _ptr(out))
+            out = np.zeros_like(a); self._lib().orc_amdemod_process_stereo(self.h, len(a), _ptr(a), _ptr(out))
         else:
-            out = np.zeros(len(a)); lib().orc_amdemod_process_mono(self.h, len(a), _ptr(a), _ptr(out))
+            out = np.zeros(len(a)); self._lib().orc_amdemod_process_mono(self.h, len(a), _ptr(a), _ptr(out))
         return out
 
 
@@ -430,14 +436,14 @@ class CSamDemod(_Handle):
     _free = "orc_samdemod_free"
 
     def __init__(self, fs):
-        self.h = lib().orc_samdemod_new(fs)
+        self.h = self._lib().orc_samdemod_new(fs)
 
     def ProcessData(self, x, stereo=False):
         a = _c128(x)
         if stereo:
-            out = np.zeros_like(a); lib().orc_samdemod_process_stereo(self.h, len(a), _ptr(a), _ptr(out))
+            out = np.zeros_like(a); self._lib().orc_samdemod_process_stereo(self.h, len(a), _ptr(a), _ptr(out))
         else:
-            out = np.zeros(len(a)); lib().orc_samdemod_process_mono(self.h, len(a), _ptr(a), _ptr(out))
+            out = np.zeros(len(a)); self._lib().orc_samdemod_process_mono(self.h, len(a), _ptr(a), _ptr(out))
         return out
 
 
@@ -445,20 +451,20 @@ class CFmDemod(_Handle):
     _free = "orc_fmdemod_free"
 
     def __init__(self, fs):
-        self.h = lib().orc_fmdemod_new(fs)
+        self.h = self._lib().orc_fmdemod_new(fs)
 
     def SetSquelch(self, v):
-        lib().orc_fmdemod_set_squelch(self.h, v)
+        self._lib().orc_fmdemod_set_squelch(self.h, v)
 
     def squelched(self):
-        return bool(lib().orc_fmdemod_squelched(self.h))
+        return bool(self._lib().orc_fmdemod_squelched(self.h))
 
     def ProcessData(self, x, fm_bw, stereo=False):
         a = _c128(x)
         if stereo:
-            out = np.zeros_like(a); lib().orc_fmdemod_process_stereo(self.h, len(a), fm_bw, _ptr(a), _ptr(out))
+            out = np.zeros_like(a); self._lib().orc_fmdemod_process_stereo(self.h, len(a), fm_bw, _ptr(a), _ptr(out))
         else:
-            out = np.zeros(len(a)); lib().orc_fmdemod_process_mono(self.h, len(a), fm_bw, _ptr(a), _ptr(out))
+            out = np.zeros(len(a)); self._lib().orc_fmdemod_process_mono(self.h, len(a), fm_bw, _ptr(a), _ptr(out))
         return out
 
 
@@ -475,10 +481,10 @@ class CFractResampler(_Handle):
     _free = "orc_resampler_free"
 
     def __init__(self):
-        self.h = lib().orc_resampler_new()
+        self.h = self._lib().orc_resampler_new()
 
     def Init(self, max_input):
-        lib().orc_resampler_init(self.h, max_input)
+        self._lib().orc_resampler_init(self.h, max_input)
 
     def Resample(self, x, rate, gain=None):
         cap = int(len(x) / rate) + 8
@@ -486,18 +492,18 @@ class CFractResampler(_Handle):
             a = _c128(x)
             if gain is None:
                 out = np.zeros(cap, dtype=np.complex128)
-                k = lib().orc_resampler_cpx(self.h, len(a), rate, _ptr(a), _ptr(out))
+                k = self._lib().orc_resampler_cpx(self.h, len(a), rate, _ptr(a), _ptr(out))
                 return out[:k]
             out = np.zeros(2 * cap, dtype=np.int16)
-            k = lib().orc_resampler_cpx_i16(self.h, len(a), rate, _ptr(a), _ptr(out), gain)
+            k = self._lib().orc_resampler_cpx_i16(self.h, len(a), rate, _ptr(a), _ptr(out), gain)
             return out[:2 * k].reshape(-1, 2)
         a = np.ascontiguousarray(x, dtype=np.float64)
         if gain is None:
             out = np.zeros(cap)
-            k = lib().orc_resampler_real(self.h, len(a), rate, _ptr(a), _ptr(out))
+            k = self._lib().orc_resampler_real(self.h, len(a), rate, _ptr(a), _ptr(out))
             return out[:k]
         out = np.zeros(cap, dtype=np.int16)
-        k = lib().orc_resampler_real_i16(self.h, len(a), rate, _ptr(a), _ptr(out), gain)
+        k = self._lib().orc_resampler_real_i16(self.h, len(a), rate, _ptr(a), _ptr(out), gain)
         return out[:k]
 
 
@@ -508,28 +514,28 @@ class CDemodulator(_Handle):
     _free = "orc_demod_free"
 
     def __init__(self, fastfir_n=2048):
-        self.h = lib().orc_demod_new(fastfir_n)
+        self.h = self._lib().orc_demod_new(fastfir_n)
 
     def SetInputSampleRate(self, r):
-        lib().orc_demod_set_input_rate(self.h, r)
+        self._lib().orc_demod_set_input_rate(self.h, r)
 
     def SetDemod(self, mode, info):
-        lib().orc_demod_set_demod(self.h, mode, C.byref(info))
+        self._lib().orc_demod_set_demod(self.h, mode, C.byref(info))
 
     def SetDemodFreq(self, f):
-        lib().orc_demod_set_freq(self.h, f)
+        self._lib().orc_demod_set_freq(self.h, f)
 
     def GetOutputRate(self):
-        return lib().orc_demod_output_rate(self.h)
+        return self._lib().orc_demod_output_rate(self.h)
 
     def GetSMeterPeak(self):
-        return lib().orc_demod_smeter_peak(self.h)
+        return self._lib().orc_demod_smeter_peak(self.h)
 
     def GetSMeterAve(self):
-        return lib().orc_demod_smeter_ave(self.h)
+        return self._lib().orc_demod_smeter_ave(self.h)
 
     def buf_limit(self):
-        return lib().orc_demod_buf_limit(self.h)
+        return self._lib().orc_demod_buf_limit(self.h)
 
     def ProcessData(self, x, stereo=False, out_cap=None):
         """Reference call semantics (every inner pass writes at out[0]; returns the sum)."""
@@ -537,33 +543,33 @@ class CDemodulator(_Handle):
         cap = out_cap or (len(a) + 65536)
         if stereo:
             out = np.zeros(cap, dtype=np.complex128)
-            k = lib().orc_demod_process_stereo(self.h, len(a), _ptr(a), _ptr(out))
+            k = self._lib().orc_demod_process_stereo(self.h, len(a), _ptr(a), _ptr(out))
         else:
             out = np.zeros(cap)
-            k = lib().orc_demod_process_mono(self.h, len(a), _ptr(a), _ptr(out))
+            k = self._lib().orc_demod_process_mono(self.h, len(a), _ptr(a), _ptr(out))
         return k, out
 
     def process_append(self, x):
         a = _c128(x)
         out = np.zeros(len(a) + 65536)
-        k = lib().orc_demod_process_mono_append(self.h, len(a), _ptr(a), _ptr(out))
+        k = self._lib().orc_demod_process_mono_append(self.h, len(a), _ptr(a), _ptr(out))
         return out[:k]
 
     def perturb_filter_output(self, mode, eps=0.0, seed=1):
         """test-of-the-tests hook (cutesdr_oracle.c): 0 off, 1 fp32 rounding, 2 fp32 +-1 ulp, 3 additive eps * max|z|"""
-        lib().orc_demod_perturb_filter_output(self.h, int(mode), float(eps), int(seed))
+        self._lib().orc_demod_perturb_filter_output(self.h, int(mode), float(eps), int(seed))
 
     def enable_taps(self, on=True):
-        lib().orc_demod_enable_taps(self.h, int(on))
+        self._lib().orc_demod_enable_taps(self.h, int(on))
 
     def clear_taps(self):
-        lib().orc_demod_clear_taps(self.h)
+        self._lib().orc_demod_clear_taps(self.h)
 
     def tap(self, k):
-        n = lib().orc_demod_tap_len(self.h, k)
+        n = self._lib().orc_demod_tap_len(self.h, k)
         if n == 0:
             return np.zeros(0, dtype=np.complex128 if k < 4 else np.float64)
-        p = lib().orc_demod_tap_data(self.h, k)
+        p = self._lib().orc_demod_tap_data(self.h, k)
         v = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_double)), shape=(n,)).copy()
         return v.view(np.complex128) if k < 4 else v
 
@@ -583,34 +589,34 @@ class CSoundOut(_Handle):
 
     def __init__(self, stereo=False):
         self.stereo = bool(stereo)
-        self.h = lib().orc_soundsink_new(int(stereo))
+        self.h = self._lib().orc_soundsink_new(int(stereo))
 
     def ChangeUserDataRate(self, rate):
-        lib().orc_soundsink_change_rate(self.h, rate)
+        self._lib().orc_soundsink_change_rate(self.h, rate)
 
     def SetVolume(self, vol):
-        lib().orc_soundsink_set_volume(self.h, vol)
+        self._lib().orc_soundsink_set_volume(self.h, vol)
 
     def SetBlocking(self, on):
-        lib().orc_soundsink_set_blocking(self.h, int(on))
+        self._lib().orc_soundsink_set_blocking(self.h, int(on))
 
     def PutOutQueue(self, x):
         a = _c128(x) if self.stereo else np.ascontiguousarray(x, dtype=np.float64)
-        return lib().orc_soundsink_put(self.h, len(a), _ptr(a))
+        return self._lib().orc_soundsink_put(self.h, len(a), _ptr(a))
 
     def GetOutQueue(self, n):
         out = np.zeros((n, 2) if self.stereo else n, dtype=np.int16)
-        lib().orc_soundsink_get(self.h, n, _ptr(out))
+        self._lib().orc_soundsink_get(self.h, n, _ptr(out))
         return out
 
     def rate_correction(self):
-        return lib().orc_soundsink_rate_correction(self.h)
+        return self._lib().orc_soundsink_rate_correction(self.h)
 
     def ave_level(self):
-        return lib().orc_soundsink_ave_level(self.h)
+        return self._lib().orc_soundsink_ave_level(self.h)
 
     def level(self):
-        return lib().orc_soundsink_level(self.h)
+        return self._lib().orc_soundsink_level(self.h)
 
     def ppm_error(self):
-        return lib().orc_soundsink_ppm(self.h)
+        return self._lib().orc_soundsink_ppm(self.h)

@@ -41,9 +41,13 @@ def test_no_cpu_fallback_without_gpu(built):
 
 
 def test_product_does_not_touch_oracle():
-    root = os.path.join(os.path.dirname(__file__), "..", "cutesdr_amd")
-    for dp, _, files in os.walk(root):
-        for f in files:
-            if f.endswith((".py", ".hip", ".hpp", ".h", ".cpp")):
-                txt = open(os.path.join(dp, f), errors="replace").read()
-                assert "oracle" not in txt.replace("no oracle", ""), os.path.join(dp, f)
+    """nothing under cutesdr_amd/ or include/ names a checker: neither the fp64 oracle nor the reference build
+    (oracle.ref, libcutesdr_ref); include/csdr_hb_taps.h may say that oracle/ uses it too"""
+    here = os.path.dirname(__file__)
+    for root in (os.path.join(here, "..", "cutesdr_amd"), os.path.join(here, "..", "include")):
+        for dp, _, files in os.walk(root):
+            for f in files:
+                if f.endswith((".py", ".hip", ".hpp", ".h", ".cpp")):
+                    txt = open(os.path.join(dp, f), errors="replace").read()
+                    assert "oracle" not in txt.replace("no oracle", "").replace("Used by oracle/ and by", ""), os.path.join(dp, f)
+                    assert "cutesdr_ref" not in txt and "_ref/" not in txt, os.path.join(dp, f)

@@ -97,3 +97,62 @@ def test_fastfir_16384_delay():
     assert len(y) == (len(x) // (n // 2)) * (n // 2)
     want = np.exp(2j * np.pi * i["pass_tone_hz"] * (t[:len(y)] - e["delay_samples"]) / fs)
     assert np.abs(y[n:] - want[n:]).max() < e["max_err"]
+
+
+# ---- tests/golden/reference_vectors.json: outputs of the reference's own compiled code, replayed on the HIP path ----
+def _reference_vectors():
+    import importlib.util
+    here = os.path.dirname(__file__)
+    spec = importlib.util.spec_from_file_location("make_reference_vectors", os.path.join(here, "golden", "make_reference_vectors.py"))
+    mod = importlib.util.module_from_spec(spec); spec.loader.exec_module(mod)
+    return mod, json.load(open(os.path.join(here, "golden", "reference_vectors.json")))
+
+
+RV, VECTORS = _reference_vectors()
+
+
+@pytest.mark.parametrize("name", sorted(VECTORS))
+def test_reference_vectors_on_the_hip_path(name):
+    """Every recorded case through the library's drop-in classes, each under the tolerance its stage has in the parity
+    tests (named per kind below); counts exact.  The words compared are the stored first and last 32; where one
+    tolerance holds for every word the three digests are held to n times it."""
+    import cutesdr_amd as ca
+    import dc_ref as D
+    import test_postchain_gpu as TP
+    FS = 32767.0
+    case = VECTORS[name]
+    e, kind = case["expect"], case["kind"]
+    v = RV.run_case(ca, case)
+    first = np.array([float.fromhex(h) for h in e["first"]]); last = np.array([float.fromhex(h) for h in e["last"]])
+    assert len(v) == e["n"]
+    gf, gl = v[:RV.WORDS], v[-RV.WORDS:]
+    x = RV.make_input(case)
+    if kind in ("ssb", "blanker"):                               # copies and zeros of fp32-representable input: exact
+        assert np.array_equal(gf, first) and np.array_equal(gl, last)
+        tol = 0.0
+    elif kind == "display":                                      # test_fft_resampler_gpu.assert_spectrum_close, word by word
+        for got, want in ((gf, first), (gl, last)):
+            lim = np.where(want > e["max"] - 6.0, 0.001, np.where(want > e["max"] - 9.0, 0.05, 0.2))
+            assert (np.abs(got - want) <= lim)[want > -15.0].all()
+        assert int(np.argmax(v)) == 2560 and abs(v.max() - e["max"]) <= 0.001
+        return
+    elif kind == "chain":                                        # test_postchain_gpu: the chain rule
+        mode = case["params"]["mode"]
+        if mode == "FM":
+            assert e["n"] >= 7 * 1024 and np.abs(gl - last).max() <= TP.FM_STEADY and np.abs(gf - first).max() <= 2.5 * FS
+        else:
+            assert e["n"] >= 3 * 1024 and np.abs(gf - first).max() <= TP.FROM_ZERO and np.abs(gl - last).max() <= TP.STEADY
+        return
+    else:
+        tol = {"downconvert": D.K * np.sqrt(2.0) * e["rms"],               # test_downconvert_plans_gpu.assert_parity
+               "fastfir": 2e-5 * np.abs(x).max(),                          # test_fastfir_gpu
+               "fft": 2e-5 * len(x) * np.abs(x).max() / np.sqrt(len(x)) * 4,   # test_fft_resampler_gpu.test_plain_transforms
+               "fir": 2e-3, "iir": 5e-3,                                   # test_postchain_gpu, the leaf filters
+               "agc": TP.STEADY, "am": TP.STEADY, "sam": TP.STEADY, "fm": TP.STEADY,
+               "smeter": 0.01, "resampler": 1e-5 * 8000 * 6}[kind]
+        skip = 2 if kind == "downconvert" else 0                            # assert_parity leaves out the first sample
+        assert np.abs(gf - first)[skip:].max() <= tol and np.abs(gl - last).max() <= tol, (np.abs(gf - first).max(), np.abs(gl - last).max(), tol)
+        if skip:
+            return
+    d = RV.digest(v)
+    assert all(abs(d[k] - e[k]) <= e["n"] * tol for k in ("sum", "abs", "dot")), (d, e, tol)

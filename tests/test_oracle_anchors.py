@@ -199,3 +199,75 @@ def test_oracle_has_not_drifted():
     for k in want:
         for f in want[k]:
             assert got[k][f] == pytest.approx(want[k][f], rel=1e-9, abs=1e-6), (k, f)
+
+
+# ---- tests/golden/reference_vectors.json: what the reference's own compiled code gave (make_reference_vectors.py) ----
+def _reference_vectors():
+    import importlib.util
+    here = os.path.dirname(__file__)
+    spec = importlib.util.spec_from_file_location("make_reference_vectors", os.path.join(here, "golden", "make_reference_vectors.py"))
+    mod = importlib.util.module_from_spec(spec); spec.loader.exec_module(mod)
+    return mod, json.load(open(os.path.join(here, "golden", "reference_vectors.json")))
+
+
+RV, VECTORS = _reference_vectors()
+BIT_EQUAL = ("downconvert", "fir", "iir", "agc", "smeter", "am", "sam", "fm", "ssb", "resampler", "blanker")
+FFT_EPS, CHAIN_EPS = 1e-13, 1e-9 * 32767.0       # tests/test_oracle_vs_reference.py derives both
+
+
+def _words(e):
+    return np.array([float.fromhex(h) for h in e["first"]]), np.array([float.fromhex(h) for h in e["last"]])
+
+
+def test_reference_vectors_file_is_in_step_with_its_recipes():
+    assert VECTORS.keys() == RV.CASES.keys()
+    for name, case in RV.CASES.items():
+        assert {k: v for k, v in VECTORS[name].items() if k != "expect"} == json.loads(json.dumps(case)), name
+    assert os.path.getsize(RV.OUT) < 64 * 1024
+
+
+@pytest.mark.parametrize("name", sorted(VECTORS))
+def test_reference_vectors_on_the_oracle(oracle, name):
+    """The stored reference outputs replayed on the fp64 oracle under the rules of tests/test_oracle_vs_reference.py:
+    classes without an FFT word for word (digests included), FFT stages within 1e-13 * max|x| (* N unscaled), the chain
+    within 1e-9 of full scale (FM: its last words, which lie behind the PLL's start-up).  Needs neither the reference
+    tree nor its library."""
+    case = VECTORS[name]
+    e, kind = case["expect"], case["kind"]
+    v = RV.run_case(oracle, case)
+    first, last = _words(e)
+    assert len(v) == e["n"]
+    d = RV.digest(v)
+    if kind in BIT_EQUAL:
+        assert np.array_equal(v[:RV.WORDS], first) and np.array_equal(v[-RV.WORDS:], last)
+        assert all(d[k] == e[k] for k in ("sum", "abs", "dot")), (d, e)
+        return
+    if kind == "display":
+        # in the linear domain, as in test_oracle_vs_reference.py::test_display_spectrum
+        n = case["params"]["n"]
+        kb = -2.0 * np.log10(n * oracle.constants()["fft.cpp:K_AMPMAX"] / 2.0)
+        err = FFT_EPS * n * 2.0 * np.abs(RV.make_input(case)).max()
+        for got, want in ((v[:RV.WORDS], first), (v[-RV.WORDS:], last)):
+            pg, pw = 10.0 ** (got - kb), 10.0 ** (want - kb)
+            assert (np.abs(pg - pw) <= 2.0 * np.sqrt(pw) * err + err * err + 1e-13 * pw).all()
+        assert int(np.argmax(v)) == 2560 and abs(v.max() - e["max"]) <= 1e-12
+        return
+    x = RV.make_input(case)
+    tol = {"fastfir": FFT_EPS * np.abs(x).max(), "fft": FFT_EPS * len(x) * np.abs(x).max(), "chain": CHAIN_EPS}[kind]
+    assert np.abs(v[-RV.WORDS:] - last).max() <= tol
+    if kind == "chain" and case["params"]["mode"] == "FM":
+        assert e["n"] >= 15 * 1024 and np.isfinite(v).all()
+        return
+    assert np.abs(v[:RV.WORDS] - first).max() <= tol
+    assert all(abs(d[k] - e[k]) <= e["n"] * tol for k in ("sum", "abs", "dot")), (d, e)
+
+
+def test_reference_vectors_are_what_the_reference_library_gives_now():
+    """where the library exists: a fresh run of the reference gives the stored words and digests, bit for bit"""
+    from oracle import ref
+    if not ref.tree_present() and ref.build() is None:
+        pytest.skip("neither oracle/_ref/libcutesdr_ref.so nor the reference tree is here")
+    assert ref.available()
+    for name, case in VECTORS.items():
+        got = RV.describe(RV.run_case(ref, case))
+        assert got == case["expect"], name
