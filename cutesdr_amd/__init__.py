@@ -10,3 +10,4 @@ from .host import *  # noqa: F401,F403
 from .host import SoundSinkBatch  # noqa: F401
 from .host import TestGenBatch  # noqa: F401
 
+from .host import ScopeBatch  # noqa: F401

@@ -7,6 +7,7 @@
 #include "pc_host.hpp"
 #include "display_plan.hpp"
 #include "testgen_host.hpp"
+#include "scope_host.hpp"
 #include "fastfir_kernels.h"
 #include <cstring>
 
@@ -158,5 +159,116 @@ int csdr__host_tg_run(void *h, int n, double fs, unsigned long long *phase, int 
     }
     return launches;
 }
+
+// the batch scope's host-side pieces (scope_host.hpp), the same functions the kernel evaluates.
+// The emissions of n samples from the state (inpos, pos) with pixel time pix at rate sr on a w-pixel screen:
+// samples[e] = index within the call of the sample that emits e (the first max_out of them), end3 = {emissions,
+// m_TimeScrnPos, m_TimeInPos} after the call; returns the emissions
+long long csdr__host_scope_emissions(long long inpos, int pos, double pix, double sr, int w, long long n, long long max_out,
+                                     long long *samples, long long *end3)
+{
+    const sc::Plan p = sc::make_plan(inpos, pos, pix, sr, w, n);
+    for (long long e = 0; e < p.emits && e < max_out; e++) samples[e] = p.sample(e);
+    end3[0] = p.emits; end3[1] = p.pos_end; end3[2] = p.inpos_end;
+    return p.emits;
+}
+// m_TimeScrnPixel and m_DisplaySkipValue of a span (ms), display rate and sample rate on a w-pixel screen
+void csdr__host_scope_settings(int span_ms, int display_rate, double sr, int w, double *pix, int *skip)
+{
+    *pix = sc::pixel_time(span_ms, w); *skip = sc::skip_value(span_ms, display_rate, sr);
+}
+// TRIG_OFF over m sweep starts: out3 = {displays, 1-based number of the last displaying start, counter afterwards}
+void csdr__host_scope_free_run(long long cnt, int skip, long long m, long long *out3)
+{
+    const sc::FreeRun r = sc::free_run(cnt, skip, m);
+    out3[0] = r.displays; out3[1] = r.last; out3[2] = r.cnt;
+}
+// One receiver of the batch scope on the CPU: the host's settings (sc::Chan, as capi_scope.hip keeps them) and the
+// put with the functions the kernel calls (make_plan, searches, crossing, decide, screen_source) in the kernel's order
+// of steps; the crossing search is a plain loop here.
+struct HostScope {
+    sc::Chan ch;
+    sc::ChanState st;
+    int w = 100, h = 100;
+    int ring[2 * sc::kMaxW], screen[2 * sc::kMaxW];
+};
+void *csdr__host_scope_create(void)
+{
+    HostScope *s = new HostScope();
+    memset(&s->st, 0, sizeof(s->st)); s->st.skipcounter = -2;
+    memset(s->ring, 0, sizeof(s->ring)); memset(s->screen, 0, sizeof(s->screen));
+    s->ch.derive(s->w);
+    return s;
+}
+void csdr__host_scope_destroy(void *h) { delete (HostScope *)h; }
+// what: 0 screen (v = w, v2 = h), 1 span, 2 display rate, 3 trigger mode, 4 level, 5 vertical range, 6 reset, 7 time_plot_done
+void csdr__host_scope_slot(void *h, int what, int v, int v2)
+{
+    HostScope &s = *(HostScope *)h;
+    switch (what) {
+    case 0: s.w = v; s.h = v2; s.ch.reset(v); break;
+    case 1: s.ch.on_horz_span(v, s.w); break;
+    case 2: s.ch.on_display_rate(v); break;
+    case 3: s.ch.on_trigger_mode(v, s.w); break;
+    case 4: s.ch.level = v; break;
+    case 5: s.ch.vert = v; break;
+    case 6: s.ch.reset(s.w); break;
+    default: s.ch.time_plot_done(); break;
+    }
+}
+// DisplayData of n samples (im NULL: the real form); returns the emits so far
+long long csdr__host_scope_put(void *h, const float *re, const float *im, int n, double fs)
+{
+    HostScope &s = *(HostScope *)h;
+    sc::ChanParam par;
+    s.ch.prepare(n, fs, s.w, par);
+    sc::ChanState &st = s.st;
+    int *ring = s.ring, *screen = s.screen;
+    const int w = s.w;
+    if (par.flags & sc::F_RESET) memset(ring, 0, sizeof(s.ring));
+    sc::apply_flags(st, par.flags);
+    if (par.n > 0) {
+        const sc::Plan pl = sc::make_plan(st.inpos, st.pos, par.pix, par.sr, w, par.n);
+        const long long E = pl.emits;
+        const int pos0 = st.pos;
+        auto get = [&](long long e, int &a, int &b) { const long long k = pl.sample(e); a = sc::sat_int(re[k]); b = im ? sc::sat_int(im[k]) : 0; };
+        long long trig = -1;
+        if (sc::searches(st, par))
+            for (long long e = 0; e < E && trig < 0; e++) {
+                int cur, prv, t;
+                get(e, cur, t);
+                if (e == 0) prv = st.prev; else get(e - 1, prv, t);
+                if (sc::crossing(par.mode, par.level, cur, prv)) trig = e;
+            }
+        const sc::Display d = sc::decide(st, par, w, E, trig);
+        if (d.at >= 0)
+            for (int i = 0; i < w; i++) {
+                int a, b, slot = 0;
+                const long long e = sc::screen_source(d, i, w, pos0, &slot);
+                if (e >= 0) get(e, a, b); else { a = ring[slot]; b = ring[sc::kMaxW + slot]; }
+                screen[i] = a; screen[sc::kMaxW + i] = b;
+            }
+        for (long long e = E > w ? E - w : 0; e < E; e++) {
+            int a, b;
+            get(e, a, b);
+            const int slot = (int)((pos0 + e) % w);
+            ring[slot] = a; ring[sc::kMaxW + slot] = b;
+        }
+        int t;
+        if (E > 0) get(E - 1, st.prev, t);
+        st.inpos = pl.inpos_end; st.pos = pl.pos_end;
+    }
+    return st.emits;
+}
+// state7 as the first seven of csdr_scope_batch_get_state; screen_re / screen_im [w]
+void csdr__host_scope_get(void *h, long long *state7, int *screen_re, int *screen_im)
+{
+    HostScope &s = *(HostScope *)h;
+    const sc::ChanState &st = s.st;
+    state7[0] = st.inpos; state7[1] = st.pos; state7[2] = st.prev; state7[3] = st.trigstate; state7[4] = st.trigcounter;
+    state7[5] = st.trigbufpos; state7[6] = st.skipcounter;
+    memcpy(screen_re, s.screen, sizeof(int) * s.w); memcpy(screen_im, s.screen + sc::kMaxW, sizeof(int) * s.w);
+}
+int csdr__host_scope_sat_int(double x) { return sc::sat_int(x); }
 
 }  // extern "C"

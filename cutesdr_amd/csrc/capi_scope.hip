@@ -1,0 +1,260 @@
+// capi_scope.hip -- C ABI of the batch test-bench scope: the time view of CTestBench::DisplayData with ChkForTrigger
+// (reference gui/testbench.cpp:583-695, :819-898; slots :247-299; Reset :541-548, :555-565, :574; DrawTimePlot
+// :973-999), one oscilloscope per receiver on the device.  The settings (sc::Chan) live on the host: a setter touches
+// no device memory and waits for nothing; what it changes, a Reset and the re-arm included, travels with the next put
+// in stream order.  Everything that depends on the data (positions, previous sample, trigger state and counters, skip
+// counter, ring, screen, emit counter) lives on the device.  put() writes the settings of the call into one slot of a
+// small ring of pinned buffers, copies the slot on the caller's stream and launches scope_kernels.hip behind it, as
+// capi_testgen.hip does; the readers wait for the event of the last put only, on a stream of the object's own.
+#include "capi_common.hpp"
+#include "scope_kernels.h"
+#include <cmath>
+#include <mutex>
+#include <vector>
+
+using namespace csdr;
+using sc::Chan;
+using sc::ChanParam;
+using sc::ChanState;
+
+namespace {
+constexpr int kRing = 16;
+constexpr int kMaxN = 1 << 24;
+}
+
+struct csdr_scope_batch {
+    int device = 0, channels = 0;
+    int w = 100, h = 100;                // m_Rect, :94
+    std::vector<Chan> ch;
+    std::mutex mu;                       // setters, put and the readers exclude each other
+    ChanParam *h_par[kRing] = {};        // pinned
+    ChanParam *d_par[kRing] = {};
+    hipEvent_t ev[kRing] = {};
+    bool busy[kRing] = {};
+    int next = 0, last = -1;             // last: the slot whose event marks the end of the latest launch
+    ChanState *d_state = nullptr;
+    int *d_ring = nullptr, *d_screen = nullptr;
+    hipStream_t rd = nullptr;            // the readers' stream
+};
+
+static int scb_alloc(csdr_scope_batch *s)
+{
+    const size_t bytes = sizeof(ChanParam) * (size_t)s->channels;
+    for (int i = 0; i < kRing; i++) {
+        if (hipHostMalloc((void **)&s->h_par[i], bytes, hipHostMallocDefault) != hipSuccess)
+            return fail(CSDR_ENOMEM, "hipHostMalloc(%zu) failed", bytes);
+        CSDR_HIP(hipMalloc((void **)&s->d_par[i], bytes));
+        CSDR_HIP(hipEventCreateWithFlags(&s->ev[i], hipEventDisableTiming));
+    }
+    const size_t words = (size_t)s->channels * 2 * sc::kMaxW;
+    CSDR_HIP(hipMalloc((void **)&s->d_state, sizeof(ChanState) * (size_t)s->channels));
+    CSDR_HIP(hipMalloc((void **)&s->d_ring, words * sizeof(int)));
+    CSDR_HIP(hipMalloc((void **)&s->d_screen, words * sizeof(int)));
+    CSDR_HIP(hipStreamCreateWithFlags(&s->rd, hipStreamNonBlocking));
+    std::vector<ChanState> st((size_t)s->channels);
+    for (auto &x : st) { memset(&x, 0, sizeof(x)); x.skipcounter = -2; }        // as after Reset(); m_TrigState WAIT, :117
+    CSDR_HIP(hipMemcpy(s->d_state, st.data(), sizeof(ChanState) * st.size(), hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemset(s->d_ring, 0, words * sizeof(int)));
+    CSDR_HIP(hipMemset(s->d_screen, 0, words * sizeof(int)));
+    return CSDR_OK;
+}
+
+template <class F> static int scb_each(csdr_scope_batch *s, int channel, F f)
+{
+    if (!s || channel >= s->channels) return fail(CSDR_EINVAL, "bad argument");
+    std::lock_guard<std::mutex> lock(s->mu);
+    for (int c = channel < 0 ? 0 : channel; c < (channel < 0 ? s->channels : channel + 1); c++) f(s->ch[c]);
+    return CSDR_OK;
+}
+
+// a free slot of the pinned ring: waits, on that launch's event only, when the launch kRing before has not finished
+static int scb_slot(csdr_scope_batch *s, int *slot)
+{
+    *slot = s->next;
+    if (s->busy[*slot]) { CSDR_HIP(hipEventSynchronize(s->ev[*slot])); s->busy[*slot] = false; }
+    return CSDR_OK;
+}
+static int scb_sent(csdr_scope_batch *s, int slot, hipStream_t st)
+{
+    CSDR_HIP(hipEventRecord(s->ev[slot], st));
+    s->busy[slot] = true;
+    s->last = slot;
+    s->next = (slot + 1) % kRing;
+    return CSDR_OK;
+}
+
+static int scb_put(csdr_scope_batch *s, const float *d_rows, long long stride, const int *n, const double *sample_rate,
+                   void *stream, int cpx)
+{
+    if (!have_device()) return CSDR_EHIP;
+    if (!s || !n || !sample_rate || stride < 0) return fail(CSDR_EINVAL, "bad argument");
+    std::lock_guard<std::mutex> lock(s->mu);
+    bool any = false;
+    for (int c = 0; c < s->channels; c++) {
+        if (n[c] < 0 || n[c] > kMaxN || n[c] > stride) return fail(CSDR_EINVAL, "n[%d] = %d: 0..2^24 and <= stride", c, n[c]);
+        if (n[c] == 0) continue;
+        const double fs = sample_rate[c];
+        if (!(fs > 0.0) || !std::isfinite(fs)) return fail(CSDR_EINVAL, "sample_rate[%d] must be positive", c);
+        if (!((double)s->ch[c].span * fs / 1000.0 <= sc::kMaxSweep))
+            return fail(CSDR_EINVAL, "receiver %d: a sweep of more than 2^30 samples", c);
+        any = true;
+    }
+    if (any && (!d_rows || ((uintptr_t)d_rows & (cpx ? 7u : 3u)) != 0)) return fail(CSDR_EINVAL, "rows missing or misaligned");
+    bool work = any;
+    for (int c = 0; c < s->channels; c++) work |= s->ch[c].flags != 0;
+    if (!work) return CSDR_OK;
+    CSDR_HIP(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    int slot;
+    if (int rc = scb_slot(s, &slot)) return rc;
+    ChanParam *hp = s->h_par[slot];
+    for (int c = 0; c < s->channels; c++)
+        s->ch[c].prepare(n[c], sample_rate[c], s->w, hp[c]);
+    if (s->last >= 0) CSDR_HIP(hipStreamWaitEvent(st, s->ev[s->last], 0));     // the state follows the previous put, whatever its stream
+    CSDR_HIP(hipMemcpyAsync(s->d_par[slot], hp, sizeof(ChanParam) * (size_t)s->channels, hipMemcpyHostToDevice, st));
+    ScopeArgs a;
+    a.rows = d_rows; a.stride = stride; a.par = s->d_par[slot]; a.state = s->d_state; a.ring = s->d_ring;
+    a.screen = s->d_screen; a.w = s->w; a.channels = s->channels;
+    CSDR_HIP(scope_put_launch(a, cpx, st));
+    return scb_sent(s, slot, st);
+}
+
+// device -> host behind the last put only
+static int scb_read(csdr_scope_batch *s, void *dst, const void *src, size_t bytes)
+{
+    CSDR_HIP(hipSetDevice(s->device));
+    if (s->last >= 0) CSDR_HIP(hipStreamWaitEvent(s->rd, s->ev[s->last], 0));
+    CSDR_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s->rd));
+    CSDR_HIP(hipStreamSynchronize(s->rd));
+    return CSDR_OK;
+}
+
+extern "C" {
+
+csdr_scope_batch *csdr_scope_batch_create(int device, int channels)
+{
+    if (channels < 1 || channels > 4096) { fail(CSDR_EINVAL, "channels 1..4096"); return nullptr; }
+    if (!device_ok(device)) return nullptr;
+    csdr_scope_batch *s = new csdr_scope_batch();
+    s->device = device; s->channels = channels;
+    s->ch.resize((size_t)channels);
+    for (auto &k : s->ch) k.derive(s->w);
+    if (scb_alloc(s) != CSDR_OK) {
+        const std::string e = last_error_ref();
+        csdr_scope_batch_destroy(s);
+        fail(CSDR_EHIP, "%s", e.c_str());
+        return nullptr;
+    }
+    return s;
+}
+void csdr_scope_batch_destroy(csdr_scope_batch *s)
+{
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    for (int i = 0; i < kRing; i++) {
+        if (s->busy[i]) (void)hipEventSynchronize(s->ev[i]);          // its launch still reads the slot
+        if (s->ev[i]) (void)hipEventDestroy(s->ev[i]);
+        if (s->h_par[i]) (void)hipHostFree(s->h_par[i]);
+        if (s->d_par[i]) (void)hipFree(s->d_par[i]);
+    }
+    if (s->rd) { (void)hipStreamSynchronize(s->rd); (void)hipStreamDestroy(s->rd); }
+    if (s->d_state) (void)hipFree(s->d_state);
+    if (s->d_ring) (void)hipFree(s->d_ring);
+    if (s->d_screen) (void)hipFree(s->d_screen);
+    delete s;
+}
+int csdr_scope_batch_set_screen(csdr_scope_batch *s, int w, int h)
+{
+    if (!s || w < 1 || w > sc::kMaxW || h < 2) return fail(CSDR_EINVAL, "screen: 1 <= w <= 2048, h >= 2");
+    std::lock_guard<std::mutex> lock(s->mu);
+    s->w = w; s->h = h;
+    for (auto &k : s->ch) k.reset(w);
+    return CSDR_OK;
+}
+int csdr_scope_batch_set_horz_span(csdr_scope_batch *s, int channel, int ms)
+{
+    if (ms < 1) return fail(CSDR_EINVAL, "span >= 1 ms");
+    return scb_each(s, channel, [=](Chan &k) { k.on_horz_span(ms, s->w); });
+}
+int csdr_scope_batch_set_display_rate(csdr_scope_batch *s, int channel, int rate)
+{
+    if (rate < 1) return fail(CSDR_EINVAL, "display rate >= 1");
+    return scb_each(s, channel, [=](Chan &k) { k.on_display_rate(rate); });
+}
+int csdr_scope_batch_set_trigger_mode(csdr_scope_batch *s, int channel, int mode)
+{
+    if (mode < sc::TRIG_OFF || mode > sc::TRIG_NSINGLE) return fail(CSDR_EINVAL, "trigger mode 0..4");
+    return scb_each(s, channel, [=](Chan &k) { k.on_trigger_mode(mode, s->w); });
+}
+int csdr_scope_batch_set_trig_level(csdr_scope_batch *s, int channel, int level)
+{ return scb_each(s, channel, [=](Chan &k) { k.level = level; }); }
+int csdr_scope_batch_set_vert_range(csdr_scope_batch *s, int channel, int range)
+{ return scb_each(s, channel, [=](Chan &k) { k.vert = range; }); }
+int csdr_scope_batch_reset(csdr_scope_batch *s, int channel)
+{ return scb_each(s, channel, [=](Chan &k) { k.reset(s->w); }); }
+int csdr_scope_batch_time_plot_done(csdr_scope_batch *s, int channel)
+{ return scb_each(s, channel, [](Chan &k) { k.time_plot_done(); }); }
+
+int csdr_scope_batch_put_real(csdr_scope_batch *s, const float *d_rows, long long stride, const int *n,
+                              const double *sample_rate, void *stream)
+{ return scb_put(s, d_rows, stride, n, sample_rate, stream, 0); }
+int csdr_scope_batch_put_cpx(csdr_scope_batch *s, const float *d_rows, long long stride, const int *n,
+                             const double *sample_rate, void *stream)
+{ return scb_put(s, d_rows, stride, n, sample_rate, stream, 1); }
+
+int csdr_scope_batch_get_emits(csdr_scope_batch *s, int *h_emits)
+{
+    if (!have_device()) return CSDR_EHIP;
+    if (!s || !h_emits) return fail(CSDR_EINVAL, "bad argument");
+    std::lock_guard<std::mutex> lock(s->mu);
+    std::vector<ChanState> st((size_t)s->channels);
+    if (int rc = scb_read(s, st.data(), s->d_state, sizeof(ChanState) * st.size())) return rc;
+    for (int c = 0; c < s->channels; c++) {
+        h_emits[c] = (int)(st[c].emits - s->ch[c].seen);
+        s->ch[c].seen = st[c].emits;
+    }
+    return CSDR_OK;
+}
+int csdr_scope_batch_get_state(csdr_scope_batch *s, int channel, long long *state8)
+{
+    if (!have_device()) return CSDR_EHIP;
+    if (!s || channel < 0 || channel >= s->channels || !state8) return fail(CSDR_EINVAL, "bad argument");
+    std::lock_guard<std::mutex> lock(s->mu);
+    ChanState st;
+    if (int rc = scb_read(s, &st, s->d_state + channel, sizeof(st))) return rc;
+    state8[0] = st.inpos; state8[1] = st.pos; state8[2] = st.prev; state8[3] = st.trigstate; state8[4] = st.trigcounter;
+    state8[5] = st.trigbufpos; state8[6] = st.skipcounter; state8[7] = st.emits;
+    return CSDR_OK;
+}
+int csdr_scope_batch_get_screen(csdr_scope_batch *s, int channel, int *re, int *im)
+{
+    if (!have_device()) return CSDR_EHIP;
+    if (!s || channel < 0 || channel >= s->channels || !re || !im) return fail(CSDR_EINVAL, "bad argument");
+    std::lock_guard<std::mutex> lock(s->mu);
+    const int *src = s->d_screen + (size_t)channel * 2 * sc::kMaxW;
+    if (int rc = scb_read(s, re, src, sizeof(int) * (size_t)s->w)) return rc;
+    return scb_read(s, im, src + sc::kMaxW, sizeof(int) * (size_t)s->w);
+}
+int csdr_scope_batch_get_screens_all(csdr_scope_batch *s, int *d_out, long long out_stride, int *d_y, long long vert_stride,
+                                     void *stream)
+{
+    if (!have_device()) return CSDR_EHIP;
+    if (!s || !d_out) return fail(CSDR_EINVAL, "bad argument");
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (out_stride < s->w || (d_y && vert_stride < s->w)) return fail(CSDR_EINVAL, "strides must be >= w = %d", s->w);
+    CSDR_HIP(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (s->last >= 0) CSDR_HIP(hipStreamWaitEvent(st, s->ev[s->last], 0));
+    ScopeScreenArgs a;
+    a.screen = s->d_screen; a.par = nullptr; a.out = d_out; a.out_stride = out_stride; a.y = d_y; a.y_stride = vert_stride;
+    a.w = s->w; a.h = s->h; a.channels = s->channels;
+    int slot;                                            // the vertical ranges travel as a put's settings do
+    if (int rc = scb_slot(s, &slot)) return rc;
+    for (int c = 0; c < s->channels; c++) { memset(&s->h_par[slot][c], 0, sizeof(ChanParam)); s->h_par[slot][c].vert = s->ch[c].vert; }
+    CSDR_HIP(hipMemcpyAsync(s->d_par[slot], s->h_par[slot], sizeof(ChanParam) * (size_t)s->channels, hipMemcpyHostToDevice, st));
+    a.par = s->d_par[slot];
+    CSDR_HIP(scope_screens_launch(a, st));
+    return scb_sent(s, slot, st);
+}
+
+}  // extern "C"

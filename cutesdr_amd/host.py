@@ -1288,3 +1288,95 @@ class TestGenBatch(_Obj):
         assert rows.dtype in (torch.complex64, torch.float32) and offset + length <= rows.shape[1]
         self.generate_ptr(rows.data_ptr() + offset * rows.element_size(), rows.stride(0), length, samplerate,
                           torch.cuda.current_stream(rows.device).cuda_stream, real=rows.dtype == torch.float32)
+
+
+class ScopeBatch(_Obj):
+    """C independent CTestBench oscilloscopes (gui/testbench.cpp:583-695, :819-898: the time view of DisplayData with
+    ChkForTrigger), one per receiver, reading the batch chain's fp32 rows on the device.  Setters as the reference's
+    slots; channel < 0: every receiver.  Trigger modes as the reference's: 0 off, 1 / 2 positive edge normal / single,
+    3 / 4 negative edge normal / single."""
+    _destroy = "csdr_scope_batch_destroy"
+    TRIG_OFF, TRIG_PNORM, TRIG_PSINGLE, TRIG_NNORM, TRIG_NSINGLE = range(5)
+
+    def __init__(self, channels, device=0):
+        self.channels, self.device = int(channels), device
+        self.w, self.height = 100, 100
+        self.h = check_ptr(lib().csdr_scope_batch_create(device, self.channels), "csdr_scope_batch_create")
+
+    def resizeEvent(self, w, h):
+        check(lib().csdr_scope_batch_set_screen(self.h, w, h), "csdr_scope_batch_set_screen")
+        self.w, self.height = int(w), int(h)
+
+    def OnHorzSpan(self, ms, channel=-1):
+        check(lib().csdr_scope_batch_set_horz_span(self.h, channel, ms), "csdr_scope_batch_set_horz_span")
+
+    def OnDisplayRate(self, rate, channel=-1):
+        check(lib().csdr_scope_batch_set_display_rate(self.h, channel, rate), "csdr_scope_batch_set_display_rate")
+
+    def OnTriggerMode(self, trigindex, channel=-1):
+        check(lib().csdr_scope_batch_set_trigger_mode(self.h, channel, trigindex), "csdr_scope_batch_set_trigger_mode")
+
+    def OnTrigLevel(self, level, channel=-1):
+        check(lib().csdr_scope_batch_set_trig_level(self.h, channel, level), "csdr_scope_batch_set_trig_level")
+
+    def OnVertRange(self, vrange, channel=-1):
+        check(lib().csdr_scope_batch_set_vert_range(self.h, channel, vrange), "csdr_scope_batch_set_vert_range")
+
+    def Reset(self, channel=-1):
+        check(lib().csdr_scope_batch_reset(self.h, channel), "csdr_scope_batch_reset")
+
+    def DrawTimePlot(self, channel=-1):
+        """the re-arm of DrawTimePlot (:995-999); applied in stream order by the next put"""
+        check(lib().csdr_scope_batch_time_plot_done(self.h, channel), "csdr_scope_batch_time_plot_done")
+
+    time_plot_done = DrawTimePlot
+
+    def put_ptr(self, d_rows, stride, n, samplerate, stream=None, cpx=False):
+        """d_rows: device [channels][stride] fp32 (complex fp32 when cpx); n, samplerate: one value or one per receiver"""
+        n = np.ascontiguousarray(np.broadcast_to(np.asarray(n, dtype=np.int32), (self.channels,)))
+        fs = np.ascontiguousarray(np.broadcast_to(np.asarray(samplerate, dtype=np.float64), (self.channels,)))
+        fn = lib().csdr_scope_batch_put_cpx if cpx else lib().csdr_scope_batch_put_real
+        check(fn(self.h, C.c_void_p(d_rows), stride, _vp(n), _vp(fs), C.c_void_p(stream) if stream else None),
+              "csdr_scope_batch_put")
+
+    def DisplayData(self, rows, length, samplerate, offset=0):
+        """rows: device tensor [channels, T], float32 or complex64; samples offset..offset+length[c]-1 of every row, on
+        the tensor's current stream"""
+        import torch
+        assert rows.is_cuda and rows.shape[0] == self.channels and rows.stride(1) == 1
+        assert rows.dtype in (torch.complex64, torch.float32)
+        assert offset + int(np.max(length)) <= rows.shape[1]
+        self.put_ptr(rows.data_ptr() + offset * rows.element_size(), rows.stride(0), length, samplerate,
+                     torch.cuda.current_stream(rows.device).cuda_stream, cpx=rows.dtype == torch.complex64)
+
+    put_real = put_cpx = DisplayData
+
+    def get_emits(self):
+        out = np.zeros(self.channels, dtype=np.int32)
+        check(lib().csdr_scope_batch_get_emits(self.h, _vp(out)), "csdr_scope_batch_get_emits")
+        return out
+
+    def get_screen(self, channel):
+        """(m_TimeScrnBuf1, m_TimeScrnBuf2) of one receiver, int32 [w] each"""
+        re, im = np.zeros(self.w, dtype=np.int32), np.zeros(self.w, dtype=np.int32)
+        check(lib().csdr_scope_batch_get_screen(self.h, channel, _vp(re), _vp(im)), "csdr_scope_batch_get_screen")
+        return re, im
+
+    def get_state(self, channel):
+        """m_TimeInPos, m_TimeScrnPos, m_PreviousSample, m_TrigState, m_TrigCounter, m_TrigBufPos, m_DisplaySkipCounter,
+        emits since creation"""
+        out = np.zeros(8, dtype=np.int64)
+        check(lib().csdr_scope_batch_get_state(self.h, channel, _vp(out)), "csdr_scope_batch_get_state")
+        return out
+
+    def get_screens_all(self, out, y=None):
+        """out (and y, DrawTimePlot's vertical mapping): int32 device tensors [channels, 2, >= w]; asynchronous on the
+        current stream"""
+        import torch
+        for t in (out,) + ((y,) if y is not None else ()):
+            assert t.is_cuda and t.dtype == torch.int32 and t.shape[0] >= self.channels and t.shape[1] == 2
+            assert t.stride(2) == 1 and t.stride(0) == 2 * t.stride(1)
+        check(lib().csdr_scope_batch_get_screens_all(
+            self.h, C.c_void_p(out.data_ptr()), out.stride(1), C.c_void_p(y.data_ptr()) if y is not None else None,
+            y.stride(1) if y is not None else 0, C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)),
+            "csdr_scope_batch_get_screens_all")

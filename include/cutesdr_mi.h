@@ -689,7 +689,7 @@ int csdr_ingest_spurcal_packets(int device, const void *d_packets, int channels,
  *
  * Deliberate deviations: a sample rate different from the last call's resets the receiver BEFORE the call's first
  * sample (the reference queues a Qt signal whose arrival time is undefined, :361-365); own generator instead of rand().
- * Out of scope: a drop-in CTestBench class (it is a QDialog), the DisplayData scope / FFT view, the USE_FILE playback
+ * Out of scope: a drop-in CTestBench class (it is a QDialog), DisplayData's FFT view (its time view is the scope below), the USE_FILE playback
  * kludge, a generator that emits datagrams, fusing the generator into the down-converter's loads, a shard form (a
  * shard host makes one generator per device, as for the batch sound sink).
  * -------------------------------------------------------------------------------------- */
@@ -718,6 +718,88 @@ int csdr_testgen_batch_set_seed(csdr_testgen_batch *t, unsigned long long seed);
 int csdr_testgen_batch_generate(csdr_testgen_batch *t, float *d_iq, long long stride, int n, double sample_rate, void *stream);
 /* the TYPEREAL overload (:454-517): 3 * amplitude * cos(phase), the noise's I term; fp32 mono rows, stride a multiple of 4 */
 int csdr_testgen_batch_generate_real(csdr_testgen_batch *t, float *d_out, long long stride, int n, double sample_rate,
+                                     void *stream);
+
+/* --------------------------------------------------------------------------------------
+ * Batch test-bench scope: the time view of CTestBench::DisplayData with ChkForTrigger (gui/testbench.cpp:583-695,
+ * :819-898), the oscilloscope that decides which stretch of a tapped stream is looked at, for every receiver of a
+ * batch at once and without the rows leaving the device.  Together with the generator above and the stage taps it is
+ * the third part of the reference's test bench.
+ *
+ * Per receiver, each input sample emits zero or more screen pixels: while (double)m_TimeInPos / samplerate >=
+ * (double)m_TimeScrnPos * m_TimeScrnPixel (:618-621).  An emission calls ChkForTrigger((int)re), writes (int)re and
+ * (int)im (0 in the real form) into the w-entry ring m_TimeBuf1/2 and advances the screen position; at w both
+ * positions go back to 0 (:623-632).  ChkForTrigger (:819-898) runs before the pixel is written and keeps
+ * m_PreviousSample on every emission: in the triggered modes it waits for the first crossing of the level, counts
+ * m_PostScrnCaptureLength = (7*w)/10 further emissions and then copies the ring, oldest entry first, into the screen
+ * m_TimeScrnBuf1/2 and emits NewTimeData: the trigger sample sits at screen index w - (7*w)/10.  TRIG_OFF decides at
+ * screen position 0 with the skip counter (:823-834) and copies the ring from slot (7*w)/10.  All of it is
+ * reproduced bit for bit; the output side is all integers.
+ *
+ * Settings, per receiver, defaults as the constructor's (:94, :111-117): screen 100 x 100 (one geometry for the
+ * object), display rate 10, horizontal span 100 ms, vertical range 65000, trigger level 100, trigger mode 0
+ * (0 TRIG_OFF, 1 TRIG_PNORM, 2 TRIG_PSINGLE, 3 TRIG_NNORM, 4 TRIG_NSINGLE), state WAIT, sample rate 1.  Each setter
+ * has exactly the state effect of its slot with the time display on; channel < 0: every receiver.  The settings live
+ * on the host: a setter waits for nothing, and what it changes -- a reset and the re-arm included -- is applied in
+ * stream order by the next put.  m_DisplaySkipValue is a qint32 (gui/testbench.h:174): the quotient is truncated
+ * when it is stored, here too.
+ *
+ * Deliberate deviations.  (1) A sample rate different from the last call's resets the receiver at once and drops the
+ * call's samples (:587-592 return without using them; the reference's reset arrives through a queued Qt signal at an
+ * undefined time).  As in the reference the first call of a receiver, whose rate differs from the constructor's 1,
+ * is such a call.  (2) After a display the trigger state is WAITDISPLAY until the GUI's DrawTimePlot puts it back to
+ * WAIT (:995-999); here that hand-back is the explicit call time_plot_done, so a receiver in a triggered mode displays
+ * at most once between two hand-backs and nothing depends on thread timing.  TRIG_OFF does not look at the state and
+ * may display several times in one call: the screen is the last one, get_emits counts all.  (3) (int) of a sample
+ * saturates at the ends of int32 and gives 0 for a NaN (undefined in the reference).  (4) The vertical mapping uses a
+ * 64-bit product (the reference's 2*c*v overflows 32 bits for large v), its result saturates to int32, and a
+ * vertical range of 0 gives y = h/2 (the reference divides by 0).
+ * Out of scope: the FFT view and its peak hold, the TYPEMONO16 / TYPESTEREO16 overloads (the mono one reads
+ * pBuf[i<<1], past its buffer), a drop-in CTestBench class (it is a QDialog), an automatic re-arm inside a call, a
+ * shard form (a shard host makes one scope per device, as for the batch sound sink), painting.
+ * -------------------------------------------------------------------------------------- */
+typedef struct csdr_scope_batch csdr_scope_batch;
+/* NULL without a HIP device (no CPU fallback); channels 1..4096 */
+csdr_scope_batch *csdr_scope_batch_create(int device, int channels);
+void csdr_scope_batch_destroy(csdr_scope_batch *s);
+/* resizeEvent (:920-932): 1 <= w <= 2048 (TB_MAX_SCREENSIZE), h >= 2; a Reset() of every receiver */
+int csdr_scope_batch_set_screen(csdr_scope_batch *s, int w, int h);
+int csdr_scope_batch_set_horz_span(csdr_scope_batch *s, int channel, int ms);          /* OnHorzSpan :270-280: pixel time and skip value, no reset; ms >= 1 */
+int csdr_scope_batch_set_display_rate(csdr_scope_batch *s, int channel, int rate);     /* OnDisplayRate :247-254; rate >= 1 */
+int csdr_scope_batch_set_trigger_mode(csdr_scope_batch *s, int channel, int mode);     /* OnTriggerMode :288-292: a Reset() */
+int csdr_scope_batch_set_trig_level(csdr_scope_batch *s, int channel, int level);      /* OnTrigLevel :294-299 */
+int csdr_scope_batch_set_vert_range(csdr_scope_batch *s, int channel, int range);      /* OnVertRange :261-268 */
+/* the time-view part of Reset() (:541-548, :555-565, :574): pixel time, positions and previous sample 0, state WAIT,
+ * ring cleared, skip value, skip counter -2; the screen keeps its contents */
+int csdr_scope_batch_reset(csdr_scope_batch *s, int channel);
+/* DisplayData(int, TYPEREAL*, double, int) (:643-695) of every receiver: d_rows = device [channels][stride] fp32, the
+ * rows csdr_demod_batch_process writes and the taps hand out; n[c] samples of row c (host array, 0 <= n[c] <= 2^24 and
+ * <= stride; 0: the receiver is left exactly as it is), sample_rate[c] > 0 (host array).  Only enqueues on `stream`
+ * and waits for nothing (the settings of a call travel in a ring of 16 pinned buffers; a call waits, on that launch's
+ * event only, when the launch 16 before it has not finished); the rows are never written; where a sweep is longer
+ * than the screen only the emitted samples are read.  One launch per call.  A sweep (span * sample rate) of more than
+ * 2^30 samples is CSDR_EINVAL (m_TimeInPos is an int), before any state changes. */
+int csdr_scope_batch_put_real(csdr_scope_batch *s, const float *d_rows, long long stride, const int *n,
+                              const double *sample_rate, void *stream);
+/* the TYPECPX overload (:583-636): rows of complex fp32, stride in complex samples; the trigger looks at re */
+int csdr_scope_batch_put_cpx(csdr_scope_batch *s, const float *d_rows, long long stride, const int *n,
+                             const double *sample_rate, void *stream);
+/* DrawTimePlot's re-arm (:995-999): the state goes back to WAIT unless the mode is one of the two single ones;
+ * applied in stream order by the next put */
+int csdr_scope_batch_time_plot_done(csdr_scope_batch *s, int channel);
+/* NewTimeData emits of every receiver since the last get_emits into h_emits[channels]; waits for the last put only
+ * (its event, on a stream of the object's own) */
+int csdr_scope_batch_get_emits(csdr_scope_batch *s, int *h_emits);
+/* host copy of m_TimeScrnBuf1/2, w entries each; waits as get_emits does */
+int csdr_scope_batch_get_screen(csdr_scope_batch *s, int channel, int *re, int *im);
+/* the data-dependent state of one receiver: m_TimeInPos, m_TimeScrnPos, m_PreviousSample, m_TrigState, m_TrigCounter,
+ * m_TrigBufPos, m_DisplaySkipCounter, emits since creation (modulo 2^32); waits as get_emits does */
+int csdr_scope_batch_get_state(csdr_scope_batch *s, int channel, long long *state8);
+/* every receiver's last screen into d_out = device [channels][2][out_stride] int32 (re, im; the first w entries of a
+ * row, the rest untouched) and, when d_y is not NULL, DrawTimePlot's vertical mapping of both halves (:973-988), y =
+ * h/2 - (2*(h/2)*v) / m_VertRange with C's truncating division, into d_y = device [channels][2][vert_stride] int32.
+ * Asynchronous on `stream`, behind the puts before it. */
+int csdr_scope_batch_get_screens_all(csdr_scope_batch *s, int *d_out, long long out_stride, int *d_y, long long vert_stride,
                                      void *stream);
 
 #ifdef __cplusplus
