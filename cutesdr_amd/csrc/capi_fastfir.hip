@@ -28,6 +28,11 @@ struct csdr_fastfir_batch {
     float *d_h;                       // [filters][n] complex fp32 in pass-F3 register order of the generic kernel
     float *d_h2;                      // N = 16384: the same responses in the pipelined kernel's order (it consumes H as
                                       // its tail groups finish bins); both are kept, a launch may go to either kernel
+    float *d_gain;                    // [filters][n] fp32: the real gains of the same responses, Re(H[k] (-j)^k), in the
+                                      // pipelined kernel's order (host_math.hpp: fastfir_gain) -- what its 16384-point
+                                      // instantiation multiplies by while own_design holds
+    bool own_design;                  // every response came from fastfir_design / the design kernel (linear phase): always
+                                      // true today, a setter of raw responses would clear it and with it the real-gain kernel
     float *d_hist;                    // 2 x [channels][n/2] complex fp32 (ping-pong)
     int hist_cur;                     // which half holds the previous call's tail
     int dbg_stage; float *dbg_out;    // diagnostics only (csdr__dbg_fastfir_stage)
@@ -36,6 +41,7 @@ struct csdr_fastfir_batch {
     double flo, fhi, off, fs;         // last shared-filter parameters (early-out like the reference)
     std::vector<std::vector<cd>> resp;   // natural-order fp64 response per filter
     std::vector<int> perm, perm2;     // device slot -> natural bin, generic / pipelined kernel
+    std::vector<int> permg;           // gain slot -> natural bin
     // A new frequency response does not stop anything: SetupParameters designs it on the host and queues the fp32 words
     // of both kernel orders as patches; the NEXT process call applies them on its own stream in front of its launch
     // (patch_queue.hpp) -- in stream order behind every earlier call's reads of H, so one buffer per filter suffices.
@@ -49,7 +55,7 @@ struct csdr_fastfir_batch {
     std::vector<int> job_of;          // slot -> index into jobs, or -1
     std::vector<char> stale;          // slot -> resp[slot] has to be fetched from d_resp
     double *d_win = nullptr, *d_tw = nullptr;     // fastfir_window and design_twiddles (host_math.hpp), fp64
-    int *d_perm = nullptr, *d_perm2 = nullptr;    // perm / perm2
+    int *d_perm = nullptr, *d_perm2 = nullptr, *d_permg = nullptr;    // perm / perm2 / permg
     double *d_resp = nullptr;         // [channels][n] complex fp64, natural order; all five allocated by the first setup_many
     hipEvent_t ev_design = nullptr;   // behind the last design launch
 };
@@ -85,7 +91,7 @@ static int flush_control(csdr_fastfir_batch *b, hipStream_t s)
     if (!rc) {
         DesignArgs a;
         a.jobs = (const DesignJob *)d; a.win = b->d_win; a.tw = b->d_tw; a.perm = b->d_perm; a.perm2 = b->d_perm2;
-        a.h = b->d_h; a.h2 = b->d_h2; a.resp = b->d_resp;
+        a.h = b->d_h; a.h2 = b->d_h2; a.resp = b->d_resp; a.permg = b->d_permg; a.gain = b->d_gain;
         e = fastfir_design_launch(b->log2n, a, (int)b->jobs.size(), s);
         if (e == hipSuccess) {
             for (const DesignJob &j : b->jobs) b->job_of[j.slot] = -1;
@@ -128,10 +134,12 @@ static int design_state(csdr_fastfir_batch *b)
     if (!b->d_tw) CSDR_HIP(hipMalloc((void **)&b->d_tw, n * sizeof(double)));
     if (!b->d_perm) CSDR_HIP(hipMalloc((void **)&b->d_perm, n * sizeof(int)));
     if (!b->d_perm2) CSDR_HIP(hipMalloc((void **)&b->d_perm2, n * sizeof(int)));
+    if (!b->d_permg) CSDR_HIP(hipMalloc((void **)&b->d_permg, n * sizeof(int)));
     CSDR_HIP(hipMemcpy(b->d_win, win->data(), p * sizeof(double), hipMemcpyHostToDevice));
     CSDR_HIP(hipMemcpy(b->d_tw, tw.data(), n * sizeof(double), hipMemcpyHostToDevice));
     CSDR_HIP(hipMemcpy(b->d_perm, b->perm.data(), n * sizeof(int), hipMemcpyHostToDevice));
     CSDR_HIP(hipMemcpy(b->d_perm2, b->perm2.data(), n * sizeof(int), hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemcpy(b->d_permg, b->permg.data(), n * sizeof(int), hipMemcpyHostToDevice));
     CSDR_HIP(hipMalloc((void **)&b->d_resp, (size_t)b->channels * n * sizeof(cd)));
     return CSDR_OK;
 }
@@ -152,6 +160,10 @@ static void build_perm(csdr_fastfir_batch *b)
             for (int t = 0; t < T; t++)
                 for (int e = 0; e < 2; e++) b->perm2[(j * T + t) * 2 + e] = fastfir2_bin_of(b->log2n, t, j, e);
     }
+    b->permg.resize(b->n);
+    for (int i = 0; i < 8; i++)
+        for (int t = 0; t < T; t++)
+            for (int c = 0; c < 4; c++) b->permg[(i * T + t) * 4 + c] = fastfir2_gain_bin_of(b->log2n, t, i, c);
 }
 
 static int upload_response(csdr_fastfir_batch *b, int slot, const std::vector<cd> &H)
@@ -169,7 +181,8 @@ static int upload_response(csdr_fastfir_batch *b, int slot, const std::vector<cd
         const int rc = b->patches.add(dst + (size_t)slot * 2 * b->n, dev.data(), dev.size() * sizeof(float));
         if (rc) return rc;
     }
-    return CSDR_OK;
+    for (int i = 0; i < b->n; i++) dev[i] = (float)fastfir_gain(H[b->permg[i]], b->permg[i]);
+    return b->patches.add(b->d_gain + (size_t)slot * b->n, dev.data(), (size_t)b->n * sizeof(float));
 }
 
 // a response designed on the HOST becomes slot `slot`'s: its words queued as patches, the mirror current, a design job
@@ -209,7 +222,8 @@ csdr_fastfir_batch *csdr_fastfir_batch_create(int device, int channels, int fft_
         const char *v = getenv("CSDR_FASTFIR_VARIANT");
         b->variant = (v && atoi(v) == 0) ? 0 : 2;
     }
-    b->d_h = b->d_h2 = b->d_hist = b->d_tw1 = b->d_tw2 = nullptr;
+    b->d_h = b->d_h2 = b->d_gain = b->d_hist = b->d_tw1 = b->d_tw2 = nullptr;
+    b->own_design = true;
     b->flo = -1.0; b->fhi = 1.0; b->off = 1.0; b->fs = 1.0;      // fastfir.cpp:126-129
     build_perm(b);
     const size_t hbytes = (size_t)fft_size * 8, histbytes = 2 * (size_t)channels * (fft_size / 2) * 8;
@@ -225,6 +239,7 @@ csdr_fastfir_batch *csdr_fastfir_batch_create(int device, int channels, int fft_
         }
     bool ok = hipMalloc((void **)&b->d_h, hbytes) == hipSuccess &&
               hipMalloc((void **)&b->d_h2, hbytes) == hipSuccess && hipMemset(b->d_h2, 0, hbytes) == hipSuccess &&
+              hipMalloc((void **)&b->d_gain, hbytes / 2) == hipSuccess && hipMemset(b->d_gain, 0, hbytes / 2) == hipSuccess &&
               hipMalloc((void **)&b->d_hist, histbytes) == hipSuccess &&
               hipMalloc((void **)&b->d_tw1, 8192) == hipSuccess &&
               hipMalloc((void **)&b->d_tw2, 8192) == hipSuccess &&
@@ -249,6 +264,7 @@ void csdr_fastfir_batch_destroy(csdr_fastfir_batch *b)
     (void)hipSetDevice(b->device);
     if (b->d_h) (void)hipFree(b->d_h);
     if (b->d_h2) (void)hipFree(b->d_h2);
+    if (b->d_gain) (void)hipFree(b->d_gain);
     if (b->d_hist) (void)hipFree(b->d_hist);
     if (b->d_tw1) (void)hipFree(b->d_tw1);
     if (b->d_tw2) (void)hipFree(b->d_tw2);
@@ -257,6 +273,7 @@ void csdr_fastfir_batch_destroy(csdr_fastfir_batch *b)
     if (b->d_tw) (void)hipFree(b->d_tw);
     if (b->d_perm) (void)hipFree(b->d_perm);
     if (b->d_perm2) (void)hipFree(b->d_perm2);
+    if (b->d_permg) (void)hipFree(b->d_permg);
     if (b->d_resp) (void)hipFree(b->d_resp);
     delete b;
 }
@@ -295,6 +312,14 @@ int csdr_fastfir_batch_setup(csdr_fastfir_batch *b, int channel, double flo, dou
                 CSDR_HIP(hipMemcpy((char *)nh2 + one * c, b->d_h2, one, hipMemcpyDeviceToDevice));
             CSDR_HIP(hipFree(b->d_h2));
             b->d_h2 = nh2;
+        }
+        {
+            float *ng = nullptr;
+            CSDR_HIP(hipMalloc((void **)&ng, one / 2 * b->channels));
+            for (int c = 0; c < b->channels; c++)
+                CSDR_HIP(hipMemcpy((char *)ng + one / 2 * c, b->d_gain, one / 2, hipMemcpyDeviceToDevice));
+            CSDR_HIP(hipFree(b->d_gain));
+            b->d_gain = ng;
         }
         b->resp.resize(b->channels, b->resp[0]);
         b->per_channel = true;
@@ -394,6 +419,7 @@ int csdr_fastfir_batch_process(csdr_fastfir_batch *b, const float *d_in, long lo
     a.hist = (const v2f_h *)(b->d_hist + b->hist_cur * hist_half);
     a.hist_next = (v2f_h *)(b->d_hist + (b->hist_cur ^ 1) * hist_half);
     a.h = (const v4f_h *)b->d_h; a.tw1 = (const v2f_h *)b->d_tw1; a.tw2 = (const v2f_h *)b->d_tw2;
+    a.gain = nullptr;
     a.in_stride = in_stride; a.out_stride = out_stride;
     a.h_stride = b->per_channel ? b->n / 2 : 0;
     a.channels = b->channels;
@@ -421,6 +447,8 @@ int csdr_fastfir_batch_process(csdr_fastfir_batch *b, const float *d_in, long lo
     a.dbg_stage = b->dbg_stage; a.dbg = (v2f_h *)b->dbg_out;
     if (b->variant >= 2) {
         a.h = (const v4f_h *)b->d_h2;         // its own H order
+        // N = 16384 on the library's own (linear-phase) designs: real gains and a quarter-block shift instead of complex H
+        if (b->log2n == 14 && b->own_design) a.gain = (const v4f_h *)b->d_gain;
         CSDR_HIP(fastfir2_launch(b->log2n, a, s));     // any block count (pairs, then a single trailing block)
     }
     else CSDR_HIP(fastfir_launch(b->log2n, a, s));
@@ -448,6 +476,7 @@ int csdr__fastfir_batch_copy_row(csdr_fastfir_batch *dst, int dr, csdr_fastfir_b
     const int slot = dst->per_channel ? dr : 0;
     int rc = set_response(dst, slot, H);
     if (rc) return rc;
+    dst->own_design = dst->own_design && src->own_design;      // (the gains set_response derived hold for a design only)
     dst->flo = dst->fhi = dst->off = dst->fs = std::nan("");      // parameters unknown: the next setup always designs
     return CSDR_OK;
 }

@@ -9,9 +9,31 @@
 #include "testgen_host.hpp"
 #include "scope_host.hpp"
 #include "fastfir_kernels.h"
+#include "fft_core.hpp"
 #include <cstring>
 
 using namespace csdr;
+
+// host builds of fft_core.hpp's real-gain butterflies (the plain C++ forms of the same templates the kernel uses).
+// x4 / g4: four complex points in network order and their four real gains; out4 = dit_head4_gain of them
+template <int SIGN> static void host_head4_gain(const float *x4, const float *g4, float *out4)
+{
+    v2f x[4];
+    for (int q = 0; q < 4; q++) x[q] = v2f{x4[2 * q], x4[2 * q + 1]};
+    dit_head4_gain<0, 4, SIGN>(x, v2f{g4[0], g4[1]}, v2f{g4[2], g4[3]});
+    for (int q = 0; q < 4; q++) { out4[2 * q] = x[q].x; out4[2 * q + 1] = x[q].y; }
+}
+// in: R complex points in NATURAL order; out: rows R/4 ... 3R/4 - 1 of their unnormalised DFT of sign `sign`, computed as
+// the overlap-save kernel's pass I3 does: head groups, (R = 32: the middle stage,) dit_tail_middle
+template <int R, int SIGN> static void host_dft_middle(const float *in, float *out)
+{
+    v2f x[R];
+    for (int n = 0; n < R; n++) x[bitrev<R>(n)] = v2f{in[2 * n], in[2 * n + 1]};
+    static_for<0, R / 4>([&](auto G) { dit_head4<G.value, R, SIGN>(x); });
+    if constexpr (R == 32) dit_single<8, 32, SIGN>(x);
+    static_for<0, R / 4>([&](auto I) { dit_tail_middle<I.value, R, SIGN>(x); });
+    for (int r = 0; r < R / 2; r++) { out[2 * r] = x[R / 4 + r].x; out[2 * r + 1] = x[R / 4 + r].y; }
+}
 
 extern "C" {
 
@@ -28,6 +50,31 @@ int csdr__host_design_job(double flo, double fhi, double off, double fs, double 
     return fastfir_design_job(flo, fhi, off, fs, *nfc, *nfs) ? 0 : -1;
 }
 int csdr__host_fastfir_bin_of(int log2n, int t, int r) { return fastfir_bin_of(log2n, t, r); }
+// the real gains of a design in natural order, P[k] = fastfir_gain(H[k], k), and the design itself
+int csdr__host_fastfir_gains(int n, double flo, double fhi, double off, double fs, double *h_out, double *p_out)
+{
+    std::vector<cd> H;
+    if (!fastfir_design(n, flo, fhi, off, fs, H)) return -1;
+    memcpy(h_out, H.data(), sizeof(cd) * n);
+    for (int k = 0; k < n; k++) p_out[k] = fastfir_gain(H[k], k);
+    return 0;
+}
+int csdr__host_fastfir2_bin_of(int log2n, int t, int j, int e) { return fastfir2_bin_of(log2n, t, j, e); }
+int csdr__host_fastfir2_gain_bin_of(int log2n, int t, int i, int c) { return fastfir2_gain_bin_of(log2n, t, i, c); }
+
+void csdr__host_dit_head4_gain(int sign, const float *x4, const float *g4, float *out4)
+{
+    if (sign > 0) host_head4_gain<+1>(x4, g4, out4); else host_head4_gain<-1>(x4, g4, out4);
+}
+int csdr__host_dft_middle(int r, int sign, const float *in, float *out)
+{
+    if (r == 16 && sign > 0) host_dft_middle<16, +1>(in, out);
+    else if (r == 16) host_dft_middle<16, -1>(in, out);
+    else if (r == 32 && sign > 0) host_dft_middle<32, +1>(in, out);
+    else if (r == 32) host_dft_middle<32, -1>(in, out);
+    else return -1;
+    return 0;
+}
 
 int csdr__host_dc_plan(double in_rate, double bw, int *codes, double *out_rate, int *warmup)
 {

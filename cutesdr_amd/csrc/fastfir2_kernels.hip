@@ -42,6 +42,12 @@ namespace csdr {
 #ifndef K1_HREG
 #define K1_HREG 8           // float4 of this thread's share of H that stay in registers for the whole run (0..8 fit)
 #endif
+#ifndef K1_REALGAIN
+#define K1_REALGAIN 1       // 0: the 16384-point kernel on complex H whatever the responses are (A/B against the parent form)
+#endif
+#ifndef K1_TWREG
+#define K1_TWREG 0          // real-gain kernel: pass twiddles of F2 / I2 that stay in registers (0 ... 3 fit; HISTORY.md)
+#endif
 #ifndef K1_HREG4K
 #define K1_HREG4K 4         // ... at N = 4096, whose outer pass (eight columns of four points) keeps more values live
 #endif
@@ -97,16 +103,22 @@ struct K1Cfg {
     static constexpr int LDS_BYTES = (VW * Base::LDS_DATA + 1024) * 8;
 };
 
-template <int LOG2N>
-__global__ __launch_bounds__(K1Cfg<LOG2N>::T) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void fastfir_os2_kernel(FastFirArgs a)
+// RG ("real gains", N = 16384 only): the responses are the library's own design, H[k] = P[k] j^k with P real
+// (host_math.hpp: fastfir_gain).  The multiply between the transforms is then a real scale by P that rides in I1's first
+// butterflies, all 32 gains of a thread stay in registers for the whole run and nothing of H is fetched inside the block
+// loop; the factor j^k is a circular shift of the block by N/4 samples -- four rows of the outer pass -- that I3 takes by
+// finishing rows 4 ... 11 instead of 8 ... 15.  The registers the in-flight half of H used hold pass twiddles of F2 / I2.
+template <int LOG2N, bool RG>
+__device__ __forceinline__ void fastfir_os2_body(const FastFirArgs a)
 {
     CSDR_WG_TRACE_SCOPE(a.trace, WGT_FF);
+    static_assert(!RG || LOG2N == 14, "the quarter-block shift is whole rows of the outer pass at N = 16384 only");
     using Cfg = FastFirCfg<LOG2N>;
     constexpr int N = Cfg::N, T = Cfg::T, R0 = Cfg::R0, G = Cfg::G, L = N / 2;
     constexpr int HALF = R0 / 2;
     constexpr int VW = K1Cfg<LOG2N>::VW;
-    constexpr int HREG = LOG2N == 12 ? K1_HREG4K : (LOG2N == 11 ? K1_HREG2K : K1_HREG);   // resident float4 of H
+    constexpr int HREG = RG ? 0 : (LOG2N == 12 ? K1_HREG4K : (LOG2N == 11 ? K1_HREG2K : K1_HREG));   // resident float4 of H
+    constexpr int TWREG = RG ? K1_TWREG : 0;      // pass twiddles k1 = 1 ... TWREG of F2 / I2 that stay in registers
     static_assert(R0 == 16 || R0 == 8 || R0 == 4 || R0 == 2, "the grouped outer pass is written for N = 2048 ... 16384");
     // a block of 2048 points is ONE wave: its two "workgroup" barriers are wave barriers (the four blocks of a workgroup
     // then run free of each other)
@@ -154,6 +166,7 @@ void fastfir_os2_kernel(FastFirArgs a)
     const rsrc_t r_hist = make_rsrc(a.hist + (long)ch * L, L * 8u);
     const rsrc_t r_out = make_rsrc(a.out + (long)ch * a.out_stride, (unsigned)a.nblocks * L * 8u);
     const rsrc_t r_h = make_rsrc(a.h + (long)ch * a.h_stride, N * 8u);
+    const rsrc_t r_g = make_rsrc(a.gain + (long)ch * (a.h_stride / 2), N * 4u);      // (RG; half of H's bytes per filter)
     // A thread's G columns of the outer pass are G / 2 PAIRS, pair pp = columns PSTEP pp + 2t, + 1 (PSTEP = 2 T: every
     // load, store and 16-byte LDS access of a wave covers 64 adjacent pairs -- with G adjacent columns per thread the
     // four 16-byte accesses of the 4096-point kernel each touched a quarter of every line: 1.8 ms instead of 0.8)
@@ -194,9 +207,15 @@ void fastfir_os2_kernel(FastFirArgs a)
     // H: float4 j of this thread (fastfir2_bin_of) multiplies in F3's tail group j / 2.  The first K1_HREG of the
     // sixteen stay in registers for the whole run -- all the registers the kernel has to spare: a 1 KB fetch from
     // L2 costs about as much energy as four packed instructions -- the rest is fetched from L2 for every block
-    v4f hv[16];
+    v4f hv[RG ? 1 : 16];
 #pragma unroll
     for (int j = 0; j < HREG; j++) hv[j] = buf_load16(r_h, t * 16, j * (T * 16));
+    // RG: float4 i of this thread (fastfir2_gain_bin_of) holds the gains of the four bins tail group i of F3 finishes
+    v4f pv[RG ? 8 : 1];
+    if constexpr (RG) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) pv[i] = buf_load16(r_g, t * 16, i * (T * 16));
+    }
 #ifdef K1_ABLATE
     v4f habl = {1.0f, 0.0f, 1.0f, 0.0f};
     asm volatile("" : "+v"(habl));
@@ -217,6 +236,15 @@ void fastfir_os2_kernel(FastFirArgs a)
     const int sb = t >> 5, sn = t & 31;       // sub-transform and column of passes F2 / I2
     v2f *const col = lds + lds_pad(1024 * sb) + sn;         // F2 / I2: point n1 at col[34 * n1]
     const v2f *const twc = tw2 + sn;                        // twiddle k1 at twc[32 * k1]
+    // twiddle k1 of F2 / I2: the first TWREG from registers (read once, from the table in device memory), the rest from LDS
+    v2f twr[TWREG > 0 ? TWREG : 1];
+#pragma unroll
+    for (int k1 = 1; k1 <= TWREG; k1++) twr[k1 - 1] = a.tw2[32 * k1 + sn];
+    auto pass_tw = [&](auto K1) {
+        constexpr int k1 = K1.value;
+        if constexpr (k1 <= TWREG) return twr[k1 - 1];
+        else return lds_ld8(twc + 32 * k1);
+    };
     v2f *const rowp = lds + 34 * t;                         // F3: this thread's 32 consecutive points
     v2f *const outer = lds + lds_pad(2 * t);                // F1 / I3: row k0, pair pp at outer[OUTER_ROW k0 + PSTEP_LDS pp]
     constexpr int OUTER_ROW = 1024 + 2 * (1024 / 32);       // padded elements between rows of the outer pass
@@ -382,7 +410,7 @@ void fastfir_os2_kernel(FastFirArgs a)
 #ifdef ABL_TW
             static_for<1, 4>([&](auto P) { tw[0][P.value] = twabl; });
 #else
-            static_for<1, 4>([&](auto P) { tw[0][P.value] = lds_ld8(twc + 32 * (8 * P.value)); });
+            static_for<1, 4>([&](auto P) { tw[0][P.value] = pass_tw(std::integral_constant<int, 8 * P.value>{}); });
 #endif
             CSDR_SB();
             CSDR_STAMP(8);                             // F2 middle stage
@@ -392,14 +420,14 @@ void fastfir_os2_kernel(FastFirArgs a)
 #ifdef ABL_TW
                     static_for<0, 4>([&](auto P) { tw[(i + 1) & 1][P.value] = twabl; });
 #else
-                    static_for<0, 4>([&](auto P) { tw[(i + 1) & 1][P.value] = lds_ld8(twc + 32 * (i + 1 + 8 * P.value)); });
+                    static_for<0, 4>([&](auto P) { tw[(i + 1) & 1][P.value] = pass_tw(std::integral_constant<int, i + 1 + 8 * P.value>{}); });
 #endif
                 if constexpr (i < 8) {
 #ifdef ABL_H
-                    hv[2 * i] = habl; hv[2 * i + 1] = habl;
+                    if constexpr (!RG) { hv[2 * i] = habl; hv[2 * i + 1] = habl; }
 #else
-                    if constexpr (2 * i >= HREG) hv[2 * i] = buf_load16(r_h, t * 16, (2 * i) * (T * 16));
-                    if constexpr (2 * i + 1 >= HREG) hv[2 * i + 1] = buf_load16(r_h, t * 16, (2 * i + 1) * (T * 16));
+                    if constexpr (!RG && 2 * i >= HREG) hv[2 * i] = buf_load16(r_h, t * 16, (2 * i) * (T * 16));
+                    if constexpr (!RG && 2 * i + 1 >= HREG) hv[2 * i + 1] = buf_load16(r_h, t * 16, (2 * i + 1) * (T * 16));
 #endif
                     dit_tail<i, 32, +1>(x);
                     static_for<0, 4>([&](auto P) {
@@ -451,8 +479,11 @@ void fastfir_os2_kernel(FastFirArgs a)
                 dit_tail<i, 32, +1>(x);
                 // times H: the products of the odd inputs ride in the FMA butterflies of the inverse's first stage
                 y[4 * g] = x[i]; y[4 * g + 1] = x[i + 16]; y[4 * g + 2] = x[i + 8]; y[4 * g + 3] = x[i + 24];
-                dit_head4_tw<g, 32, -1>(y, v2f{hv[2 * i].x, hv[2 * i].y}, v2f{hv[2 * i].z, hv[2 * i].w},
-                                        v2f{hv[2 * i + 1].x, hv[2 * i + 1].y}, v2f{hv[2 * i + 1].z, hv[2 * i + 1].w});
+                if constexpr (RG)
+                    dit_head4_gain<g, 32, -1>(y, v2f{pv[i].x, pv[i].y}, v2f{pv[i].z, pv[i].w});
+                else
+                    dit_head4_tw<g, 32, -1>(y, v2f{hv[2 * i].x, hv[2 * i].y}, v2f{hv[2 * i].z, hv[2 * i].w},
+                                            v2f{hv[2 * i + 1].x, hv[2 * i + 1].y}, v2f{hv[2 * i + 1].z, hv[2 * i + 1].w});
                 if constexpr ((i & 1) == 1) CSDR_SB();
             });
 #pragma unroll
@@ -503,7 +534,7 @@ void fastfir_os2_kernel(FastFirArgs a)
 #ifdef ABL_TW
                     if constexpr (r != 0) tw[r] = twabl;
 #else
-                    if constexpr (r != 0) tw[r] = lds_ld8(twc + 32 * bitrev<32>(r));
+                    if constexpr (r != 0) tw[r] = pass_tw(std::integral_constant<int, bitrev<32>(r)>{});
 #endif
                 });
             };
@@ -570,10 +601,18 @@ void fastfir_os2_kernel(FastFirArgs a)
                 static_for<0, R0 / 4 + 1>([&](auto I) {
                     constexpr int i = I.value;
                     if constexpr (i < R0 / 4) {
-                        dit_tail_upper<i, R0, -1>(y[0]);      // only rows 8..15 of the inverse transform are kept
-                        dit_tail_upper<i, R0, -1>(y[1]);
-                        sv[2 * i] = store_operand(y[0][i + 8], y[1][i + 8]);
-                        sv[2 * i + 1] = store_operand(y[0][i + 12], y[1][i + 12]);
+                        if constexpr (RG) {
+                            // the scale by P left out the response's delay of N/4 samples: output row n1 is row n1 + 4
+                            dit_tail_middle<i, R0, -1>(y[0]);     // only rows 4..11 of the inverse transform are kept
+                            dit_tail_middle<i, R0, -1>(y[1]);
+                            sv[2 * i] = store_operand(y[0][i + 4], y[1][i + 4]);
+                            sv[2 * i + 1] = store_operand(y[0][i + 8], y[1][i + 8]);
+                        } else {
+                            dit_tail_upper<i, R0, -1>(y[0]);      // only rows 8..15 of the inverse transform are kept
+                            dit_tail_upper<i, R0, -1>(y[1]);
+                            sv[2 * i] = store_operand(y[0][i + 8], y[1][i + 8]);
+                            sv[2 * i + 1] = store_operand(y[0][i + 12], y[1][i + 12]);
+                        }
                     }
                     if constexpr (i > 0) {
                         CSDR_STORE_GROUP_BEGIN();
@@ -687,23 +726,38 @@ void fastfir_os2_kernel(FastFirArgs a)
     }
 }
 
+// fastfir_os2_kernel<14> runs on real gains (a.gain); fastfir_os2h_kernel is the same size on complex H, for responses
+// that are not the library's own design (a.gain null)
+template <int LOG2N>
+__global__ __launch_bounds__(K1Cfg<LOG2N>::T) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void fastfir_os2_kernel(FastFirArgs a)
+{
+    fastfir_os2_body<LOG2N, LOG2N == 14 && K1_REALGAIN>(a);
+}
+__global__ __launch_bounds__(K1Cfg<14>::T) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void fastfir_os2h_kernel(FastFirArgs a)
+{
+    fastfir_os2_body<14, false>(a);
+}
+
 template <int LOG2N>
 static hipError_t launch2_one(const FastFirArgs &a, hipStream_t stream)
 {
     using Cfg = K1Cfg<LOG2N>;
-    // once per device and size (the attribute belongs to the device, and a process may drive several): the per-launch
+    void (*kernel)(FastFirArgs) = &fastfir_os2_kernel<LOG2N>;
+    if (LOG2N == 14 && !(K1_REALGAIN && a.gain)) kernel = &fastfir_os2h_kernel;
+    // once per device and kernel (the attribute belongs to the device, and a process may drive several): the per-launch
     // call cost the per-datagram host form microseconds
-    hipError_t e = CSDR_MAX_LDS_ONCE(&fastfir_os2_kernel<LOG2N>, Cfg::LDS_BYTES);
+    hipError_t e = kernel == &fastfir_os2h_kernel ? CSDR_MAX_LDS_ONCE(&fastfir_os2h_kernel, Cfg::LDS_BYTES)
+                                                  : CSDR_MAX_LDS_ONCE(&fastfir_os2_kernel<LOG2N>, Cfg::LDS_BYTES);
     if (e != hipSuccess) return e;
 #ifdef CSDR_WG_TRACE
     FastFirArgs b = a;
     b.trace = wgtrace_next();
-    hipLaunchKernelGGL((fastfir_os2_kernel<LOG2N>), dim3((a.channels * a.runs + Cfg::VW - 1) / Cfg::VW), dim3(Cfg::T),
-                       Cfg::LDS_BYTES, stream, b);
+    hipLaunchKernelGGL(kernel, dim3((a.channels * a.runs + Cfg::VW - 1) / Cfg::VW), dim3(Cfg::T), Cfg::LDS_BYTES, stream, b);
     return hipGetLastError();
 #endif
-    hipLaunchKernelGGL((fastfir_os2_kernel<LOG2N>), dim3((a.channels * a.runs + Cfg::VW - 1) / Cfg::VW), dim3(Cfg::T),
-                       Cfg::LDS_BYTES, stream, a);
+    hipLaunchKernelGGL(kernel, dim3((a.channels * a.runs + Cfg::VW - 1) / Cfg::VW), dim3(Cfg::T), Cfg::LDS_BYTES, stream, a);
     return hipGetLastError();
 }
 
@@ -727,6 +781,12 @@ int fastfir2_bin_of(int log2n, int t, int j, int e)
     const int i = j >> 1, h = j & 1;
     const int k2 = i + 8 * h + 16 * e;
     return (t >> 5) + R0 * ((t & 31) + 32 * k2);
+}
+// ... and of the real gains: float4 i of thread t holds, in the order I1's head group takes them, the gains of the bins
+// k2 = i, i + 16, i + 8, i + 24 -- the halves of H's float4 2 i and 2 i + 1
+int fastfir2_gain_bin_of(int log2n, int t, int i, int c)
+{
+    return fastfir2_bin_of(log2n, t, 2 * i + (c >> 1), c & 1);
 }
 
 }  // namespace csdr

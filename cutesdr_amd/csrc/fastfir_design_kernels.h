@@ -16,6 +16,8 @@ struct DesignArgs {
     const double *tw;           // design_twiddles(N): [2j] = cos, [2j+1] = sin of 2 pi j / N, j < N/2, nearest doubles
     const int *perm, *perm2;    // device slot -> natural bin, generic / pipelined overlap-save kernel
     float *h, *h2;              // [filters][N] complex fp32 in those two orders
+    const int *permg;           // gain slot -> natural bin (fastfir2_gain_bin_of)
+    float *gain;                // [filters][N] fp32 real gains Re(H[k] (-j)^k) in that order (host_math.hpp: fastfir_gain)
     double *resp;               // [filters][N] complex fp64, natural order (N = 16384: also the transform's work row)
 };
 

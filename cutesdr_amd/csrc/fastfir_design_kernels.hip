@@ -9,7 +9,8 @@
 //      multiply-adds: the response is then the same words whatever the compiler, and a plain fp64 model of the network
 //      reproduces it),
 //   3. writes the fp32 response in the generic and in the pipelined overlap-save kernel's register order (permutation
-//      tables) and the fp64 response in natural order (the row get_response reads).
+//      tables), its real gains Re(H[k] (-j)^k) in the 16384-point kernel's order, and the fp64 response in natural order
+//      (the row get_response reads).
 // N = 2048 / 4096 / 8192: the transform lives in LDS as complex fp64 (32 / 64 / 128 KB); N = 16384 would need 256 KB, so
 // that size works in its fp64 response row in device memory (L2 resident, workgroup barriers between the stages).
 // Control plane: one launch per process call at most.  Nothing here is tuned beyond keeping consecutive lanes on
@@ -87,11 +88,17 @@ __global__ __launch_bounds__(DesignCfg<LOG2N>::T) void fastfir_design_kernel(Des
     // ---- the three forms of the response
     v2f_d *h = reinterpret_cast<v2f_d *>(a.h) + (size_t)job.slot * N;
     v2f_d *h2 = reinterpret_cast<v2f_d *>(a.h2) + (size_t)job.slot * N;
+    float *gain = a.gain + (size_t)job.slot * N;
     for (int i = tid; i < N; i += T) {
         const v2d p = w[a.perm[i]], p2 = w[a.perm2[i]];
         v2f_d f = {(float)p.x, (float)p.y}, f2 = {(float)p2.x, (float)p2.y};
         h[i] = f;
         h2[i] = f2;
+        // the real gain of the linear-phase response, Re(H[k] (-j)^k): the component of H[k] that k mod 4 selects
+        const int kg = a.permg[i];
+        const v2d pg = w[kg];
+        const double gr = (kg & 1) ? pg.y : pg.x;
+        gain[i] = (float)((kg & 2) ? -gr : gr);
         if constexpr (Cfg::IN_LDS) row[i] = w[i];
     }
 }

@@ -14,6 +14,8 @@ struct FastFirArgs {
     v2f_h *hist_next;     // [channels][N/2]: receives this call's tail (other ping-pong half)
     v2f_h *out;           // [channels][out_stride]
     const v4f_h *h;       // frequency response in pass-F3 register order, [16][N/32] float4 per filter
+    const v4f_h *gain;    // N = 16384, pipelined kernel, responses of the library's own design only (else null): the real
+                          // gains P[k] = Re(H[k] (-j)^k) in that kernel's order, [8][N/32] float4 per filter (fastfir2_gain_bin_of)
     const v2f_h *tw1;     // W_N^{n}, n = 0..1023
     const v2f_h *tw2;     // W_1024^{n*k}, [k][n], 32x32
     long in_stride;       // complex samples between channels
@@ -38,5 +40,8 @@ int fastfir_bin_of(int log2n, int t, int r);
 hipError_t fastfir2_launch(int log2n, const FastFirArgs &a, hipStream_t stream);
 // natural-order spectrum bin of H slot (float4 index j*(N/32) + t, half e) of that kernel
 int fastfir2_bin_of(int log2n, int t, int j, int e);
+// natural-order spectrum bin of gain slot (float4 index i*(N/32) + t, component c): the same per-thread order, four
+// gains per tail group i
+int fastfir2_gain_bin_of(int log2n, int t, int i, int c);
 
 }  // namespace csdr

@@ -354,6 +354,50 @@ __host__ __device__ __forceinline__ void dit_head4_tw(v2f (&x)[R], v2f t0, v2f t
     bfly_dit<0, SIGN>(x[a], x[a + 2]);                               // stage 4
     bfly_dit<8, SIGN>(x[a + 1], x[a + 3]);
 }
+// Butterfly with REAL multipliers of its two inputs folded in: a' = a g.x + b g.y, b' = a g.x - b g.y -- one packed
+// multiply and two packed FMAs (the gain pair sits in one 64-bit register pair, op_sel broadcasts a half)
+__host__ __device__ __forceinline__ void bfly_gain(v2f &xa, v2f &xb, v2f g)
+{
+#if CSDR_PK_ASM
+    v2f t, a, b;
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0]" : "=v"(t) : "v"(xa), "v"(g));
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(a) : "v"(xb), "v"(g), "v"(t));
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[0,1,0] neg_hi:[0,1,0]"
+        : "=v"(b) : "v"(xb), "v"(g), "v"(t));
+    xa = a; xb = b;
+#else
+    const v2f t = xa * g.xx, v = xb * g.yy;
+    xa = t + v; xb = t - v;
+#endif
+}
+// dit_head4 with real multipliers of its four inputs folded in: x[4G+q] *= gq first, (g0, g1) = g01, (g2, g3) = g23
+// (the frequency response of a linear-phase filter, whose phase is a circular shift the caller accounts for): 6 packed
+// instructions + 4 for the stage-4 pair, against dit_head4_tw's 10 + 4
+template <int G, int R, int SIGN>
+__host__ __device__ __forceinline__ void dit_head4_gain(v2f (&x)[R], v2f g01, v2f g23)
+{
+    constexpr int a = 4 * G;
+    bfly_gain(x[a], x[a + 1], g01);                                  // stage 2
+    bfly_gain(x[a + 2], x[a + 3], g23);
+    bfly_dit<0, SIGN>(x[a], x[a + 2]);                               // stage 4
+    bfly_dit<8, SIGN>(x[a + 1], x[a + 3]);
+}
+// DIT butterfly of which only the sum output is wanted: a' = a + b * e^{SIGN j 2 pi K/32} (b is left alone)
+template <int K, int SIGN>
+__host__ __device__ __forceinline__ void bfly_dit_sum(v2f &xa, const v2f xb)
+{
+    if constexpr (K == 0) {
+        xa = xa + xb;
+    } else if constexpr (K == 8) {
+        xa = add_jv<SIGN>(xa, xb);
+    } else {
+        constexpr float c = kCos32[K];
+        constexpr float s = (SIGN > 0 ? 1.0f : -1.0f) * kCos32[(K + 24) & 31];
+        const v2f w1 = {c, s}, w2 = {-s, c};
+        const v2f t = __builtin_elementwise_fma(xb.xx, w1, xa);
+        xa = __builtin_elementwise_fma(xb.yy, w2, t);
+    }
+}
 // DIT butterfly of which only the difference output is wanted: b' = a - b * e^{SIGN j 2 pi K/32} (a is left alone)
 template <int K, int SIGN>
 __host__ __device__ __forceinline__ void bfly_dit_lower(const v2f xa, v2f &xb)
@@ -381,6 +425,19 @@ __host__ __device__ __forceinline__ void dit_tail_upper(v2f (&x)[R])
     bfly_dit<I *(64 / R), SIGN>(x[I + 2 * Q], x[I + 3 * Q]);
     bfly_dit_lower<I *(32 / R), SIGN>(x[I], x[I + 2 * Q]);           // stage R, difference outputs only
     bfly_dit_lower<(I + Q) * (32 / R), SIGN>(x[I + Q], x[I + 3 * Q]);
+}
+// dit_tail whose caller keeps only the MIDDLE half of the transform's outputs, rows R/4 ... 3R/4 - 1 (x[I + R/4], the sum
+// output of its last-stage butterfly, and x[I + R/2], the difference output of the other): the kept half of an
+// overlap-save block whose response carries a delay of N/4 samples that the multiply left out
+template <int I, int R, int SIGN>
+__host__ __device__ __forceinline__ void dit_tail_middle(v2f (&x)[R])
+{
+    static_assert(R >= 8 && I < R / 4, "dit_tail_middle");
+    constexpr int Q = R / 4;
+    bfly_dit<I *(64 / R), SIGN>(x[I], x[I + Q]);                     // stage R/2
+    bfly_dit<I *(64 / R), SIGN>(x[I + 2 * Q], x[I + 3 * Q]);
+    bfly_dit_lower<I *(32 / R), SIGN>(x[I], x[I + 2 * Q]);           // stage R: row I + R/2 = difference,
+    bfly_dit_sum<(I + Q) * (32 / R), SIGN>(x[I + Q], x[I + 3 * Q]);  //          row I + R/4 = sum
 }
 template <int I, int R, int SIGN>
 __host__ __device__ __forceinline__ void dit_tail(v2f (&x)[R])

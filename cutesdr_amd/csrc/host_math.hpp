@@ -133,4 +133,22 @@ inline bool fastfir_design(int n, double flo, double fhi, double offset, double 
     return true;
 }
 
+// Every response fastfir_design makes is LINEAR PHASE: the taps are a real window-times-sinc, symmetric about the centre
+// tap c = (p - 1) / 2 = n / 4, times e^{j nfs (i - c)}.  With g[m] = h[m + c] (g[-m] = conj(g[m]), so its transform G is
+// real) and the forward transform's sign +1 (host_fft, dsp/fft.cpp:416-420):
+//     H[k] = sum_i h[i] e^{+j 2 pi i k / n} = e^{+j 2 pi c k / n} G[k] = j^k G[k],
+// whatever the edges and the offset are.  So P[k] = Re(H[k] (-j)^k) is the whole response (the imaginary part is
+// rounding, 1e-12 max|H| and less: tests/test_fastfir_realgain.py), and the factor j^k = e^{+j 2 pi (n/4) k / n} is,
+// under the inverse transform's sign -1, a delay of the block by n / 4 samples: y[m] = z[m - n/4] with z the inverse
+// transform of X P.  The 16384-point overlap-save kernel multiplies by P and keeps z[n/4 ... 3n/4) (fastfir2_kernels.hip).
+inline double fastfir_gain(const cd &h, int k)
+{
+    switch (k & 3) {
+    case 0: return h.real();
+    case 1: return h.imag();          // Re(h * -j)
+    case 2: return -h.real();
+    default: return -h.imag();        // Re(h * +j)
+    }
+}
+
 }  // namespace csdr
