@@ -214,6 +214,46 @@ def _build(force=False, verbose=False, link_extra=()):
     return LIB
 
 
+def alt_path(name):
+    return os.path.join(HERE, "libcutesdr_mi_%s.so" % name)
+
+
+def alt_lib(name, extra, units=("fastfir2_kernels",), verbose=False):
+    """A copy of the library in which only `units` (by default K1's, fastfir2_kernels.hip) are compiled with the extra
+    flags `extra` (-D...), every other object the product's own: cutesdr_amd/libcutesdr_mi_NAME.so, for A/B runs and
+    parity tests of a kernel build (pick it with CSDR_LIB_PATH; tools/altlib.py is the command line).  The alternative
+    objects sit beside the product's and are cached by their flags like them."""
+    build(verbose=verbose)
+    hipcc = _hipcc()
+    headers = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hpp")) + \
+        glob.glob(os.path.join(HERE, "..", "include", "*.h"))
+    out = alt_path(name)
+    alt, fresh = [], False
+    for unit in units:
+        src = os.path.join(CSRC, unit + ".hip")
+        obj = os.path.join(OBJ, "%s.%s.o" % (unit, name))
+        cmd = [hipcc] + FLAGS + FILE_FLAGS.get(unit + ".hip", []) + ["-I", OBJ] + list(extra) + ["-c", src, "-o", obj]
+        stamp, flags = obj + ".flags", " ".join(cmd[1:-4])
+        if _newer(obj, [src] + headers) or not os.path.exists(stamp) or open(stamp).read() != flags:
+            if verbose:
+                print(" ".join(cmd), file=sys.stderr)
+            subprocess.check_call(cmd)
+            with open(stamp, "w") as f:
+                f.write(flags)
+            fresh = True
+        alt.append(obj)
+    objs = [o for o in sorted(glob.glob(os.path.join(OBJ, "*.hip.o")) + glob.glob(os.path.join(OBJ, "downconv_plan_*.o")))
+            if os.path.basename(o)[:-6] not in units]
+    if fresh or _newer(out, objs + alt):
+        subprocess.check_call([hipcc, "-shared", "-fPIC", "--offload-arch=" + ARCH, "-o", out] + objs + alt)
+    return out
+
+
+# the build of K1 whose pass twiddles k1 = 1, 2 and 3 stay in registers (fastfir2_kernels.hip: K1_TWREG), kept beside
+# the product's library for tests/test_fastfir_twreg_gpu.py
+TWREG3 = ("twreg3", ["-DK1_TWREG=3"])
+
+
 if __name__ == "__main__":
     kind = next((a.split("=", 1)[1] for a in sys.argv if a.startswith("--sanitize=")), None)
     var = next((a.split("=", 1)[1] for a in sys.argv if a.startswith("--variant=")), None)

@@ -31,8 +31,10 @@ struct csdr_fastfir_batch {
     float *d_gain;                    // [filters][n] fp32: the real gains of the same responses, Re(H[k] (-j)^k), in the
                                       // pipelined kernel's order (host_math.hpp: fastfir_gain) -- what its 16384-point
                                       // instantiation multiplies by while own_design holds
-    bool own_design;                  // every response came from fastfir_design / the design kernel (linear phase): always
-                                      // true today, a setter of raw responses would clear it and with it the real-gain kernel
+    bool own_design;                  // every response came from fastfir_design / the design kernel (linear phase): a setter
+                                      // of raw responses would clear it and with it the real-gain kernel; today only the
+                                      // test hook csdr__fastfir_set_own_design does
+    int last_kernel;                  // FastFirKernel of the most recent process call (csdr__fastfir_last_kernel)
     float *d_hist;                    // 2 x [channels][n/2] complex fp32 (ping-pong)
     int hist_cur;                     // which half holds the previous call's tail
     int dbg_stage; float *dbg_out;    // diagnostics only (csdr__dbg_fastfir_stage)
@@ -224,6 +226,7 @@ csdr_fastfir_batch *csdr_fastfir_batch_create(int device, int channels, int fft_
     }
     b->d_h = b->d_h2 = b->d_gain = b->d_hist = b->d_tw1 = b->d_tw2 = nullptr;
     b->own_design = true;
+    b->last_kernel = FASTFIR_KERNEL_NONE;
     b->flo = -1.0; b->fhi = 1.0; b->off = 1.0; b->fs = 1.0;      // fastfir.cpp:126-129
     build_perm(b);
     const size_t hbytes = (size_t)fft_size * 8, histbytes = 2 * (size_t)channels * (fft_size / 2) * 8;
@@ -449,9 +452,14 @@ int csdr_fastfir_batch_process(csdr_fastfir_batch *b, const float *d_in, long lo
         a.h = (const v4f_h *)b->d_h2;         // its own H order
         // N = 16384 on the library's own (linear-phase) designs: real gains and a quarter-block shift instead of complex H
         if (b->log2n == 14 && b->own_design) a.gain = (const v4f_h *)b->d_gain;
-        CSDR_HIP(fastfir2_launch(b->log2n, a, s));     // any block count (pairs, then a single trailing block)
+        b->last_kernel = FASTFIR_KERNEL_NONE;
+        CSDR_HIP(fastfir2_launch(b->log2n, a, s, &b->last_kernel));     // any block count (pairs, then a single trailing block)
     }
-    else CSDR_HIP(fastfir_launch(b->log2n, a, s));
+    else {
+        b->last_kernel = FASTFIR_KERNEL_NONE;
+        CSDR_HIP(fastfir_launch(b->log2n, a, s));
+        b->last_kernel = FASTFIR_KERNEL_GENERIC;
+    }
     b->hist_cur ^= 1;        // the kernel left this call's tail in the other half
     return CSDR_OK;
 }
@@ -486,6 +494,26 @@ int csdr__fastfir_set_variant(csdr_fastfir_batch *b, int variant)
 {
     if (!b || (variant != 0 && variant != 2)) return CSDR_EINVAL;
     b->variant = variant;
+    return CSDR_OK;
+}
+
+/* test-only hook, not part of the public ABI: say whether the object's responses are all the library's own design (the
+ * flag a setter of raw responses would clear): 0 sends a 16384-point launch to the pipelined kernel on complex H */
+int csdr__fastfir_set_own_design(csdr_fastfir_batch *b, int own)
+{
+    if (!b) return CSDR_EINVAL;
+    b->own_design = own != 0;
+    return CSDR_OK;
+}
+
+/* test-only hook, not part of the public ABI: *kernel = which kernel the most recent process call launched (FastFirKernel,
+ * fastfir_kernels.h: -1 none yet, 0 generic, 1 pipelined on complex H, 2 pipelined on real gains -- written by the code
+ * that chooses), *twreg = the K1_TWREG the pipelined kernels were compiled with */
+int csdr__fastfir_last_kernel(const csdr_fastfir_batch *b, int *kernel, int *twreg)
+{
+    if (!b || !kernel || !twreg) return CSDR_EINVAL;
+    *kernel = b->last_kernel;
+    *twreg = fastfir2_twreg();
     return CSDR_OK;
 }
 

@@ -741,11 +741,13 @@ void fastfir_os2h_kernel(FastFirArgs a)
 }
 
 template <int LOG2N>
-static hipError_t launch2_one(const FastFirArgs &a, hipStream_t stream)
+static hipError_t launch2_one(const FastFirArgs &a, hipStream_t stream, int *which)
 {
     using Cfg = K1Cfg<LOG2N>;
     void (*kernel)(FastFirArgs) = &fastfir_os2_kernel<LOG2N>;
     if (LOG2N == 14 && !(K1_REALGAIN && a.gain)) kernel = &fastfir_os2h_kernel;
+    // (the one instantiation whose body runs on real gains: fastfir_os2_kernel<14> of a K1_REALGAIN build)
+    if (which) *which = (LOG2N == 14 && K1_REALGAIN && kernel != &fastfir_os2h_kernel) ? FASTFIR_KERNEL_PIPELINED_GAIN : FASTFIR_KERNEL_PIPELINED_H;
     // once per device and kernel (the attribute belongs to the device, and a process may drive several): the per-launch
     // call cost the per-datagram host form microseconds
     hipError_t e = kernel == &fastfir_os2h_kernel ? CSDR_MAX_LDS_ONCE(&fastfir_os2h_kernel, Cfg::LDS_BYTES)
@@ -761,16 +763,18 @@ static hipError_t launch2_one(const FastFirArgs &a, hipStream_t stream)
     return hipGetLastError();
 }
 
-hipError_t fastfir2_launch(int log2n, const FastFirArgs &a, hipStream_t stream)
+hipError_t fastfir2_launch(int log2n, const FastFirArgs &a, hipStream_t stream, int *kernel)
 {
     switch (log2n) {
-    case 11: return launch2_one<11>(a, stream);
-    case 12: return launch2_one<12>(a, stream);
-    case 13: return launch2_one<13>(a, stream);
-    case 14: return launch2_one<14>(a, stream);
+    case 11: return launch2_one<11>(a, stream, kernel);
+    case 12: return launch2_one<12>(a, stream, kernel);
+    case 13: return launch2_one<13>(a, stream, kernel);
+    case 14: return launch2_one<14>(a, stream, kernel);
     default: return hipErrorInvalidValue;
     }
 }
+
+int fastfir2_twreg() { return K1_TWREG; }
 
 // Host mirror of the kernel's index algebra: thread t of pass F3 owns k0 = t >> 5 (sub-transform) and k1 = t & 31
 // (its row), and consumes H in the order its tail groups finish bins: float4 j = 2 i + h of thread t, half e,

@@ -37,7 +37,12 @@ int fastfir_bin_of(int log2n, int t, int r);
 
 // software-pipelined build, N = 2048 ... 16384 (fastfir2_kernels.hip): same LDS image as fastfir_launch, its
 // own H order
-hipError_t fastfir2_launch(int log2n, const FastFirArgs &a, hipStream_t stream);
+// *kernel, where given, receives which kernel the launch took (FastFirKernel): the test hook
+// csdr__fastfir_last_kernel reports it, so the answer comes from the code that chooses
+enum FastFirKernel { FASTFIR_KERNEL_NONE = -1, FASTFIR_KERNEL_GENERIC = 0, FASTFIR_KERNEL_PIPELINED_H = 1, FASTFIR_KERNEL_PIPELINED_GAIN = 2 };
+hipError_t fastfir2_launch(int log2n, const FastFirArgs &a, hipStream_t stream, int *kernel = nullptr);
+// the K1_TWREG that unit was compiled with
+int fastfir2_twreg();
 // natural-order spectrum bin of H slot (float4 index j*(N/32) + t, half e) of that kernel
 int fastfir2_bin_of(int log2n, int t, int j, int e);
 // natural-order spectrum bin of gain slot (float4 index i*(N/32) + t, component c): the same per-thread order, four

@@ -76,9 +76,26 @@ def _oracle_out(r, x, stereo):
     return np.concatenate(w) if w else np.zeros(0, dtype=np.complex128)
 
 
-def _start_bound(mode, k, errs, first, stereo, late):
+def _span(bursts, hop):
+    """an allowance of `bursts` 1024-sample bursts keeps its length in samples: the whole bursts of `hop` samples it touches"""
+    return -(-bursts * 1024 // hop)
+
+
+def _start_bound(mode, k, errs, first, stereo, late, hop=1024):
     """the chain rule (test_postchain_gpu.check_chain_bursts; a restart as in test_live_mode_change_inside_a_batch) as
-    per-burst bounds; k: bursts since the demodulator started, errs: the errors from there"""
+    per-burst bounds; k: bursts since the demodulator started, errs: the errors from there.  hop = 8192 (the 16384-point
+    filter): a burst's bound is the largest the rule gives any of the eight 1024-sample bursts in it -- every allowance
+    keeps its length in samples, rounded up to whole bursts -- except the stream's first burst, which holds the whole
+    start-up: startup_bounds.first_burst_16k on this rig's rows (FM: the pull-in, arbitrary), the steady bound behind it"""
+    if hop != 1024:
+        assert hop == 8192, hop
+        r = hop // 1024
+        fine = (np.asarray(k)[:, None] * r + np.arange(r)[None, :]).ravel()
+        out = _start_bound(mode, fine, np.zeros(0), first, stereo, late).reshape(-1, r).max(axis=1)
+        if first:
+            b0 = SB.first_burst_16k(mode, stereo, rig=True)
+            out = np.where(k == 0, 2.5 * FULL_SCALE if b0 is None else b0 * FULL_SCALE, out)
+        return out
     if mode == "FM":
         s = 0
         big = np.nonzero(errs[:3] > 0.2 * FULL_SCALE)[0]
@@ -101,8 +118,8 @@ class Track:
     """one receiver's per-burst audio errors since its stream began, and the events that set their bounds: every event's
     rule holds from its burst until the demodulator's next start; the bound of a burst is the largest that holds there"""
 
-    def __init__(self, mode, stereo=False, fm_late=0):
-        self.mode, self.stereo, self.fm_late = mode, stereo, fm_late
+    def __init__(self, mode, stereo=False, fm_late=0, hop=1024):
+        self.mode, self.stereo, self.fm_late, self.hop = mode, stereo, fm_late, hop
         self.errs = []
         self.events = [(0, "start", mode, True)]
 
@@ -124,9 +141,9 @@ class Track:
             on = (i >= pos) & (i < end)
             k = i - pos
             if kind == "ctl":
-                b = np.where(k < 8, (1e-3 if mode == "FM" else 5e-4) * FULL_SCALE, FM_STEADY if mode == "FM" else STEADY)
+                b = np.where(k < _span(8, self.hop), (1e-3 if mode == "FM" else 5e-4) * FULL_SCALE, FM_STEADY if mode == "FM" else STEADY)
             else:
-                b = _start_bound(mode, k, e[pos:] if pos < n else e[:0], first, self.stereo, self.fm_late if first else 0)
+                b = _start_bound(mode, k, e[pos:] if pos < n else e[:0], first, self.stereo, self.fm_late if first else 0, self.hop)
             bound = np.where(on, np.maximum(bound, b), bound)
         return bound
 
@@ -135,9 +152,9 @@ class Track:
         if not len(want):
             return
         if self.mode == "FM" and not self.stereo:                   # identical squelch decisions, burst by burst
-            for j in range(0, len(want), 1024):
-                assert (not np.any(got[j:j + 1024])) == (not np.any(want[j:j + 1024])), (what, j // 1024)
-        self.errs.extend(burst_errors(np.asarray(got, dtype=want.dtype), want))
+            for j in range(0, len(want), self.hop):
+                assert (not np.any(got[j:j + self.hop])) == (not np.any(want[j:j + self.hop])), (what, j // self.hop)
+        self.errs.extend(burst_errors(np.asarray(got, dtype=want.dtype), want, self.hop))
         e, bd = np.asarray(self.errs), self.bounds()
         assert np.isfinite(e).all(), (what, self.mode)
         bad = np.nonzero(e > bd)[0]
@@ -154,14 +171,15 @@ class Rig:
     """a batch and one oracle CDemodulator per receiver, driven by the same calls"""
 
     def __init__(self, ca, oracle, names, kinds=None, rows=None, form=0, taps=0, oracle_taps=False, stereo=False,
-                 freqs=None, fm_late=0):
+                 freqs=None, fm_late=0, nfft=2048):
         self.ca, self.oracle, self.stereo = ca, oracle, stereo
+        self.nfft = nfft                                   # the band-pass filter's size; a burst of audio is one hop of it
         self.C = len(names)
         self.modes = list(names)
         self.kinds = list(kinds or [KIND_OF[m] for m in names])
         self.freqs = list(freqs or [-100e3] * self.C)
         self.fs = FS
-        self.batches = [ca.DemodBatch(self.C, 2048)]
+        self.batches = [ca.DemodBatch(self.C, nfft)]
         self.refs = []
         for b in self.batches:
             b.set_input_rate(FS)
@@ -171,7 +189,7 @@ class Rig:
             m, kw = _info_kw(name)
             for b in self.batches:
                 b.set_demod(c, m, info(ca, **kw))
-            r = oracle.CDemodulator(2048)
+            r = oracle.CDemodulator(nfft)
             r.SetInputSampleRate(FS); r.SetDemod(m, info(oracle, **kw)); r.SetDemodFreq(self.freqs[c])
             if oracle_taps:
                 r.enable_taps(True)
@@ -185,7 +203,7 @@ class Rig:
             self.b.set_taps(taps)
         if form:
             self.b.set_pipelined(form)
-        self.tracks = [Track(m, stereo, fm_late) for m in names]
+        self.tracks = [Track(m, stereo, fm_late, nfft // 2) for m in names]
         self.set_demods = [0] * self.C                     # SetDemod calls a receiver has had since commit
 
     def set_demod(self, c, name, **over):

@@ -454,7 +454,7 @@ def test_whole_cdemodulator_chain_composed_from_the_independent_stages(oracle, m
 
 
 # ---- the start-up tolerances of the GPU chain tests, derived on the oracle alone (VERDICT r5 task 4) ------------------------
-def _startup_spread(oracle, mode, stereo, fs, nfft, nwin, seeds=(1, 2, 3, 4, 5, 6)):
+def _startup_spread(oracle, mode, stereo, fs, nfft, nwin, seeds=(1, 2, 3, 4, 5, 6), x=None):
     """per-burst max |audio(disturbed filter output) - audio(fp64 filter output)| of the ORACLE chain, maximum over
     seeds and over the two disturbances of an fp32 filter's error floor (oracle/cutesdr_oracle.c: mode 3 = additive
     noise of 3e-7 of the largest filter input, K1's measured error; mode 4 = the same floor as a grid of 1e-8), in units
@@ -462,7 +462,7 @@ def _startup_spread(oracle, mode, stereo, fs, nfft, nwin, seeds=(1, 2, 3, 4, 5, 
     import test_postchain_gpu as T
     from test_chain_parity_gpu import chain_input
     lim = 19968 if fs == 2e6 else 99840
-    x = chain_input(mode, lim * nwin, fs)
+    x = chain_input(mode, lim * nwin, fs) if x is None else x(lim * nwin)      # x: another input, as a function of its length
     hop = nfft // 2
 
     def run(perturb=None):
@@ -557,3 +557,59 @@ def test_startup_spread_linear_modes(oracle, mode):
     if mode == "AM":
         _reproduces(worst[0], SB.LINEAR_SPREAD[0], "AM burst 0")
     assert worst[1:].max() < 2e-6 and rounding.max() < 2e-7
+
+
+@pytest.mark.parametrize("mode,stereo", [("AM", False), ("USB", False), ("LSB", False), ("CWU", False), ("SAM", False),
+                                         ("AM", True), ("SAM", True), ("FM", False), ("FM", True)],
+                         ids=lambda v: v if isinstance(v, str) else ("stereo" if v else "mono"))
+def test_startup_spread_behind_the_16384_point_filter(oracle, mode, stereo):
+    """one burst is 8192 samples: the whole start-up is in burst 0 (startup_bounds.SPREAD_16K...), behind it nothing --
+    every later burst at least five times below the steady bounds the GPU tests apply from the second burst on"""
+    import startup_bounds as SB
+    worst, rounding = _startup_spread(oracle, mode, stereo, 2e6, 16384, 160 if mode == "CWU" else 80)
+    assert rounding.max() < 2e-7
+    if mode == "FM":
+        rec = SB.FM_SPREAD_16K_STEREO if stereo else SB.FM_SPREAD_16K
+        _reproduces(worst[0], rec[0], ("FM", stereo, 0))
+        _reproduces(worst[1], rec[1], ("FM", stereo, 1))
+        assert worst[0] <= 2.5 and worst[1] <= 3e-5 / 5.0 and worst[2:].max() <= 1.5 * 1.2e-7
+    else:
+        _reproduces(worst[0], (SB.SPREAD_16K_STEREO if stereo else SB.SPREAD_16K)[mode], (mode, stereo, 0))
+        assert worst[1:].max() <= SB.LATER_16K <= 2e-5 / 5.0, worst[1:].max()
+        if mode == "SAM" and stereo:
+            assert worst[0] <= SB.SAM_STEREO_BISTABLE
+
+
+@pytest.mark.parametrize("mode", ["AM", "USB", "LSB", "CWU", "SAM", "FM"])
+def test_startup_spread_behind_the_16384_point_filter_on_the_batch_rigs_rows(oracle, mode):
+    """the same on the input tests/test_chain_16384_gpu.py feeds (test_batch_control_combinations_gpu._signal, -20 dBFS):
+    the six tones of the SSB / CW row give three times chain_input's spread, the carriers the same"""
+    import startup_bounds as SB
+    from test_batch_control_combinations_gpu import _signal, KIND_OF
+    worst, _ = _startup_spread(oracle, mode, False, 2e6, 16384, 160 if mode == "CWU" else 80,
+                               x=lambda n: _signal(KIND_OF[mode], 0, n, 2e6).astype(np.complex128))
+    if mode == "FM":
+        _reproduces(worst[0], SB.FM_SPREAD_16K[0], ("FM", 0))
+        _reproduces(worst[1], SB.FM_SPREAD_16K[1], ("FM", 1))
+        assert worst[1] <= 3e-5 / 5.0
+    else:
+        _reproduces(worst[0], SB.SPREAD_16K_RIG[mode], (mode, 0))
+        assert worst[1:].max() <= SB.LATER_16K_RIG <= 2e-5 / 5.0, worst[1:].max()
+
+
+def test_a_carrier_restarted_at_a_call_boundary_is_not_a_stream_behind_the_16384_point_filter(oracle):
+    """why tests/test_chain_16384_gpu.py cuts ONE stream into its calls: the 2048-point batch tests start their signal
+    again with every call, and the carrier's phase jump there rings through the 8193 taps with the AGC behind it -- the
+    reference's own spread in the two bursts behind the first jump is 7.2e-5 / 3.0e-5 of full scale (AM), above the steady
+    bound of 2e-5; on one stream of the same length it is 3e-7"""
+    import startup_bounds as SB
+    from test_batch_control_combinations_gpu import _signal, LIM
+    windows = [32, 16, 16, 32]
+    restarted = lambda n: np.concatenate([_signal("AM", 0, w * LIM, 2e6) for w in windows]).astype(np.complex128)
+    stream = lambda n: _signal("AM", 0, n, 2e6).astype(np.complex128)
+    jump, _ = _startup_spread(oracle, "AM", False, 2e6, 16384, sum(windows), seeds=(1, 2, 3), x=restarted)
+    one, _ = _startup_spread(oracle, "AM", False, 2e6, 16384, sum(windows), seeds=(1, 2, 3), x=stream)
+    assert len(jump) == 3
+    _reproduces(jump[1], 7.2e-5, "burst 1 behind a phase jump")
+    _reproduces(jump[2], 3.0e-5, "burst 2 behind a phase jump")
+    assert jump[1] > 2e-5 and one[1:].max() <= SB.LATER_16K_RIG
