@@ -1,5 +1,5 @@
 // capi_demod_batch.hip -- C ABI of the batched, device-resident form of the receive chain (CDemodulator for many
-// receivers at once): plan groups of receivers that decimate alike, each a ChainCore (chain_core.hpp), and the three
+// receivers at once): plan groups of receivers that decimate alike, each a ChainCore (chain_core.hpp), and the two
 // schedules a process call runs them in.  The single-channel host form: capi_demod.hip.
 #include "chain_core.hpp"
 #include <algorithm>
@@ -23,10 +23,9 @@ struct PlanGroup {
     int *d_rows = nullptr;                            // device array of the rows' input rows
     int *d_out_rows = nullptr;                        // ... and of their output rows (= channel ids), -1 = muted
     hipStream_t stream = nullptr;
-    hipStream_t post_stream = nullptr;                // chained pipeline: its post-chain's stream
+    hipStream_t post_stream = nullptr;                // pipelined mode: its post-chain's stream
     Event join;                                       // the group's part of a call has been issued
     Event dc_done;                                    // its down-converter has been issued and finished
-    int prev_post = -1;                               // pipelined: the post-chain event of the previous call
     bool prev_join = false;                           // pipelined: `join` of the previous call not yet waited for
     ~PlanGroup()
     {
@@ -48,12 +47,11 @@ struct PlanGroup {
         if (!post_stream) CSDR_HIP(stream_pool().get(core.device, prio, &post_stream, STREAM_POST));
         return CSDR_OK;
     }
-    // pipelined mode: `caller` waits for what the previous call left in flight here -- its join event (the input has been
-    // consumed) and, with_post, the three-stage form's post-chain (the output rows are complete)
-    int late_join(hipStream_t caller, bool with_post)
+    // pipelined mode: `caller` waits for what the previous call left in flight here -- its join event, recorded behind the
+    // call's last work (the input has been consumed, the output rows are complete)
+    int late_join(hipStream_t caller)
     {
         if (prev_join) { CSDR_HIP(hipStreamWaitEvent(caller, join, 0)); prev_join = false; }
-        if (with_post && prev_post >= 0) { CSDR_HIP(hipStreamWaitEvent(caller, core.ts.ev_post[prev_post], 0)); prev_post = -1; }
         return CSDR_OK;
     }
 };
@@ -69,8 +67,7 @@ struct csdr_demod_batch {
     std::vector<int> order;                           // groups, heaviest post-chain first
     Event fork;
     bool pipelined = false;                           // csdr_demod_batch_set_pipelined
-    bool chained = false;                             // ... its chained form (ChainCore::step_split): the cores stay plain
-    bool have_last_dc = false;                        // chained pipeline: dc_done of order.back() holds the previous call's record
+    bool have_last_dc = false;                        // pipelined mode: dc_done of order.back() holds the previous call's record
     int taps = 0;                                     // csdr_demod_batch_set_taps (new groups inherit it: batch_move_row)
     bool rate_change_failed = false;                  // csdr_demod_batch_set_input_rate stopped half way: no processing until one succeeds
     float *d_blank = nullptr;                         // blanked input of process_packets (two-pass form)
@@ -89,7 +86,7 @@ struct csdr_demod_batch {
 // first: its down-converter should not share the chip with the other groups' while its demodulators wait.
 static void batch_order(csdr_demod_batch *b)
 {
-    b->have_last_dc = false;                            // (the chained pipeline's link to the previous call's last group)
+    b->have_last_dc = false;                            // (the pipelined mode's link to the previous call's last group)
     std::vector<double> weight(b->groups.size(), 0.0);
     for (int c = 0; c < b->channels; c++) {
         if (b->core_of[c] < 0) continue;
@@ -117,9 +114,9 @@ static int batch_plumbing(csdr_demod_batch *b, bool ranked, PlanGroup *extra = n
     return extra ? extra->plumbing(pr_lo) : CSDR_OK;
 }
 // pipelined mode: `stream` waits for what the previous call left in flight (PlanGroup::late_join), in every group
-static int batch_late_join(csdr_demod_batch *b, void *stream, bool with_post)
+static int batch_late_join(csdr_demod_batch *b, void *stream)
 {
-    for (auto &g : b->groups) { const int rc = g->late_join((hipStream_t)stream, with_post); if (rc) return rc; }
+    for (auto &g : b->groups) { const int rc = g->late_join((hipStream_t)stream); if (rc) return rc; }
     return CSDR_OK;
 }
 
@@ -169,9 +166,7 @@ static int batch_move_row(csdr_demod_batch *b, int channel, int new_stages, Appl
         fresh.reset(new PlanGroup());
         rc = fresh->core.init(b->device, 1, b->fft_n);
         fresh->core.taps = b->taps;                    // the batch's stage taps hold for its new groups too
-        // the chained form's cores stay plain (its post-chain streams grow in run_chained); only the three-stage form
-        // gives a new group its own filter and post-chain streams
-        if (rc == CSDR_OK && b->pipelined && !b->chained) rc = fresh->core.pipelined_init();
+        // (a pipelined batch's new group gets its post-chain stream in run_chained)
         if (rc == CSDR_OK) rc = fresh->core.ensure((long)A.pending + 1);
         if (rc == CSDR_OK) { hip(hipMalloc((void **)&fresh->d_rows, sizeof(int))) && hip(hipMalloc((void **)&fresh->d_out_rows, sizeof(int))); }
         if (rc == CSDR_OK) rc = batch_plumbing(b, false, fresh.get());
@@ -184,7 +179,7 @@ static int batch_move_row(csdr_demod_batch *b, int channel, int new_stages, Appl
     if (rc == CSDR_OK) rc = csdr__fastfir_batch_copy_row(T.ff, tr, A.ff, r);
     if (rc == CSDR_OK) rc = T.pc.import_channel(tr, A.pc, r);
     if (rc == CSDR_OK && A.pending > 0)
-        hip(hipMemcpy(T.stage_now() + (size_t)tr * T.cap * 2, A.stage_now() + (size_t)r * A.cap * 2, (size_t)A.pending * 8,
+        hip(hipMemcpy(T.d_stage + (size_t)tr * T.cap * 2, A.d_stage + (size_t)r * A.cap * 2, (size_t)A.pending * 8,
                       hipMemcpyDeviceToDevice));
     if (rc == CSDR_OK) rc = apply(T, tr, cfg);
     const int muted = -1;
@@ -431,9 +426,11 @@ int csdr_demod_batch_commit(csdr_demod_batch *b)
     batch_order(b);                                    // heaviest post-chain first, and on the highest-priority stream
     return b->groups.size() > 1 ? batch_plumbing(b, true) : CSDR_OK;
 }
-/* Pipelined mode.  on != 0: a process call only enqueues on internal streams; in the caller's stream order the
- * INPUT buffer of call k has been consumed and the OUTPUT rows of call k-1 are complete after process call k+1
- * (everything after csdr_demod_batch_flush).  Results are identical to the strict mode. */
+/* Pipelined mode.  on != 0 (1, 2 and 3 mean the same): a process call only enqueues on internal streams -- the strict
+ * mode's schedule, one down-converter at a time and each group's filter in queue order behind it, carried across calls:
+ * the first group's next down-converter follows the last group's, the post-chains run in streams of their own
+ * (run_chained).  In the caller's stream order the INPUT buffer and the OUTPUT rows of call k are complete after process
+ * call k+1 (everything after csdr_demod_batch_flush).  Results are identical to the strict mode. */
 int csdr_demod_batch_set_pipelined(csdr_demod_batch *b, int on)
 {
     if (!b) return fail(CSDR_EINVAL, "bad handle");
@@ -445,25 +442,12 @@ int csdr_demod_batch_set_pipelined(csdr_demod_batch *b, int on)
         int rc = batch_plumbing(b, true);
         if (rc) return rc;
     }
-    // Two forms.  CHAINED (round 6, the default; on == 2 asks for it by name): the strict mode's schedule -- one
-    // down-converter at a time, each group's filter in queue order behind it -- carried across calls: the first group's next
-    // down-converter follows the last group's, the post-chains run in streams of their own and the caller joins a call behind
-    // the next call's launches.  Two streams per group, no second staging buffer.  1.65-1.68 ms per call of the C4 share, the
-    // strict mode's period, against 1.75-1.80 for THREE-STAGE (rounds 3-5; on == 3 or CSDR_PIPE_KIND=3): every group's
-    // down-converter at once, filter and post-chain on two more streams per group over double buffers.  A batch that has ever
-    // run the three-stage form keeps its cores' extra streams and stays with it.
-    static const int kind_env = getenv("CSDR_PIPE_KIND") ? atoi(getenv("CSDR_PIPE_KIND")) : 0;
-    bool plain = true;
-    for (auto &g : b->groups) plain = plain && !g->core.has_stage_streams();
-    const bool chained = on && plain && on != 3 && (on == 2 || kind_env != 3);
-    if (on && !chained) for (auto &g : b->groups) { int rc = g->core.pipelined_init(); if (rc) return rc; }
     for (auto &g : b->groups) {
-        g->prev_post = -1; g->prev_join = false;
+        g->prev_join = false;
         g->core.ch.post_busy[0] = g->core.ch.post_busy[1] = false;
     }
     b->have_last_dc = false;
     b->pipelined = on != 0;
-    b->chained = chained;
     return CSDR_OK;
 }
 /* stream-orders the caller's stream behind everything the batch has in flight (pipelined mode: the post-chain
@@ -472,7 +456,7 @@ int csdr_demod_batch_flush(csdr_demod_batch *b, void *stream)
 {
     if (!b) return fail(CSDR_EINVAL, "bad handle");
     if (!device_ok(b->device)) return CSDR_EHIP;
-    return batch_late_join(b, stream, true);
+    return batch_late_join(b, stream);
 }
 /* internal (csdr_demod_shard_process_shared): orders `stream` behind the batch's reads of the INPUT of its previous
  * call.  Strict mode: nothing to do (a process call joins the caller's stream itself).  Pipelined mode: the previous
@@ -483,7 +467,7 @@ int csdr__demod_batch_wait_input_free(csdr_demod_batch *b, void *stream)
     if (!b) return fail(CSDR_EINVAL, "bad handle");
     if (!b->pipelined) return CSDR_OK;
     if (!device_ok(b->device)) return CSDR_EHIP;
-    return batch_late_join(b, stream, false);
+    return batch_late_join(b, stream);
 }
 int csdr_demod_batch_set_freq(csdr_demod_batch *b, int channel, double freq)
 {
@@ -539,8 +523,8 @@ static long corun_wgs(int device, size_t oi)
     return wgs[oi > 1 ? 1 : 0];
 }
 
-// The chained pipeline's schedule (csdr_demod_batch_set_pipelined): one down-converter at a time, across calls; every
-// group's post-chain in a stream of its own, joined by the NEXT call.
+// The pipelined schedule (csdr_demod_batch_set_pipelined): one down-converter at a time, across calls; every group's
+// post-chain in a stream of its own, joined by the NEXT call.
 static int run_chained(csdr_demod_batch *b, ChainIn in, ChainOut out, hipStream_t caller)
 {
     int pr_lo = 0, pr_hi = 0;
@@ -559,7 +543,7 @@ static int run_chained(csdr_demod_batch *b, ChainIn in, ChainOut out, hipStream_
         csdr__downconvert_batch_set_wgs(k.dc, wgs);
         CSDR_HIP(hipStreamWaitEvent(g.stream, b->fork, 0));
         // the caller's stream catches up with the PREVIOUS call behind this call's fork event (the pipelined contract)
-        { const int rcj = g.late_join(caller, false); if (rcj) return rcj; }
+        { const int rcj = g.late_join(caller); if (rcj) return rcj; }
         // one down-converter at a time, across calls: behind the previous group's, the first behind the previous call's last
         hipEvent_t after = nullptr;
         if (oi > 0) after = b->groups[b->order[oi - 1]]->dc_done;
@@ -571,60 +555,39 @@ static int run_chained(csdr_demod_batch *b, ChainIn in, ChainOut out, hipStream_
         if (rc < 0 && !err) err = rc;
         CSDR_HIP(hipEventRecord(g.join, joined));
         g.prev_join = true;
-        g.prev_post = -1;
     }
     b->have_last_dc = !err;
     return err ? err : CSDR_OK;
 }
 
-// Strict mode and the three-stage pipeline.  Strict: the groups' down-converters run one after the other (each fills the
-// chip on its own) and what follows a group's down-converter overlaps the next group's.  Three-stage: all at once, the
-// overlap comes from the next call.  forked: the groups run on their own streams (several groups, or pipelined).
-static int run_groups(csdr_demod_batch *b, ChainIn in, ChainOut out, hipStream_t caller, bool forked, bool plain)
+// The strict schedule: the groups' down-converters run one after the other (each fills the chip on its own) and what
+// follows a group's down-converter overlaps the next group's.  Several groups run forked, each on its own stream; one
+// group runs on the caller's.
+static int run_strict(csdr_demod_batch *b, ChainIn in, ChainOut out, hipStream_t caller)
 {
-    const bool strict_multi = forked && !b->pipelined && plain && b->groups.size() > 1;
-    // strict mode: CSDR_CHAIN_DC_CHAINED=0 starts every group's down-converter at once (A/B)
-    static const bool dc_chained = !(getenv("CSDR_CHAIN_DC_CHAINED") && atoi(getenv("CSDR_CHAIN_DC_CHAINED")) == 0);
+    const size_t ng = b->groups.size();
+    const bool forked = ng > 1;
     int err = 0;
-    for (size_t oi = 0; oi < b->groups.size(); oi++) {
+    for (size_t oi = 0; oi < ng; oi++) {
         PlanGroup &g = *b->groups[b->order[oi]];
         ChainCore &k = g.core;
         hipStream_t st = forked ? g.stream : caller;
-        csdr__downconvert_batch_set_wgs(k.dc, strict_multi && oi > 0 ? corun_wgs(b->device, oi) : 0);
+        csdr__downconvert_batch_set_wgs(k.dc, oi > 0 ? corun_wgs(b->device, oi) : 0);
         if (forked) CSDR_HIP(hipStreamWaitEvent(st, b->fork, 0));
-        // pipelined: the caller's stream catches up with the PREVIOUS call only now, behind this call's fork
-        // event, so that this call's down-converter is not held back by it: previous input consumed, output
-        // rows of the call before that complete
-        if (b->pipelined) { const int rcj = g.late_join(caller, true); if (rcj) return rcj; }
         hipEvent_t prev_dc = oi > 0 ? (hipEvent_t)b->groups[b->order[oi - 1]]->dc_done : nullptr;
         in.d_in_rows = g.d_rows; out.d_out_rows = g.d_out_rows;
-        int rc;
-        if (k.has_stage_streams())
-            rc = k.step_pipelined(in, out, st, !b->pipelined ? prev_dc : nullptr, g.dc_done);
-        else
-        {
-            // strict mode, several groups: the LAST group's filter, S-meter, peaks and walk are the end of the call, and
-            // its S-meter -- which nothing in the call waits for -- goes to the first group's stream, long idle by then:
-            // 30 us less on the critical path.  (CSDR_CHAIN_SM_BORROW=0: in the group's own stream, in front of the peaks.)
-            static const bool borrow = !(getenv("CSDR_CHAIN_SM_BORROW") && atoi(getenv("CSDR_CHAIN_SM_BORROW")) == 0);
-            k.pc.sm_borrow = (borrow && forked && !b->pipelined && oi > 0 && oi + 1 == b->groups.size())
-                                 ? b->groups[b->order[0]]->stream : nullptr;
-            // ONE group (a single receiver, or receivers of one plan): the call is that group's walk from end to end, and
-            // the S-meter scan beside it on a side stream of its own is 6 % of a C2 / C5 call
-            k.pc.sm_own_side = borrow && !forked;
-            rc = k.step(in, out, st, forked && dc_chained ? prev_dc : nullptr, forked ? (hipEvent_t)g.dc_done : nullptr);
-            k.pc.sm_borrow = nullptr;
-        }
+        // several groups: the LAST group's filter, S-meter, peaks and walk are the end of the call, and its S-meter -- which
+        // nothing in the call waits for -- goes to the first group's stream, long idle by then: 30 us less on the critical path
+        k.pc.sm_borrow = oi > 0 && oi + 1 == ng ? b->groups[b->order[0]]->stream : nullptr;
+        // ONE group (a single receiver, or receivers of one plan): the call is that group's walk from end to end, and the
+        // S-meter scan beside it on a side stream of its own is 6 % of a C2 / C5 call
+        k.pc.sm_own_side = !forked;
+        const int rc = k.step(in, out, st, prev_dc, forked ? (hipEvent_t)g.dc_done : nullptr);
+        k.pc.sm_borrow = nullptr;
         if (rc < 0 && !err) err = rc;
         if (forked) {                                   // join even after an error: the caller's stream stays ordered
-            CSDR_HIP(hipEventRecord(g.join, st));       // the input has been consumed (+ filter and shift, strict mode)
-            if (b->pipelined) {                         // joined by the next call / flush
-                g.prev_join = true;
-                g.prev_post = k.ts.last_post;
-            } else {
-                CSDR_HIP(hipStreamWaitEvent(caller, g.join, 0));
-                if (k.ts.last_post >= 0) CSDR_HIP(hipStreamWaitEvent(caller, k.ts.ev_post[k.ts.last_post], 0));
-            }
+            CSDR_HIP(hipEventRecord(g.join, st));
+            CSDR_HIP(hipStreamWaitEvent(caller, g.join, 0));
         }
     }
     return err ? err : CSDR_OK;
@@ -645,14 +608,10 @@ static int demod_batch_run(csdr_demod_batch *b, const float *d_in, long long in_
         return fail(CSDR_ESTATE, "a csdr_demod_batch_set_input_rate failed half way (rows of one group decimate differently): call it again");
     if (!device_ok(b->device)) return CSDR_EHIP;
     hipStream_t caller = (hipStream_t)stream;
-    const bool forked = b->groups.size() > 1 || b->pipelined;
-    if (forked) CSDR_HIP(hipEventRecord(b->fork, caller));
-    bool plain = true;                                   // (an object that was ever pipelined keeps its three-stream cores)
-    for (auto &g : b->groups) plain = plain && !g->core.has_stage_streams();
+    if (b->groups.size() > 1 || b->pipelined) CSDR_HIP(hipEventRecord(b->fork, caller));      // the groups run on their own streams
     const ChainIn in{d_in, (long)in_stride, nullptr, n_per_channel, d_packets, pkt_len, blank};
     const ChainOut out{d_out, (long)out_stride, nullptr, stereo};
-    if (b->pipelined && b->chained && plain) return run_chained(b, in, out, caller);
-    return run_groups(b, in, out, caller, forked, plain);
+    return b->pipelined ? run_chained(b, in, out, caller) : run_strict(b, in, out, caller);
 }
 // the caller's blanker must be as wide as the chain and on its device: the mask has one row per receiver, and the
 // down-converter indexes the blanker's state and history by input row
@@ -709,7 +668,7 @@ int csdr_demod_batch_process_packets(csdr_demod_batch *b, const void *d_packets,
     // history halves alternate per call: in pipelined mode the down-converters of the PREVIOUS call (on the batch's own
     // streams) may still be reading them, and the caller's stream -- on which the blanker of this call runs -- has not
     // joined them yet (demod_batch_run does that, later)
-    if (b->pipelined) { const int rcj = batch_late_join(b, stream, false); if (rcj) return rcj; }
+    if (b->pipelined) { const int rcj = batch_late_join(b, stream); if (rcj) return rcj; }
     // FUSED (default): the blanker decides, the down-converter applies -- noiseblank_kernel leaves one bit per sample,
     // downconv_kernel<.., BLK> reads the datagram sample delay_n + 1 behind and zeroes it under the mask in its own
     // load.  No blanked copy of the input: 8 B written + 8 B read back per sample less, and one input stream less in
@@ -752,7 +711,7 @@ int csdr_demod_batch_process_blanked(csdr_demod_batch *b, const float *d_in, lon
     { const int rcs = batch_blanker_fits(b, nb); if (rcs) return rcs; }
     const long n = n_per_channel;
     // (the single-buffered mask, as in process_packets)
-    if (b->pipelined) { const int rcj = batch_late_join(b, stream, false); if (rcj) return rcj; }
+    if (b->pipelined) { const int rcj = batch_late_join(b, stream); if (rcj) return rcj; }
     { const int rcm = batch_mask_rows(b, n); if (rcm) return rcm; }
     int rc = csdr__noiseproc_batch_mask(nb, d_in, in_stride, nullptr, 0, 0, (int)n, b->d_mask, b->mask_cap,
                                         &b->blank.state, &b->blank.hist, stream);
@@ -787,14 +746,11 @@ int csdr__demod_batch_probe(csdr_demod_batch *b, double *us_out, double *bytes_o
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     return n;
 }
-/* internal (tests): the batch's pipelined form -- bit 0 pipelined, bit 1 the chained form, bit 2 some plan group has the
- * three-stage form's own filter and post-chain streams (then every call runs the three-stage schedule) */
+/* internal (tests): the batch's form -- 3 pipelined (bit 0 pipelined, bit 1 the chained schedule: the only one), 0 strict */
 int csdr__demod_batch_form(csdr_demod_batch *b)
 {
     if (!b) return fail(CSDR_EINVAL, "bad handle");
-    bool three = false;
-    for (auto &g : b->groups) three = three || g->core.has_stage_streams();
-    return (b->pipelined ? 1 : 0) | (b->chained ? 2 : 0) | (three ? 4 : 0);
+    return b->pipelined ? 3 : 0;
 }
 /* stage taps of a batch's receivers: see include/cutesdr_mi.h */
 int csdr_demod_batch_set_taps(csdr_demod_batch *b, int mask)

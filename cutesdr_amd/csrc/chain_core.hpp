@@ -12,8 +12,7 @@
 
 #pragma GCC visibility push(hidden)                     // the library's own: nothing here is part of the ABI
 namespace {
-// move the not-yet-filtered tail of every row to the front of the staging buffer (dst == src) or of the other
-// staging buffer (three-stage form)
+// move the not-yet-filtered tail of every row to the front of the staging buffer (dst == src)
 __global__ void shift_rows_kernel(float *dst, const float *src, long stride, int src_off, int count)
 {
     float2 *drow = reinterpret_cast<float2 *>(dst) + (long)blockIdx.x * stride;
@@ -24,14 +23,6 @@ __global__ void shift_rows_kernel(float *dst, const float *src, long stride, int
 }  // namespace
 
 namespace csdr {
-
-// CSDR_CHAIN_PIPELINE=1: the post-chain stage pipeline, off by default -- with four waves per channel one fused launch
-// already fills the chip and the extra launches cost more than the overlap returns
-inline bool post_pipe_on()
-{
-    static const bool on = getenv("CSDR_CHAIN_PIPELINE") && atoi(getenv("CSDR_CHAIN_PIPELINE")) != 0;
-    return on;
-}
 
 // one call's input: fp32 rows (d_in) or datagrams the down-converter decodes in its own loads (pk), optionally with the
 // noise blanker's mask to apply; d_in_rows = the input row each row of the core reads (nullptr: its own)
@@ -60,48 +51,6 @@ struct ChainCore {
     int taps = 0;
     float *d_tap1 = nullptr; long tap1_cap = 0; int tap1_n = 0;
 
-    // ---- Three-stage pipeline (csdr_demod_batch_set_pipelined(3)): three stages on three streams -- down-converter on the
-    // group's stream, filter (+ staging shift) on s_fir, post-chain on s_post -- with the staging and the filter
-    // output ping-ponging between two buffers each, so that stage i of call k+1 never waits for stage i+1 of
-    // call k: the down-converters of successive calls run back to back.
-    struct ThreeStage {
-        int device = 0;
-        hipStream_t s_fir = nullptr, s_post = nullptr;
-        float *d_stage2 = nullptr, *d_filt2 = nullptr;
-        Event ev_dc;                    // down-converter of the current call done
-        Event ev_stage_free[2];         // filter + shift have finished with staging buffer i
-        Event ev_fir[2];                // filter output buffer i written
-        Event ev_post[2];               // post-chain has finished with filter output buffer i
-        bool stage_busy[2] = {false, false}, post_pending[2] = {false, false};
-        int stage_cur = 0, filt_cur = 0, last_post = -1;
-        int init(int dev, size_t buffer_bytes)
-        {
-            if (s_post) return CSDR_OK;
-            device = dev;
-            CSDR_HIP(hipDeviceSynchronize());
-            int pr_lo = 0, pr_hi = 0;                            // the post-chain is the long pole of a call: highest priority
-            CSDR_HIP(hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi));
-            CSDR_HIP(stream_pool().get(device, pr_hi, &s_post, STREAM_STAGE_POST));
-            CSDR_HIP(stream_pool().get(device, pr_hi, &s_fir, STREAM_STAGE_FIR));
-            CSDR_HIP(ev_dc.create());
-            for (auto &e : ev_stage_free) CSDR_HIP(e.create());
-            for (auto &e : ev_fir) CSDR_HIP(e.create());
-            for (auto &e : ev_post) CSDR_HIP(e.create());
-            if (buffer_bytes > 0) {
-                if (!d_filt2) CSDR_HIP(hipMalloc((void **)&d_filt2, buffer_bytes));
-                if (!d_stage2) CSDR_HIP(hipMalloc((void **)&d_stage2, buffer_bytes));
-            }
-            stage_cur = 0;                                       // the pending samples sit in d_stage
-            return CSDR_OK;
-        }
-        ~ThreeStage()
-        {
-            if (d_filt2) (void)hipFree(d_filt2);
-            if (d_stage2) (void)hipFree(d_stage2);
-            if (s_post) stream_pool().put(device, s_post);
-            if (s_fir) stream_pool().put(device, s_fir);
-        }
-    } ts;
     // ---- Chained pipeline (csdr_demod_batch_set_pipelined, round 6): filter + shift stay in the down-converter's stream,
     // the post-chain goes to a second one; the filter's output alternates between d_filt and d_agc
     struct Chained {
@@ -116,30 +65,6 @@ struct ChainCore {
             return CSDR_OK;
         }
     } ch;
-    // ---- Post-chain stage pipeline (CSDR_CHAIN_PIPELINE=1): long calls run S-meter | AGC | demodulator as a pipeline
-    // of launches over burst groups
-    struct PostPipe {
-        int device = 0;
-        hipStream_t s_dem = nullptr, s_sm = nullptr;
-        Event ev_fork, ev_dem, ev_sm, ev_agc[8];
-        int init(int dev)
-        {
-            if (s_dem) return CSDR_OK;
-            device = dev;
-            CSDR_HIP(stream_pool().get(device, 0, &s_dem, STREAM_SIDE));
-            CSDR_HIP(stream_pool().get(device, 0, &s_sm, STREAM_SIDE));
-            CSDR_HIP(ev_fork.create());
-            CSDR_HIP(ev_dem.create());
-            CSDR_HIP(ev_sm.create());
-            for (auto &e : ev_agc) CSDR_HIP(e.create());
-            return CSDR_OK;
-        }
-        ~PostPipe()
-        {
-            if (s_dem) stream_pool().put(device, s_dem);
-            if (s_sm) stream_pool().put(device, s_sm);
-        }
-    } pp;
 
     ~ChainCore()
     {
@@ -155,31 +80,21 @@ struct ChainCore {
         if (!dc || !ff) return CSDR_EHIP;
         return pc.init(dev, nrows);
     }
-    int pipelined_init() { return ts.init(device, (size_t)rows * cap * 8); }
-    bool has_stage_streams() const { return ts.s_post != nullptr; }        // this core runs the three-stage form
-    float *stage_now() const { return ts.stage_cur ? ts.d_stage2 : d_stage; }   // where the pending samples sit
     int ensure(long need)
     {
         if (need <= cap) return CSDR_OK;
         need = (need + L + 1023) / 1024 * 1024;
         // growing the staging (rare): the pending samples may still be in flight on a non-blocking stream
         CSDR_HIP(hipDeviceSynchronize());
-        float *ns = nullptr, *nf = nullptr, *na = nullptr, *nf2 = nullptr, *ns2 = nullptr;
+        float *ns = nullptr, *nf = nullptr, *na = nullptr;
         CSDR_HIP(hipMalloc((void **)&ns, (size_t)rows * need * 8));
         CSDR_HIP(hipMalloc((void **)&nf, (size_t)rows * need * 8));
         CSDR_HIP(hipMalloc((void **)&na, (size_t)rows * need * 8));
-        if (has_stage_streams()) {
-            CSDR_HIP(hipMalloc((void **)&nf2, (size_t)rows * need * 8));
-            CSDR_HIP(hipMalloc((void **)&ns2, (size_t)rows * need * 8));
-        }
-        const float *cur = stage_now();
-        if (cur && pending > 0)
-            CSDR_HIP(hipMemcpy2D(ns, (size_t)need * 8, cur, (size_t)cap * 8, (size_t)pending * 8, rows,
+        if (d_stage && pending > 0)
+            CSDR_HIP(hipMemcpy2D(ns, (size_t)need * 8, d_stage, (size_t)cap * 8, (size_t)pending * 8, rows,
                                  hipMemcpyDeviceToDevice));
-        for (float *p : {d_stage, d_filt, d_agc, ts.d_filt2, ts.d_stage2}) if (p) (void)hipFree(p);
-        d_stage = ns; d_filt = nf; d_agc = na; ts.d_filt2 = nf2; ts.d_stage2 = ns2; cap = need;
-        ts.stage_cur = 0;
-        ts.stage_busy[0] = ts.stage_busy[1] = ts.post_pending[0] = ts.post_pending[1] = false;
+        for (float *p : {d_stage, d_filt, d_agc}) if (p) (void)hipFree(p);
+        d_stage = ns; d_filt = nf; d_agc = na; cap = need;
         return CSDR_OK;
     }
     // One pass of the chain over in.n input samples per row (demodulator.cpp:172-207), strict mode: everything in stream s.
@@ -209,7 +124,7 @@ struct ChainCore {
         int rc = csdr_fastfir_batch_process(ff, d_stage, cap, nb * L, d_filt, cap, s, 0);
         if (rc) return rc;
         if ((rc = post(d_filt, out, nb, s))) return rc;
-        if ((rc = shift_tail(d_stage, d_stage, nb * L, total - nb * L, s))) return rc;
+        if ((rc = shift_tail(nb * L, total - nb * L, s))) return rc;
         pending = total - nb * L;
         last_out = nb * L;
         return last_out;
@@ -232,14 +147,14 @@ struct ChainCore {
         const int total = pending + m, nb = total / L;
         last_out = 0;
         if (nb == 0) { pending = total; return 0; }
-        const int fc = post_pipe_on() ? 0 : ch.filt_cur;     // (the post-chain stage pipeline uses d_agc itself: one buffer)
+        const int fc = ch.filt_cur;
         ch.filt_cur ^= 1;
         float *fb = fc ? d_agc : d_filt;
         if (ch.post_busy[fc]) { CSDR_HIP(hipStreamWaitEvent(s, ch.ev_post_done[fc], 0)); ch.post_busy[fc] = false; }
         int rc = csdr_fastfir_batch_process(ff, d_stage, cap, nb * L, fb, cap, s, 0);
         if (rc) return rc;
         CSDR_HIP(hipEventRecord(ch.ev_filt, s));
-        if ((rc = shift_tail(d_stage, d_stage, nb * L, total - nb * L, s))) return rc;
+        if ((rc = shift_tail(nb * L, total - nb * L, s))) return rc;
         pending = total - nb * L;
         CSDR_HIP(hipStreamWaitEvent(sp, ch.ev_filt, 0));
         if ((rc = post(fb, out, nb, sp))) return rc;
@@ -249,118 +164,41 @@ struct ChainCore {
         last_out = nb * L;
         return last_out;
     }
-    // The same pass in the three-stage form: s = the group's stream (down-converter only).
-    int step_pipelined(const ChainIn &in, const ChainOut &out, hipStream_t s, hipEvent_t dc_after, hipEvent_t dc_done)
-    {
-        const int m = room_for(in.n);
-        if (m < 0) return m;
-        const int sc = ts.stage_cur;
-        float *stage = sc ? ts.d_stage2 : d_stage, *other = sc ? d_stage : ts.d_stage2;
-        if (dc_after) CSDR_HIP(hipStreamWaitEvent(s, dc_after, 0));
-        // the filter + shift of the call that last used this staging buffer must have finished with it
-        if (ts.stage_busy[sc]) { CSDR_HIP(hipStreamWaitEvent(s, ts.ev_stage_free[sc], 0)); ts.stage_busy[sc] = false; }
-        int rc = dc_launch(in, stage, s);
-        if (rc) return rc;
-        CSDR_HIP(hipEventRecord(ts.ev_dc, s));
-        if (dc_done) CSDR_HIP(hipEventRecord(dc_done, s));
-        const int total = pending + m, nb = total / L;
-        last_out = 0;
-        ts.last_post = -1;
-        if (nb == 0) { pending = total; return 0; }      // not a hop yet: the next call appends to the same buffer
-        const int fc = ts.filt_cur;
-        ts.filt_cur ^= 1;
-        float *fb = fc ? ts.d_filt2 : d_filt;
-        CSDR_HIP(hipStreamWaitEvent(ts.s_fir, ts.ev_dc, 0));
-        if (ts.post_pending[fc]) CSDR_HIP(hipStreamWaitEvent(ts.s_fir, ts.ev_post[fc], 0));
-        rc = csdr_fastfir_batch_process(ff, stage, cap, nb * L, fb, cap, ts.s_fir, 0);
-        if (rc) return rc;
-        CSDR_HIP(hipEventRecord(ts.ev_fir[fc], ts.s_fir));
-        // the tail moves to the front of the OTHER staging buffer
-        if ((rc = shift_tail(other, stage, nb * L, total - nb * L, ts.s_fir))) return rc;
-        CSDR_HIP(hipEventRecord(ts.ev_stage_free[sc], ts.s_fir));
-        ts.stage_busy[sc] = true;
-        ts.stage_cur ^= 1;
-        pending = total - nb * L;
-        CSDR_HIP(hipStreamWaitEvent(ts.s_post, ts.ev_fir[fc], 0));
-        if ((rc = post(fb, out, nb, ts.s_post))) return rc;
-        CSDR_HIP(hipEventRecord(ts.ev_post[fc], ts.s_post));
-        ts.post_pending[fc] = true;
-        ts.last_post = fc;
-        last_out = nb * L;
-        return last_out;
-    }
 
 private:
-    // what the three passes share: the decimated samples a call of n appends, with room made for them (< 0: error) ...
-    int room_for(int n)
-    {
-        const int m = csdr_downconvert_batch_out_count(dc, 0, n);
-        if (m < 0) return m;
-        const int rc = ensure((long)pending + m);
-        return rc ? rc : m;
-    }
-    // ... the down-converter of this call, appending to the pending samples of `stage` ...
-    int dc_launch(const ChainIn &in, float *stage, hipStream_t s)
-    {
-        return csdr__downconvert_batch_process_rows(dc, in.d_in, in.in_stride, in.d_in_rows, in.n, stage + 2 * (size_t)pending,
-                                                    cap, s, in.pk, in.pk_len, in.blank);
-    }
-    // ... and the move of the tail no hop has taken yet to the front of `dst`
-    int shift_tail(float *dst, const float *src, int from, int count, hipStream_t s)
+    // the move of the tail no hop has taken yet to the front of the staging rows
+    int shift_tail(int from, int count, hipStream_t s)
     {
         if (count <= 0) return CSDR_OK;
-        hipLaunchKernelGGL(shift_rows_kernel, dim3(rows), dim3(256), 0, s, dst, src, cap, from, count);
+        hipLaunchKernelGGL(shift_rows_kernel, dim3(rows), dim3(256), 0, s, d_stage, d_stage, cap, from, count);
         CSDR_HIP(hipGetLastError());
         return CSDR_OK;
     }
-    // S-meter, AGC and demodulator of nb bursts: one fused launch.  Optionally (long calls, CSDR_CHAIN_PIPELINE=1) the
-    // S-meter on its own stream and AGC -> demodulator pipelined over burst groups through d_agc.
+    // S-meter, AGC and demodulator of nb bursts: one fused launch
     int post(const float *filt, const ChainOut &out, int nb, hipStream_t s)
     {
         const int st = out.stereo ? PC_STEREO : 0;
-        // parameters set since the last call: applied HERE, on the stream every launch below is ordered behind (the optional
-        // stage pipeline forks to side streams; a patch kernel on one of them would not be ordered before the others)
+        // parameters set since the last call: applied HERE, on the stream every launch below is ordered behind
         { const int rcp = pc.patches.flush(s); if (rcp) return rcp; }
         if (taps & 4) {                 // PROFILE_3: the AGC's output through device memory
             int rc = pc.run(PC_DO_SMETER | PC_DO_AGC, filt, cap, d_agc, cap, nb, L, s, nullptr);
             if (rc) return rc;
             return pc.run(PC_DO_DEMOD | st, d_agc, cap, out.d_out, out.out_stride, nb, L, s, out.d_out_rows);
         }
-        if (nb < 16 || !post_pipe_on())
-            return pc.run(PC_DO_SMETER | PC_DO_AGC | PC_DO_DEMOD | st, filt, cap, out.d_out, out.out_stride, nb, L, s, out.d_out_rows);
-        int rc = pp.init(device);
-        if (rc) return rc;
-        const int G = 8;
-        CSDR_HIP(hipEventRecord(pp.ev_fork, s));
-        CSDR_HIP(hipStreamWaitEvent(pp.s_sm, pp.ev_fork, 0));
-        CSDR_HIP(hipStreamWaitEvent(pp.s_dem, pp.ev_fork, 0));
-        if ((rc = pc.run(PC_DO_SMETER, filt, cap, nullptr, 0, nb, L, pp.s_sm, nullptr))) return rc;
-        for (int g = 0; g < G; g++) {
-            const int b0 = (int)((long)nb * g / G), b1 = (int)((long)nb * (g + 1) / G);
-            if (b1 == b0) continue;
-            const size_t off = (size_t)b0 * L;
-            if ((rc = pc.run(PC_DO_AGC, filt + 2 * off, cap, d_agc + 2 * off, cap, b1 - b0, L, s, nullptr))) return rc;
-            CSDR_HIP(hipEventRecord(pp.ev_agc[g], s));
-            CSDR_HIP(hipStreamWaitEvent(pp.s_dem, pp.ev_agc[g], 0));
-            if ((rc = pc.run(PC_DO_DEMOD | st, d_agc + 2 * off, cap, out.d_out + (out.stereo ? 2 : 1) * off, out.out_stride,
-                             b1 - b0, L, pp.s_dem, out.d_out_rows))) return rc;
-        }
-        CSDR_HIP(hipEventRecord(pp.ev_dem, pp.s_dem));
-        CSDR_HIP(hipEventRecord(pp.ev_sm, pp.s_sm));
-        CSDR_HIP(hipStreamWaitEvent(s, pp.ev_dem, 0));
-        CSDR_HIP(hipStreamWaitEvent(s, pp.ev_sm, 0));
-        return CSDR_OK;
+        return pc.run(PC_DO_SMETER | PC_DO_AGC | PC_DO_DEMOD | st, filt, cap, out.d_out, out.out_stride, nb, L, s, out.d_out_rows);
     }
-    // the plain passes' first half: the down-converter of this call into the staging rows; returns what it appended
+    // both passes' first half: the down-converter of this call, appending to the pending samples of the staging rows, with
+    // room made for what it appends; returns that count (< 0: error)
     int step_dc(const ChainIn &in, hipStream_t s, hipEvent_t dc_after, hipEvent_t dc_done)
     {
-        if (has_stage_streams()) return fail(CSDR_ESTATE, "pipelined objects take step_pipelined()");
-        const int m = room_for(in.n);
+        const int m = csdr_downconvert_batch_out_count(dc, 0, in.n);
         if (m < 0) return m;
+        { const int rce = ensure((long)pending + m); if (rce) return rce; }
         // the down-converters of the groups run one after the other (each fills the chip on its own);
         // what follows a group's down-converter overlaps with the next group's
         if (dc_after) CSDR_HIP(hipStreamWaitEvent(s, dc_after, 0));
-        const int rc = dc_launch(in, d_stage, s);
+        const int rc = csdr__downconvert_batch_process_rows(dc, in.d_in, in.in_stride, in.d_in_rows, in.n,
+                                                            d_stage + 2 * (size_t)pending, cap, s, in.pk, in.pk_len, in.blank);
         if (rc) return rc;
         if (dc_done) CSDR_HIP(hipEventRecord(dc_done, s));
         return m;

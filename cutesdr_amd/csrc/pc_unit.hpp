@@ -259,11 +259,8 @@ struct PcUnit {
         // the peaks kernel and the walk
         bool sm_forked = false;
         if ((a.flags & PC_DO_SMETER) && (long)nbursts * burst >= 4096 && smeter_whole_call()) {
-            // (a stream of its own: measured 2.31 against 1.80 ms strict and 4.7-6.1 against 1.74 pipelined -- with one more
-            // stream per plan group the process goes past the hardware queues it is given; opt-in for diagnostics only)
-            static const bool side = getenv("CSDR_SM_SIDE") && atoi(getenv("CSDR_SM_SIDE")) != 0;
             const bool alone = !(a.flags & (PC_DO_AGC | PC_DO_DEMOD));
-            if ((side || sm_borrow || sm_own_side) && !alone) {
+            if ((sm_borrow || sm_own_side) && !alone) {
                 if (!sm_borrow && !s_side) CSDR_HIP(hipStreamCreateWithFlags(&s_side, hipStreamNonBlocking));
                 if (!ev_side_fork) {
                     CSDR_HIP(hipEventCreateWithFlags(&ev_side_fork, hipEventDisableTiming));

@@ -14,13 +14,13 @@
 // for every object the process makes.  (An idle pooled stream may still have work of its former owner in flight: a
 // stream is in-order, the new owner's work queues behind it.)
 namespace csdr {
-// A stream also keeps the ROLE it was created for (a plan group's stream, a chained pipeline's post-chain stream, the
-// three-stage pipeline's filter / post streams ...): the streams of one priority are not interchangeable -- a strict object
+// A stream also keeps the ROLE it was created for (a plan group's stream, the pipelined form's post-chain stream): the
+// streams of one priority are not interchangeable -- a strict object
 // whose first group ran on a stream that had been created as a post-chain stream took 2.14-2.32 ms per C4 call instead of
 // 1.56 (tools/experiments/r6_repro_mode2.py: every second strict object after a pipelined one, by the order in which the
 // pool handed the streams out).  With the role in the key an object of either mode gets, role by role, the streams the first
 // object of that mode created.
-enum StreamRole { STREAM_GROUP = 0, STREAM_POST = 1, STREAM_STAGE_POST = 2, STREAM_STAGE_FIR = 3, STREAM_SIDE = 4 };
+enum StreamRole { STREAM_GROUP = 0, STREAM_POST = 1 };
 struct StreamPool {
     std::mutex m;
     std::map<std::tuple<int, int, int>, std::vector<hipStream_t>> idle;      // (device, priority, role) -> streams

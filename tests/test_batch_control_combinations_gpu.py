@@ -1,5 +1,5 @@
 """A committed batch whose control-plane features meet: SetDemod that moves a receiver or changes it in place, stage taps,
-the chained and the three-stage pipelined forms, set_input_rate, set_input_rows and the datagram form with the blanker.
+the pipelined (chained) form, set_input_rate, set_input_rows and the datagram form with the blanker.
 The other files check each feature alone.  Here they run together, and every receiver follows its own fp64 oracle
 CDemodulator, which gets the same calls at the same stream positions.
 
@@ -9,7 +9,7 @@ Bounds, all existing ones:
   * behind a same-mode SetDemod, a retune, a new input row or an input-rate switch: the rule of
     test_control_plane_gpu.py (1e-3 FM / 5e-4 for eight bursts, then the steady bound);
   * stage taps: the bounds of test_chain_taps_gpu.py::test_batch_taps_equal_the_single_receivers;
-  * pipelined forms against the strict mode: the same words."""
+  * the pipelined form against the strict mode: the same words."""
 import concurrent.futures as cf
 import ctypes as C
 import functools
@@ -49,7 +49,7 @@ def _signal(kind, variant, n, fs):
 
 
 def _form(b):
-    """csdr__demod_batch_form: bit 0 pipelined, bit 1 chained, bit 2 some plan group has the three-stage streams"""
+    """csdr__demod_batch_form: 3 for a pipelined batch (bit 0 pipelined, bit 1 chained), 0 for a strict one"""
     from cutesdr_amd._capi import lib
     L = lib()
     L.csdr__demod_batch_form.restype = C.c_int
@@ -332,12 +332,12 @@ def test_set_pipelined_is_refused_while_taps_are_on(oracle):
     rig.check(b.process(x), rig.oracle_outs(x), ("chained", 2))
 
 
-@pytest.mark.parametrize("form", [1, 3], ids=["chained", "three-stage"])
+@pytest.mark.parametrize("form", [1], ids=["chained"])
 def test_pipelined_form_survives_moves(form):
     """A pipelined batch and a strict twin fed the same calls and changes: a move that opens a group (USB -> AM), one into
     the muted row it left (AM -> USB, which drops the group), an in-place change (FM -> USB), an input-rate switch that
-    moves a receiver, and back.  The chained form stays chained -- no plan group gets the three-stage form's streams --
-    the three-stage form stays three-stage, and every output word equals the twin's."""
+    moves a receiver, and back.  The pipelined batch stays pipelined, the strict twin strict, and every output word equals
+    the twin's."""
     import cutesdr_amd as ca
     C_ = len(NAMES8)
     groups_before_rate = None
@@ -351,7 +351,7 @@ def test_pipelined_form_survives_moves(form):
         for c in range(C_):
             b.set_freq(c, -100e3 - 500.0 * c)
     pipe.set_pipelined(form)
-    want_form = 3 if form == 1 else 5
+    want_form = {0: 0, 1: 3}[form]
     assert _form(pipe) == want_form and _form(strict) == 0
     # (as in test_taps_follow_receivers_that_move: a new group, a muted row, a dropped group; then an in-place change that
     # the switch to 3.2 MSPS turns into a move, and back)
@@ -382,10 +382,10 @@ def test_pipelined_form_survives_moves(form):
 
 
 @pytest.mark.parametrize("case", ["AM-SAM", "USB-LSB", "FM-USB"])
-@pytest.mark.parametrize("form", [0, 1, 3], ids=["strict", "chained", "three-stage"])
+@pytest.mark.parametrize("form", [0, 1], ids=["strict", "chained"])
 def test_in_place_changes_while_a_call_is_in_flight(oracle, form, case):
     """64 receivers, calls of 64 windows (1.28 M samples) issued with process_ptr and never waited for.  Right after call 1
-    returns -- its launches still on the device in the pipelined forms -- three receivers get a same-mode SetDemod with
+    returns -- its launches still on the device in the pipelined form -- three receivers get a same-mode SetDemod with
     another AGC knee and decay, then a mode change that keeps their row: AM -> SAM, USB -> LSB, or FM -> USB (a new
     decimator plan of the same stage count: its histories are reset).  Call 1 must be the oracle's with the OLD
     parameters, call 2 with the new ones, and every other receiver untouched.  The strict mode is the control."""
@@ -424,7 +424,7 @@ def test_in_place_changes_while_a_call_is_in_flight(oracle, form, case):
             assert b.group_count() == g0                     # nobody moved
     b.flush()
     ca.sync()
-    assert _form(b) == {0: 0, 1: 3, 3: 5}[form]
+    assert _form(b) == {0: 0, 1: 3}[form]
     # the oracle side, call by call, the changes between calls 1 and 2
     ghost = {}
     for k in range(calls):
@@ -554,7 +554,7 @@ def _sweep(ca, oracle, seed, form, stereo, packets=False):
 
 
 @pytest.mark.parametrize("stereo", [False, True], ids=["mono", "stereo"])
-@pytest.mark.parametrize("form", [0, 1, 3], ids=["strict", "chained", "three-stage"])
+@pytest.mark.parametrize("form", [0, 1], ids=["strict", "chained"])
 @pytest.mark.parametrize("seed", range(6))
 def test_seeded_control_sequences(oracle, seed, form, stereo):
     import cutesdr_amd as ca

@@ -378,11 +378,22 @@ def test_chain_words_do_not_depend_on_how_the_stream_is_cut():
         assert np.abs(mtr - meters[0]).max() <= 1e-3
 
 
-@pytest.mark.parametrize("form", [1, 3], ids=["chained", "three-stage"])
+def _batch_form(b):
+    """csdr__demod_batch_form: 3 for a pipelined batch, 0 for a strict one"""
+    import ctypes as C
+    from cutesdr_amd._capi import lib
+    L = lib()
+    L.csdr__demod_batch_form.restype = C.c_int
+    L.csdr__demod_batch_form.argtypes = [C.c_void_p]
+    return L.csdr__demod_batch_form(b.h)
+
+
+@pytest.mark.parametrize("form", [1, 3], ids=["chained", "on3"])
 def test_pipelined_mode_gives_the_strict_mode_results(form):
     """csdr_demod_batch_set_pipelined: the post-chain of call k overlaps the down-converter of call k+1 on
     internal streams; six calls issued back to back without any host synchronisation, one flush at the end --
-    every output word equals the strict mode's.  Both forms: the chained one (the default) and the three-stage one."""
+    every output word equals the strict mode's.  on = 3, which once named another pipelined form, is still accepted and
+    selects the same one."""
     import cutesdr_amd as ca
     C, fs, n, calls = 12, 2e6, 19968 * 8, 6
     names = ["AM", "FM", "USB", "SAM"]
@@ -400,6 +411,7 @@ def test_pipelined_mode_gives_the_strict_mode_results(form):
             b.set_freq(c, -100e3 - 700.0 * c)
         if pipelined:
             b.set_pipelined(form)
+            assert _batch_form(b) == 3
         cap = n // 8
         din = ca.DeviceBuffer(x.nbytes)
         dout = ca.DeviceBuffer(4 * C * cap * calls)

@@ -172,7 +172,7 @@ def _many(rig, entries, batches=None):
     return sts
 
 
-@pytest.mark.parametrize("form", [0, 1, 3], ids=["strict", "chained", "three-stage"])
+@pytest.mark.parametrize("form", [0, 1], ids=["strict", "chained"])
 def test_new_edges_for_every_receiver_of_a_committed_batch(oracle, form):
     """48 receivers of mixed AM / SAM / FM / USB / CWL in four plan groups on three shared input rows: three calls, one
     set_demod_many that gives every receiver new edges (same modes), three more calls -- every receiver against its own
@@ -196,7 +196,7 @@ def test_new_edges_for_every_receiver_of_a_committed_batch(oracle, form):
         x = np.stack([s[k * n:(k + 1) * n] for s in src] + [np.zeros(n, dtype=np.complex64)] * (Cn - 3))
         got = rig.b.process(x)
         rig.check(got, rig.oracle_outs([x[rows[c]] for c in range(Cn)]), ("call", k))
-    assert _form(rig.b) == {0: 0, 1: 3, 3: 5}[form]
+    assert _form(rig.b) == {0: 0, 1: 3}[form]
 
 
 def test_a_call_that_mixes_same_mode_changes_in_place_changes_and_a_mover(oracle):
@@ -236,7 +236,7 @@ def test_a_call_that_mixes_same_mode_changes_in_place_changes_and_a_mover(oracle
         assert [len(a) for a in tw] == [len(a) for a in got], k
 
 
-@pytest.mark.parametrize("form", [1, 3], ids=["chained", "three-stage"])
+@pytest.mark.parametrize("form", [1], ids=["chained"])
 def test_set_demod_many_reaches_the_next_call_not_the_one_in_flight(form):
     import cutesdr_amd as ca
     Cn = 48
