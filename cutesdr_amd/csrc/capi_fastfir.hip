@@ -156,16 +156,18 @@ static void build_perm(csdr_fastfir_batch *b)
             for (int e = 0; e < 2; e++)
                 b->perm[(j * T + t) * 2 + e] = fastfir_bin_of(b->log2n, t, 2 * j + e);
     b->perm2.clear();
+    // (the pipelined kernel's two orders with the rotation of its shared pass twiddles composed in, fastfir2_slot_bin:
+    // host design, device design, re-commits and copy_row all go through these two tables)
     {
         b->perm2.resize(b->n);
         for (int j = 0; j < 16; j++)
             for (int t = 0; t < T; t++)
-                for (int e = 0; e < 2; e++) b->perm2[(j * T + t) * 2 + e] = fastfir2_bin_of(b->log2n, t, j, e);
+                for (int e = 0; e < 2; e++) b->perm2[(j * T + t) * 2 + e] = fastfir2_slot_bin(b->log2n, t, j, e);
     }
     b->permg.resize(b->n);
     for (int i = 0; i < 8; i++)
         for (int t = 0; t < T; t++)
-            for (int c = 0; c < 4; c++) b->permg[(i * T + t) * 4 + c] = fastfir2_gain_bin_of(b->log2n, t, i, c);
+            for (int c = 0; c < 4; c++) b->permg[(i * T + t) * 4 + c] = fastfir2_gain_slot_bin(b->log2n, t, i, c);
 }
 
 static int upload_response(csdr_fastfir_batch *b, int slot, const std::vector<cd> &H)

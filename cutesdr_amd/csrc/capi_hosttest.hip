@@ -61,6 +61,12 @@ int csdr__host_fastfir_gains(int n, double flo, double fhi, double off, double f
 }
 int csdr__host_fastfir2_bin_of(int log2n, int t, int j, int e) { return fastfir2_bin_of(log2n, t, j, e); }
 int csdr__host_fastfir2_gain_bin_of(int log2n, int t, int i, int c) { return fastfir2_gain_bin_of(log2n, t, i, c); }
+// the same two orders composed with the rotation of the shared pass twiddles (K1_TWSHARE): the slot -> bin maps the uploads
+// are built from, the rotation alone, and the build flag
+int csdr__host_fastfir2_slot_bin(int log2n, int t, int j, int e) { return fastfir2_slot_bin(log2n, t, j, e); }
+int csdr__host_fastfir2_gain_slot_bin(int log2n, int t, int i, int c) { return fastfir2_gain_slot_bin(log2n, t, i, c); }
+void csdr__host_fastfir2_twshare_shift(int log2n, int t, int *inner, int *outer) { fastfir2_twshare_shift(log2n, t, inner, outer); }
+int csdr__host_fastfir2_twshare(void) { return fastfir2_twshare(); }
 
 void csdr__host_dit_head4_gain(int sign, const float *x4, const float *g4, float *out4)
 {

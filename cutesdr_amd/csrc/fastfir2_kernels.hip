@@ -45,8 +45,15 @@ namespace csdr {
 #ifndef K1_REALGAIN
 #define K1_REALGAIN 1       // 0: the 16384-point kernel on complex H whatever the responses are (A/B against the parent form)
 #endif
+#ifndef K1_TWSHARE
+#define K1_TWSHARE 2        // N = 16384 only (both of its kernels).  1: rows k1 and 32 - k1 of F2 / I2 share one pass twiddle (16 reads per
+                            // pass instead of 31); 2: also rows k0 and 16 - k0 of the outer pass (8 twiddle powers per column instead of 15); 0: the
+                            // instruction stream and the upload order of the build before it (kernel and fastfir2_slot_bin together)
+#endif
 #ifndef K1_TWREG
-#define K1_TWREG 0          // real-gain kernel: pass twiddles of F2 / I2 that stay in registers (0 ... 3 fit; HISTORY.md)
+#define K1_TWREG (K1_TWSHARE >= 2 ? 16 : 0)   // real-gain kernel: pass twiddles k1 = 1 ... of F2 / I2 that stay in registers.  With
+                            // K1_TWSHARE = 2 all sixteen the passes use fit (252 VGPRs, no scratch) and none is read from LDS; with
+                            // 0 / 1 three fit and none measured better than noise (HISTORY.md)
 #endif
 #ifndef K1_HREG4K
 #define K1_HREG4K 4         // ... at N = 4096, whose outer pass (eight columns of four points) keeps more values live
@@ -89,6 +96,40 @@ namespace csdr {
 __device__ __forceinline__ void keep_alive(v4f v) { asm volatile("" ::"v"(v)); }
 #endif
 
+// K1_TWSHARE.  The table entry of row k1 and column sn is W_1024^(sn k1), and W_1024^(sn (32 - k1)) = W_32^sn conj(W_1024^(sn k1)):
+// rows 17 ... 31 of F2 take conj(twiddle 32 - k1) and are then W_32^(-sn) off, which F3 -- a transform over sn -- turns into a
+// circular shift of its 32 outputs by one bin (index j of such a row holds bin j - 1).  No instruction looks at what bin a
+// register holds; only the upload order of H / the gains does (fastfir2_slot_bin).  I1 returns such a row times
+// conj(W_32^sn), which with twiddle 32 - k1 UNconjugated is the conjugate twiddle I2 needs.  Tail group i of F2 and head
+// group bitrev3(i) of I2 hold the rows k1 = i + 8 {0, 1, 2, 3}: groups i and 8 - i run on the same four twiddles.  The groups
+// are walked in the order 0, 4, (1, 7), (2, 6), (3, 5) -- step s is group tws_group(s) -- on twiddle SETS: set 0 = rows {8, 16},
+// set 1 = {4, 12}, set 1 + m = {m, m + 8, 8 - m, 16 - m} for the pair (m, 8 - m).
+constexpr int tws_group(int step) { return step < 2 ? 4 * step : ((step & 1) ? 8 - step / 2 : step / 2); }
+constexpr int tws_set(int step) { return step < 2 ? step : 1 + step / 2; }
+constexpr bool tws_opens(int step) { return step < 2 || (step & 1) == 0; }          // the step is the first of its set
+constexpr int tws_row(int set, int slot)                                             // table row in `slot` of `set` (0: none)
+{
+    if (set < 2) return slot < 2 ? 8 - 4 * set + 8 * slot : 0;
+    const int m = set - 1;
+    return slot == 0 ? m : (slot == 1 ? m + 8 : (slot == 2 ? 8 - m : 16 - m));
+}
+constexpr int tws_row_of(int k1) { return k1 <= 16 ? k1 : 32 - k1; }                 // the table row that serves row k1
+constexpr int tws_set_of(int k1)
+{
+    const int r = tws_row_of(k1) & 7;
+    return r == 0 ? 0 : (r == 4 ? 1 : 1 + (r < 4 ? r : 8 - r));
+}
+constexpr int tws_slot_of(int k1)
+{
+    for (int slot = 0; slot < 4; slot++)
+        if (tws_row(tws_set_of(k1), slot) == tws_row_of(k1)) return slot;
+    return -1;
+}
+static_assert(K1_TWSHARE >= 0 && K1_TWSHARE <= 2 && K1_TWREG >= 0 && K1_TWREG <= (K1_TWSHARE ? 16 : 31), "K1_TWSHARE / K1_TWREG");
+static_assert(tws_group(2) == 1 && tws_group(3) == 7 && tws_group(7) == 5 && tws_set(7) == 4 && tws_set_of(31) == 2 &&
+              tws_slot_of(24) == 0 && tws_slot_of(16) == 1 && tws_slot_of(20) == 1 && tws_slot_of(25) == 2 && tws_slot_of(23) == 1,
+              "twiddle sets of K1_TWSHARE");
+
 // (N = 2048 likewise: FOUR blocks of one wave each, and a block's barriers are wave barriers.)
 // N = 4096 runs TWO blocks side by side in one workgroup: a block of 4096 points is 128 threads and 43 KB of LDS, three
 // workgroups -- six waves -- per CU, against the eight (two per SIMD) the schedule below is made for.  Two "virtual
@@ -118,6 +159,11 @@ __device__ __forceinline__ void fastfir_os2_body(const FastFirArgs a)
     constexpr int HALF = R0 / 2;
     constexpr int VW = K1Cfg<LOG2N>::VW;
     constexpr int HREG = RG ? 0 : (LOG2N == 12 ? K1_HREG4K : (LOG2N == 11 ? K1_HREG2K : K1_HREG));   // resident float4 of H
+    // The 16384-point kernels only.  The smaller sizes keep a twiddle per row and with it their former words: with the inner
+    // step at N = 2048 (whose filter words then differ in the last bits; its error stays 1.1e-7 of max|x|) a SAM
+    // receiver restarted inside tests/test_batch_control_combinations_gpu.py::test_seeded_control_sequence_on_datagrams_with_
+    // the_blanker came out 1.0e-2 / 7.8e-3 of full scale off in its first two bursts, bound 1e-3 (HISTORY.md, "Shared twiddles")
+    constexpr bool TWS = K1_TWSHARE >= 1 && LOG2N == 14;
     constexpr int TWREG = RG ? K1_TWREG : 0;      // pass twiddles k1 = 1 ... TWREG of F2 / I2 that stay in registers
     static_assert(R0 == 16 || R0 == 8 || R0 == 4 || R0 == 2, "the grouped outer pass is written for N = 2048 ... 16384");
     // a block of 2048 points is ONE wave: its two "workgroup" barriers are wave barriers (the four blocks of a workgroup
@@ -198,10 +244,14 @@ __device__ __forceinline__ void fastfir_os2_body(const FastFirArgs a)
         }
     };
     load_w1();
-    v2f pw[G][R0];
+    // (K1_TWSHARE = 2, N = 16384: W_N^(n2 (16 - k0)) = W_1024^n2 conj(W_N^(n2 k0)) -- rows 9 ... 15 of F1 take conj(power 16 - k0),
+    // which leaves the whole 1024-point sub-transform one bin on, I3 takes the same power unconjugated: powers 1 ... 8 only)
+    constexpr bool OUTER_SHARE = K1_TWSHARE >= 2 && R0 == 16;
+    constexpr int PWN = OUTER_SHARE ? R0 / 2 + 1 : R0;
+    v2f pw[G][PWN];
     if constexpr (R0 > 2) {
 #pragma unroll
-        for (int e = 0; e < G; e++) twiddle_powers<R0>(opaque(w1[e]), pw[e]);
+        for (int e = 0; e < G; e++) twiddle_powers<PWN>(opaque(w1[e]), pw[e]);
     }
 
     // H: float4 j of this thread (fastfir2_bin_of) multiplies in F3's tail group j / 2.  The first K1_HREG of the
@@ -294,7 +344,10 @@ __device__ __forceinline__ void fastfir_os2_body(const FastFirArgs a)
                         dit_tail<i, R0, +1>(y[1]);
                         static_for<0, 4>([&](auto P) {
                             constexpr int k0 = i + 4 * P.value;
-                            if constexpr (k0 != 0) {
+                            if constexpr (OUTER_SHARE && k0 > R0 / 2) {
+                                y[0][k0] = cmul_conj(y[0][k0], pw[0][R0 - k0]);
+                                y[1][k0] = cmul_conj(y[1][k0], pw[1][R0 - k0]);
+                            } else if constexpr (k0 != 0) {
                                 y[0][k0] = cmul(y[0][k0], pw[0][k0]);
                                 y[1][k0] = cmul(y[1][k0], pw[1][k0]);
                             }
@@ -406,6 +459,49 @@ __device__ __forceinline__ void fastfir_os2_body(const FastFirArgs a)
             // tail group i finishes k1 = i, i+8, i+16, i+24: twiddle, store (one group behind).  H[k] comes from
             // L2 (what is not resident: K1_HREG), at most two loads per tail group (a burst of sixteen held the wave for
             // ~500 cycles of issue alone), in flight from here to the multiply in F3
+            if constexpr (TWS) {
+            // (K1_TWSHARE: the groups in the order tws_group, a twiddle set read one step ahead of the first group it serves;
+            // the H fetches keep their order, two per step)
+            v2f tw[5][4];
+            auto load_set = [&](auto S) {
+                static_for<0, 4>([&](auto Q) {
+                    constexpr int row = tws_row(S.value, Q.value);
+#ifdef ABL_TW
+                    if constexpr (row != 0) tw[S.value][Q.value] = twabl;
+#else
+                    if constexpr (row != 0) tw[S.value][Q.value] = pass_tw(std::integral_constant<int, row>{});
+#endif
+                });
+            };
+            load_set(std::integral_constant<int, 0>{});
+            CSDR_SB();
+            CSDR_STAMP(8);                             // F2 middle stage
+            static_for<0, 9>([&](auto St) {
+                constexpr int s = St.value;
+                if constexpr (s < 7 && tws_opens(s + 1)) load_set(std::integral_constant<int, tws_set(s + 1)>{});
+                if constexpr (s < 8) {
+                    constexpr int i = tws_group(s);
+#ifdef ABL_H
+                    if constexpr (!RG) { hv[2 * s] = habl; hv[2 * s + 1] = habl; }
+#else
+                    if constexpr (!RG && 2 * s >= HREG) hv[2 * s] = buf_load16(r_h, t * 16, (2 * s) * (T * 16));
+                    if constexpr (!RG && 2 * s + 1 >= HREG) hv[2 * s + 1] = buf_load16(r_h, t * 16, (2 * s + 1) * (T * 16));
+#endif
+                    dit_tail<i, 32, +1>(x);
+                    static_for<0, 4>([&](auto P) {
+                        constexpr int k1 = i + 8 * P.value;
+                        if constexpr (k1 != 0 && k1 <= 16) x[k1] = cmul(x[k1], tw[tws_set_of(k1)][tws_slot_of(k1)]);
+                        if constexpr (k1 > 16) x[k1] = cmul_conj(x[k1], tw[tws_set_of(k1)][tws_slot_of(k1)]);
+                    });
+                }
+                if constexpr (s > 0)
+                    static_for<0, 4>([&](auto P) {
+                        constexpr int k1 = tws_group(s - 1) + 8 * P.value;
+                        lds_st8(col + 34 * k1, x[k1]);
+                    });
+                CSDR_SB();
+            });
+            } else {
             v2f tw[2][4];
 #ifdef ABL_TW
             static_for<1, 4>([&](auto P) { tw[0][P.value] = twabl; });
@@ -442,6 +538,7 @@ __device__ __forceinline__ void fastfir_os2_body(const FastFirArgs a)
                     });
                 CSDR_SB();
             });
+            }
         }
         CSDR_STAMP(2);                                 // F2
         // F2 -> F3 stays inside the half-wave that owns sub-transform sb
@@ -522,6 +619,39 @@ __device__ __forceinline__ void fastfir_os2_body(const FastFirArgs a)
         // ================= I2: conj twiddle, radix-32 DIT inverse =================
         CSDR_PRIO(0);
         {
+            if constexpr (TWS) {
+            // points of the head group of step s (g = bitrev3(tws_group(s)): rows k1 = i, i + 16, i + 8, i + 24 at positions
+            // 4g ... 4g + 3) and the twiddle set the step opens, two steps ahead of the butterflies; rows up to 16 take the
+            // conjugate twiddle, rows from 17 twiddle 32 - k1 as it is
+            v2f tw[5][4];
+            auto fetch = [&](auto St) {
+                constexpr int s = St.value, g = bitrev<8>(tws_group(s));
+                static_for<0, 4>([&](auto Q) {
+                    constexpr int r = 4 * g + Q.value;
+                    x[r] = lds_ld8(col + 34 * bitrev<32>(r));
+                });
+                if constexpr (tws_opens(s))
+                    static_for<0, 4>([&](auto Q) {
+                        constexpr int row = tws_row(tws_set(s), Q.value);
+#ifdef ABL_TW
+                        if constexpr (row != 0) tw[tws_set(s)][Q.value] = twabl;
+#else
+                        if constexpr (row != 0) tw[tws_set(s)][Q.value] = pass_tw(std::integral_constant<int, row>{});
+#endif
+                    });
+            };
+            static_for<0, 2>(fetch);
+            CSDR_SB();
+            static_for<0, 8>([&](auto St) {
+                constexpr int s = St.value, i = tws_group(s), g = bitrev<8>(i);
+                if constexpr (s + 2 < 8) fetch(std::integral_constant<int, s + 2>{});
+                constexpr int ka = i == 0 ? 8 : i, kb = i + 16, kc = i + 8, kd = i + 24;      // (group 0: position 0 is plain)
+                dit_head4_seltw<g, 32, -1, i == 0, (ka <= 16), (kb <= 16), (kc <= 16), (kd <= 16)>(
+                    x, tw[tws_set_of(ka)][tws_slot_of(ka)], tw[tws_set_of(kb)][tws_slot_of(kb)],
+                    tw[tws_set_of(kc)][tws_slot_of(kc)], tw[tws_set_of(kd)][tws_slot_of(kd)]);
+                if constexpr ((s & 1) == 1) CSDR_SB();
+            });
+            } else {
             v2f tw[32];
             // points and twiddles of head group g, two groups ahead of the butterflies
             auto fetch = [&](auto Gg) {
@@ -546,6 +676,7 @@ __device__ __forceinline__ void fastfir_os2_body(const FastFirArgs a)
                 dit_head4_conjtw<g, 32, -1, g == 0>(x, tw[4 * g], tw[4 * g + 1], tw[4 * g + 2], tw[4 * g + 3]);
                 if constexpr ((g & 1) == 1) CSDR_SB();
             });
+            }
             dit_single<8, 32, -1>(x);
             CSDR_SB();
             static_for<0, 9>([&](auto I) {
@@ -582,12 +713,20 @@ __device__ __forceinline__ void fastfir_os2_body(const FastFirArgs a)
             if constexpr (R0 > 2) {
                 if constexpr (!W1_RESIDENT) load_w1();
 #pragma unroll
-                for (int e = 0; e < G; e++) twiddle_powers<R0>(opaque(w1[e]), pw[e]);     // while the reads are in flight
+                for (int e = 0; e < G; e++) twiddle_powers<PWN>(opaque(w1[e]), pw[e]);     // while the reads are in flight
                 CSDR_SB();
                 static_for<0, (R0 >= 8 ? R0 / 4 : 1)>([&](auto Gg) {
                     constexpr int g = Gg.value;
                     static_for<0, G>([&](auto E) {
                         constexpr int e = E.value;
+                        if constexpr (OUTER_SHARE) {
+                            // position 4g + q holds row k0 = bitrev(4g + q): rows above R0 / 2 take power R0 - k0 as it is
+                            constexpr int ka = bitrev<R0>(4 * g), kb = bitrev<R0>(4 * g + 1), kc = bitrev<R0>(4 * g + 2), kd = bitrev<R0>(4 * g + 3);
+                            constexpr int H0 = R0 / 2;
+                            dit_head4_seltw<g, R0, -1, g == 0, (ka <= H0), (kb <= H0), (kc <= H0), (kd <= H0)>(
+                                y[e], pw[e][ka <= H0 ? ka : R0 - ka], pw[e][kb <= H0 ? kb : R0 - kb],
+                                pw[e][kc <= H0 ? kc : R0 - kc], pw[e][kd <= H0 ? kd : R0 - kd]);
+                        } else
                         dit_head4_conjtw<g, R0, -1, g == 0>(y[e], pw[e][bitrev<R0>(4 * g)], pw[e][bitrev<R0>(4 * g + 1)],
                                                             pw[e][bitrev<R0>(4 * g + 2)], pw[e][bitrev<R0>(4 * g + 3)]);
                     });
@@ -791,6 +930,33 @@ int fastfir2_bin_of(int log2n, int t, int j, int e)
 int fastfir2_gain_bin_of(int log2n, int t, int i, int c)
 {
     return fastfir2_bin_of(log2n, t, 2 * i + (c >> 1), c & 1);
+}
+
+int fastfir2_twshare() { return K1_TWSHARE; }
+// K1_TWSHARE: the two orders above say where a bin's multiplier sits when every row runs on its own twiddle.  A row of F3
+// that ran on a shared one (k1 = t & 31 from 17 up, N = 16384) has its 32 outputs one bin on: index k2 holds bin
+// k2 - *inner (mod 32).  *outer is the same shift of a whole 1024-point sub-transform by the outer pass: sub-transforms
+// k0 = t >> 5 from 9 up of a K1_TWSHARE = 2 build at N = 16384 hold sub-bin k1 + 32 (k2 - *inner) - *outer (mod 1024).  Both
+// are 0 in a K1_TWSHARE = 0 build.
+void fastfir2_twshare_shift(int log2n, int t, int *inner, int *outer)
+{
+    *inner = (K1_TWSHARE >= 1 && log2n == 14 && (t & 31) >= 17) ? 1 : 0;
+    *outer = (K1_TWSHARE >= 2 && log2n == 14 && (t >> 5) > 8) ? 1 : 0;
+}
+// ... and composed with them: the natural bin whose multiplier belongs in H slot (t, j, e) / gain slot (t, i, c) -- what
+// the uploads (capi_fastfir.hip: perm2 / permg, host and device design alike) are built from
+int fastfir2_slot_bin(int log2n, int t, int j, int e)
+{
+    const int R0 = (1 << log2n) / 1024;
+    int inner, outer;
+    fastfir2_twshare_shift(log2n, t, &inner, &outer);
+    const int k2 = ((j >> 1) + 8 * (j & 1) + 16 * e - inner) & 31;
+    const int sub = ((t & 31) + 32 * k2 - outer) & 1023;           // bin of the 1024-point sub-transform t >> 5
+    return (t >> 5) + R0 * sub;
+}
+int fastfir2_gain_slot_bin(int log2n, int t, int i, int c)
+{
+    return fastfir2_slot_bin(log2n, t, 2 * i + (c >> 1), c & 1);
 }
 
 }  // namespace csdr

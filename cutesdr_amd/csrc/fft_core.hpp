@@ -340,6 +340,20 @@ __host__ __device__ __forceinline__ void dit_head4_conjtw(v2f (&x)[R], v2f t0, v
     bfly_dit<0, SIGN>(x[a], x[a + 2]);                               // stage 4
     bfly_dit<8, SIGN>(x[a + 1], x[a + 3]);
 }
+// dit_head4_conjtw with a compile-time choice per input: x[4G+q] *= conj(tq) where Cq, else *= tq (a pass whose rows
+// k and R - k share one twiddle: the upper row takes it unconjugated).  Same instruction count: the conjugation is a
+// neg modifier of the same two packed instructions.
+template <int G, int R, int SIGN, bool FIRST_PLAIN, bool C0, bool C1, bool C2, bool C3>
+__host__ __device__ __forceinline__ void dit_head4_seltw(v2f (&x)[R], v2f t0, v2f t1, v2f t2, v2f t3)
+{
+    constexpr int a = 4 * G;
+    if constexpr (!FIRST_PLAIN) x[a] = C0 ? cmul_conj(x[a], t0) : cmul(x[a], t0);
+    x[a + 2] = C2 ? cmul_conj(x[a + 2], t2) : cmul(x[a + 2], t2);
+    if constexpr (C1) bfly_fma_conj(x[a], x[a + 1], t1); else bfly_fma(x[a], x[a + 1], t1);          // stage 2
+    if constexpr (C3) bfly_fma_conj(x[a + 2], x[a + 3], t3); else bfly_fma(x[a + 2], x[a + 3], t3);
+    bfly_dit<0, SIGN>(x[a], x[a + 2]);                               // stage 4
+    bfly_dit<8, SIGN>(x[a + 1], x[a + 3]);
+}
 // dit_head4 with run-time multipliers of its four inputs folded in: x[4G+q] *= tq first (the frequency response
 // between the forward and the inverse transform of the overlap-save filter).  The odd inputs' products ride in
 // the FMA butterflies: 10 packed instructions + 4 for the stage-4 pair instead of 8 + 8.
