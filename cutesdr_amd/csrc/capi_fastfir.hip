@@ -26,7 +26,7 @@ struct csdr_fastfir_batch {
     hipStream_t last_stream;          // stream of the most recent process call (setup waits for it)
     bool per_channel;                 // false: one shared filter
     float *d_h;                       // [filters][n] complex fp32 in pass-F3 register order of the generic kernel
-    float *d_h2;                      // N = 16384: the same responses in the pipelined kernel's order (it consumes H as
+    float *d_h2;                      // the same responses in the pipelined kernel's order, at every size (it consumes H as
                                       // its tail groups finish bins); both are kept, a launch may go to either kernel
     float *d_gain;                    // [filters][n] fp32: the real gains of the same responses, Re(H[k] (-j)^k), in the
                                       // pipelined kernel's order (host_math.hpp: fastfir_gain) -- what its 16384-point
@@ -221,8 +221,8 @@ csdr_fastfir_batch *csdr_fastfir_batch_create(int device, int channels, int fft_
         b->cus = cus;
     }
     {
-        // N = 16384 runs the software-pipelined build; CSDR_FASTFIR_VARIANT=0
-        // forces the generic kernel (diagnostics; launches it cannot take fall back to the generic one anyway)
+        // every size and block count runs the software-pipelined build; the generic kernel is reached only through
+        // CSDR_FASTFIR_VARIANT=0 / csdr__fastfir_set_variant (diagnostics, and the form the pipelined one is tested against)
         const char *v = getenv("CSDR_FASTFIR_VARIANT");
         b->variant = (v && atoi(v) == 0) ? 0 : 2;
     }
@@ -303,29 +303,20 @@ int csdr_fastfir_batch_setup(csdr_fastfir_batch *b, int channel, double flo, dou
         { const int rcm = fetch_mirror(b, 0); if (rcm) return rcm; }
         { const int rcp = flush_control(b, b->last_stream); if (rcp) return rcp; }
         CSDR_HIP(hipDeviceSynchronize());
-        float *nh = nullptr;
+        // one row per channel in place of the shared row, every row a copy of it
+        auto per_channel_rows = [&](float *&d, size_t row) -> int {
+            float *rows = nullptr;
+            CSDR_HIP(hipMalloc((void **)&rows, row * b->channels));
+            for (int c = 0; c < b->channels; c++)
+                CSDR_HIP(hipMemcpy((char *)rows + row * c, d, row, hipMemcpyDeviceToDevice));
+            CSDR_HIP(hipFree(d));
+            d = rows;
+            return 0;
+        };
         const size_t one = (size_t)b->n * 8;
-        CSDR_HIP(hipMalloc((void **)&nh, one * b->channels));
-        for (int c = 0; c < b->channels; c++)
-            CSDR_HIP(hipMemcpy((char *)nh + one * c, b->d_h, one, hipMemcpyDeviceToDevice));
-        CSDR_HIP(hipFree(b->d_h));
-        b->d_h = nh;
-        if (b->d_h2) {
-            float *nh2 = nullptr;
-            CSDR_HIP(hipMalloc((void **)&nh2, one * b->channels));
-            for (int c = 0; c < b->channels; c++)
-                CSDR_HIP(hipMemcpy((char *)nh2 + one * c, b->d_h2, one, hipMemcpyDeviceToDevice));
-            CSDR_HIP(hipFree(b->d_h2));
-            b->d_h2 = nh2;
-        }
-        {
-            float *ng = nullptr;
-            CSDR_HIP(hipMalloc((void **)&ng, one / 2 * b->channels));
-            for (int c = 0; c < b->channels; c++)
-                CSDR_HIP(hipMemcpy((char *)ng + one / 2 * c, b->d_gain, one / 2, hipMemcpyDeviceToDevice));
-            CSDR_HIP(hipFree(b->d_gain));
-            b->d_gain = ng;
-        }
+        { const int rc = per_channel_rows(b->d_h, one); if (rc) return rc; }
+        { const int rc = per_channel_rows(b->d_h2, one); if (rc) return rc; }
+        { const int rc = per_channel_rows(b->d_gain, one / 2); if (rc) return rc; }
         b->resp.resize(b->channels, b->resp[0]);
         b->per_channel = true;
     }

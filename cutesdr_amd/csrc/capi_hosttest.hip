@@ -61,7 +61,7 @@ int csdr__host_fastfir_gains(int n, double flo, double fhi, double off, double f
 }
 int csdr__host_fastfir2_bin_of(int log2n, int t, int j, int e) { return fastfir2_bin_of(log2n, t, j, e); }
 int csdr__host_fastfir2_gain_bin_of(int log2n, int t, int i, int c) { return fastfir2_gain_bin_of(log2n, t, i, c); }
-// the same two orders composed with the rotation of the shared pass twiddles (K1_TWSHARE): the slot -> bin maps the uploads
+// the same two orders composed with the rotation of the shared pass twiddles (fastfir2_twshare_shift): the slot -> bin maps the uploads
 // are built from, the rotation alone, and the build flag
 int csdr__host_fastfir2_slot_bin(int log2n, int t, int j, int e) { return fastfir2_slot_bin(log2n, t, j, e); }
 int csdr__host_fastfir2_gain_slot_bin(int log2n, int t, int i, int c) { return fastfir2_gain_slot_bin(log2n, t, i, c); }

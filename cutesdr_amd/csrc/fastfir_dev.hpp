@@ -56,6 +56,15 @@ __device__ __forceinline__ v4f store_operand(v2f lo, v2f hi)
     return v;
 }
 
+// The threads of one wave have written LDS that other threads of the same wave go on to read (a pass handing over inside
+// the half-wave that owns a sub-transform; a block that is one wave): no s_barrier, the wave only orders its own accesses
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 template <int LOG2N>
 struct FastFirCfg {
     static constexpr int N = 1 << LOG2N;

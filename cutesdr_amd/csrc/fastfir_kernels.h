@@ -48,7 +48,8 @@ int fastfir2_bin_of(int log2n, int t, int j, int e);
 // natural-order spectrum bin of gain slot (float4 index i*(N/32) + t, component c): the same per-thread order, four
 // gains per tail group i
 int fastfir2_gain_bin_of(int log2n, int t, int i, int c);
-// K1_TWSHARE (the unit's build flag: rows k1 and 32 - k1 of the radix-32 passes on one twiddle): by how many bins the
+// The shared twiddles of the 16384-point kernels (rows k1 and 32 - k1 of the radix-32 passes on one twiddle, rows k0 and
+// 16 - k0 of the outer pass on one power; fastfir2_twshare() is 2, the builds 0 and 1 are retired): by how many bins the
 // outputs of thread t's row of F3 (*inner) and of its whole 1024-point sub-transform (*outer) are rotated, and the two
 // orders above composed with that rotation -- the bin whose multiplier a slot has to hold.  What the uploads use.
 int fastfir2_twshare();

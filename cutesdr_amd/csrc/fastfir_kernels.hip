@@ -171,9 +171,7 @@ void fastfir_os_kernel(FastFirArgs a)
             });
         }
         // F2 -> F3 stays inside the half-wave that owns sub-transform sb
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         dbg_dump<LOG2N, DBG>(a, lds, 2);
         if (DBG && a.dbg_stage == 2) return;
 
@@ -208,9 +206,7 @@ void fastfir_os_kernel(FastFirArgs a)
             for (int j = 0; j < 16; j++) wrow[j] = wv[j];
             CSDR_STORE_GROUP_END();
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
 
         dbg_dump<LOG2N, DBG>(a, lds, 3);
         if (DBG && a.dbg_stage == 3) return;

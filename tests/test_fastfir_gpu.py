@@ -165,8 +165,8 @@ def test_full_size_properties():
 
 
 def test_generic_kernel_at_16384_in_child_process():
-    """N = 16384 normally runs the software-pipelined build (fastfir2_kernels.hip), which walks its blocks
-    in pairs; launches with an odd block count fall back to the generic kernel (fastfir_kernels.hip).
+    """N = 16384 runs the software-pipelined build (fastfir2_kernels.hip) for every block count; no launch reaches
+    the generic kernel (fastfir_kernels.hip) by itself any more.
     CSDR_FASTFIR_VARIANT=0 forces the generic kernel for every launch: it stays under the same parity cases.
     The switch is read when a batch object is created, so they run in a child interpreter."""
     import os, subprocess, sys

@@ -1,6 +1,7 @@
 """The K1_TWREG = 3 build of K1 (fastfir2_kernels.hip: the pass twiddles k1 = 1, 2 and 3 of F2 / I2 stay in registers)
-under the parity cases of the product's build.  It is the next build to be timed against K1_TWREG = 0; a build that
-computes something else is not worth timing."""
+under the parity cases of the product's build.  The product keeps all sixteen (K1_TWREG = 16, the default, timed against
+this build and against 0: HISTORY.md); 3 is the build in which some pass twiddles come from registers and the rest from
+LDS in the same pass, the path the default no longer takes."""
 import os
 import subprocess
 import sys

@@ -1,5 +1,5 @@
 """GPU parity of the pipelined overlap-save kernels against the fp64 oracle where the upload order of H / the gains goes
-through fastfir2_slot_bin (fastfir2_kernels.hip, K1_TWSHARE).
+through fastfir2_slot_bin (fastfir2_kernels.hip, the shared twiddles).
 
 The two 16384-point kernels (real gains, complex H) run on SHARED twiddles: rows k1 and 32 - k1 of the radix-32 passes on
 one table entry, rows k0 and 16 - k0 of the outer pass on one twiddle power, and the rows / sub-transforms that took the
