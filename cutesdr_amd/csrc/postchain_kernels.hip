@@ -18,6 +18,7 @@
 #include "ref_constants.hpp"
 #include <cstdlib>
 #include "launch_once.hpp"
+#include "pc_scan.hpp"
 
 namespace csdr {
 
@@ -54,27 +55,21 @@ __device__ __forceinline__ void fir_cpx(PcFir &f, float &re, float &im)
     re = ar; im = ai;
 }
 // ---- CIir (dsp/iir.cpp:171-201) ------------------------------------------------------------------
-__device__ __forceinline__ float iir_a(PcIir &f, float x)
+__device__ __forceinline__ float iir_step(const PcIir &f, float x, double &w1, double &w2)
 {
-    const double w0 = (double)x - f.a1 * f.w1a - f.a2 * f.w2a;
-    const double y = f.b0 * w0 + f.b1 * f.w1a + f.b2 * f.w2a;
-    f.w2a = f.w1a; f.w1a = w0;
+    const double w0 = (double)x - f.a1 * w1 - f.a2 * w2;
+    const double y = f.b0 * w0 + f.b1 * w1 + f.b2 * w2;
+    w2 = w1; w1 = w0;
     return (float)y;
 }
-__device__ __forceinline__ float iir_b(PcIir &f, float x)
-{
-    const double w0 = (double)x - f.a1 * f.w1b - f.a2 * f.w2b;
-    const double y = f.b0 * w0 + f.b1 * f.w1b + f.b2 * f.w2b;
-    f.w2b = f.w1b; f.w1b = w0;
-    return (float)y;
-}
+__device__ __forceinline__ float iir_a(PcIir &f, float x) { return iir_step(f, x, f.w1a, f.w2a); }
+__device__ __forceinline__ float iir_b(PcIir &f, float x) { return iir_step(f, x, f.w1b, f.w2b); }
 
 // =====================================================================================================
-// One workgroup of NW waves (1 or 4) per channel, 1024-sample tiles staged in LDS.  Thread t owns the
+// One workgroup of NW waves (1 or 4) per channel, 1024-sample tiles (PT, pc_scan.hpp) staged in LDS.  Thread t owns the
 // LC = 1024 / (64 NW) consecutive samples [LC t, LC t + LC) in every recurrence; element-wise work is
 // strided over the workgroup.
 // =====================================================================================================
-constexpr int PT = 1024;                 // tile length (samples)
 constexpr int PH = PC_AGC_RING;          // longest history (AGC delay / window)
 constexpr int PC_NCHUNK = (PC_AGC_RING + PT) / 16, PC_RLEVELS = 8;
 constexpr int LCMAX = 16;                // samples per thread at NW = 1
@@ -82,14 +77,6 @@ constexpr int BQ_TAB = (LCMAX + 1) * 4 + LCMAX * 2;   // biquad chunk tables: M^
 constexpr double kInvTwoPiD = 1.0 / (2.0 * 3.14159265358979323846);
 constexpr int PC_PLL_WARM_MAX = 192;     // longest warm-up of the overlapped PLL walks (pll_overlap) worth running
 constexpr float kNegBig = -1.0e30f;
-
-// what a workgroup's scans and broadcasts exchange through LDS (Wg<NW> holds a pointer to it)
-struct alignas(16) PcSync {               // (16: the arrays behind it are read and written in 16-byte pieces)
-    double xch[2][8][8];                 // per-wave totals of a workgroup scan; two banks used in turn, so that a scan
-                                         // needs ONE workgroup barrier (the next scan's writes go to the other bank)
-    double bc[4];                        // broadcast slot (thread 0 -> workgroup)
-    int flag;                            // workgroup-wide "any"
-};
 
 struct PcLds {
     PcSync sy;
@@ -159,296 +146,14 @@ __device__ __forceinline__ double pll_zero_err(float code, double p, double sgn)
     const double a = neg_re ? (neg_im ? -0.5 : 0.5) : 0.0;             // atan2(t.im, t.re) in turns
     return -sgn * a;
 }
-
-// A wave's scan steps on the DPP network instead of __shfl_up (two ds_bpermute per double and step: an LDS-pipe
-// round trip each, and a tile runs some ninety such steps one after the other on a single wave per SIMD).
-// pc_dpp<CTRL, ROW_MASK>(v, ident): v of the source lane, `ident` where the step has none.  The six steps
-// row_shr 1, 2, 4, 8, row_bcast 15 (rows 1, 3), row_bcast 31 (rows 2, 3) leave in every lane the combination of
-// lanes 0 .. lane, like the six __shfl_up steps (associativity is all they need; identities make the lane guards
-// unnecessary); wave_shr 1 then gives the exclusive value.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double pc_dpp(double v, double ident)
+// One exact step of the loop (fmdemod.cpp:166-177, samdemod.cpp:83-97) in turns -- wrapping is a - rint(a) -- on the sample
+// theta = v: the one-thread walks of FM and SAM and the overlapped walks (pll_overlap).  FM is the SAM form with sgn = 1.0.
+__device__ __forceinline__ void pll_step(float v, double &p, double &f, double alpha, double beta, double lo, double hi, double sgn)
 {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v), o = (unsigned long long)__double_as_longlong(ident);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)o, (int)(unsigned)u, CTRL, ROW_MASK, 0xf, false);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)(o >> 32), (int)(unsigned)(u >> 32), CTRL, ROW_MASK, 0xf, false);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+    const double err = pll_theta_is_zero_code(v) ? pll_zero_err(v, p, sgn) : -sgn * wrap_turn((double)v + sgn * p);
+    f = fmin(fmax(f + beta * err, lo), hi);
+    p = wrap_turn(p + f + alpha * err);
 }
-#define PC_SCAN_STEPS(STEP) STEP(0x111, 0xf) STEP(0x112, 0xf) STEP(0x114, 0xf) STEP(0x118, 0xf) STEP(0x142, 0xa) STEP(0x143, 0xc)
-
-// workgroup context: thread id, lane, wave; barrier that orders LDS traffic of the whole workgroup
-template <int NW>
-struct Wg {
-    static constexpr int NT = 64 * NW, LC = PT / NT;
-    int t, lane, w;
-    PcSync *S;
-    mutable int bank = 0;                // exchange bank of the next workgroup scan (uniform)
-    __device__ __forceinline__ double (*xbank() const)[8] { double (*b)[8] = S->xch[bank]; bank ^= 1; return b; }
-    __device__ __forceinline__ void sync() const
-    {
-        if constexpr (NW == 1) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        } else {
-            __syncthreads();
-        }
-    }
-    // true on every thread if pred holds on any thread
-    __device__ __forceinline__ bool any(bool pred) const
-    {
-        if constexpr (NW == 1) return __any(pred);
-        if (t == 0) S->flag = 0;
-        __syncthreads();
-        if (__any(pred) && lane == 0) S->flag = 1;
-        __syncthreads();
-        const bool r = S->flag != 0;
-        __syncthreads();
-        return r;
-    }
-    // value held by thread 0 -> every thread
-    __device__ __forceinline__ double bcast0(double v, int slot) const
-    {
-        if constexpr (NW == 1) return __shfl(v, 0);
-        if (t == 0) S->bc[slot] = v;
-        __syncthreads();
-        const double r = S->bc[slot];
-        __syncthreads();
-        return r;
-    }
-    // Affine maps s -> A s + B, thread t's map applied after those of threads < t.
-    // In: this thread's chunk map.  Out: (A, B) = composition of all EARLIER threads (exclusive),
-    // (At, Bt) = composition of all threads.
-    __device__ __forceinline__ void scan1(double &A, double &B, double &At, double &Bt) const
-    {
-#define PC_STEP(C_, R_) { const double A1 = pc_dpp<C_, R_>(A, 1.0), B1 = pc_dpp<C_, R_>(B, 0.0); B = A * B1 + B; A = A * A1; }
-        PC_SCAN_STEPS(PC_STEP)
-#undef PC_STEP
-        double Ae = pc_dpp<0x138, 0xf>(A, 1.0), Be = pc_dpp<0x138, 0xf>(B, 0.0);
-        if constexpr (NW == 1) {
-            At = __shfl(A, 63); Bt = __shfl(B, 63);
-        } else {
-            double (*xc)[8] = xbank();
-            if (lane == 63) { xc[w][0] = A; xc[w][1] = B; }
-            __syncthreads();
-            double PA = 1.0, PB = 0.0;
-            At = 1.0; Bt = 0.0;
-#pragma unroll
-            for (int q = 0; q < NW; q++) {
-                const double qa = xc[q][0], qb = xc[q][1];
-                if (q < w) { PB = qa * PB + qb; PA = qa * PA; }
-                Bt = qa * Bt + qb; At = qa * At;
-            }
-            Be = Ae * PB + Be; Ae = Ae * PA;
-        }
-        A = Ae; B = Be;
-    }
-    // scan1 and, in lockstep with it, the workgroup maximum of pk (returned in pk on every thread)
-    __device__ __forceinline__ void scan1_max(double &A, double &B, double &At, double &Bt, double &pk) const
-    {
-#define PC_STEP(C_, R_) { const double A1 = pc_dpp<C_, R_>(A, 1.0), B1 = pc_dpp<C_, R_>(B, 0.0), P1 = pc_dpp<C_, R_>(pk, -1.0e300); \
-                          B = A * B1 + B; A = A * A1; pk = fmax(pk, P1); }
-        PC_SCAN_STEPS(PC_STEP)
-#undef PC_STEP
-        double Ae = pc_dpp<0x138, 0xf>(A, 1.0), Be = pc_dpp<0x138, 0xf>(B, 0.0);
-        if constexpr (NW == 1) {
-            At = __shfl(A, 63); Bt = __shfl(B, 63); pk = __shfl(pk, 63);
-        } else {
-            double (*xc)[8] = xbank();
-            if (lane == 63) { xc[w][0] = A; xc[w][1] = B; xc[w][2] = pk; }
-            __syncthreads();
-            double PA = 1.0, PB = 0.0;
-            At = 1.0; Bt = 0.0; pk = -1.0e300;
-#pragma unroll
-            for (int q = 0; q < NW; q++) {
-                const double qa = xc[q][0], qb = xc[q][1];
-                if (q < w) { PB = qa * PB + qb; PA = qa * PA; }
-                Bt = qa * Bt + qb; At = qa * At; pk = fmax(pk, xc[q][2]);
-            }
-            Be = Ae * PB + Be; Ae = Ae * PA;
-        }
-        A = Ae; B = Be;
-    }
-    // scan1 and scan2 in lockstep (the FM squelch average and the speculative audio low-pass of a one-tile burst)
-    __device__ __forceinline__ void scan1_2(double &A, double &B, double &At, double &Bt, double (&m)[4], double (&v)[2], double (&mt)[4],
-                                            double (&vt)[2]) const
-    {
-#define PC_STEP(C_, R_) { \
-            const double A1 = pc_dpp<C_, R_>(A, 1.0), B1 = pc_dpp<C_, R_>(B, 0.0); \
-            const double p00 = pc_dpp<C_, R_>(m[0], 1.0), p01 = pc_dpp<C_, R_>(m[1], 0.0), p10 = pc_dpp<C_, R_>(m[2], 0.0), p11 = pc_dpp<C_, R_>(m[3], 1.0); \
-            const double q0 = pc_dpp<C_, R_>(v[0], 0.0), q1 = pc_dpp<C_, R_>(v[1], 0.0); \
-            B = A * B1 + B; A = A * A1; \
-            const double nv0 = m[0] * q0 + m[1] * q1 + v[0], nv1 = m[2] * q0 + m[3] * q1 + v[1]; \
-            const double n00 = m[0] * p00 + m[1] * p10, n01 = m[0] * p01 + m[1] * p11; \
-            const double n10 = m[2] * p00 + m[3] * p10, n11 = m[2] * p01 + m[3] * p11; \
-            m[0] = n00; m[1] = n01; m[2] = n10; m[3] = n11; v[0] = nv0; v[1] = nv1; }
-        PC_SCAN_STEPS(PC_STEP)
-#undef PC_STEP
-        double Ae = pc_dpp<0x138, 0xf>(A, 1.0), Be = pc_dpp<0x138, 0xf>(B, 0.0);
-        double e[4] = {pc_dpp<0x138, 0xf>(m[0], 1.0), pc_dpp<0x138, 0xf>(m[1], 0.0), pc_dpp<0x138, 0xf>(m[2], 0.0), pc_dpp<0x138, 0xf>(m[3], 1.0)};
-        double ev[2] = {pc_dpp<0x138, 0xf>(v[0], 0.0), pc_dpp<0x138, 0xf>(v[1], 0.0)};
-        static_assert(NW > 1, "scan1_2 is used by the four-wave kernel only");
-        double (*xc)[8] = xbank();
-        if (lane == 63) {
-            xc[w][0] = A; xc[w][1] = B;
-#pragma unroll
-            for (int k = 0; k < 4; k++) xc[w][2 + k] = m[k];
-            xc[w][6] = v[0]; xc[w][7] = v[1];
-        }
-        __syncthreads();
-        double PA = 1.0, PB = 0.0, P[4] = {1.0, 0.0, 0.0, 1.0}, Pv[2] = {0.0, 0.0};
-        At = 1.0; Bt = 0.0; mt[0] = 1.0; mt[1] = 0.0; mt[2] = 0.0; mt[3] = 1.0; vt[0] = 0.0; vt[1] = 0.0;
-#pragma unroll
-        for (int q = 0; q < NW; q++) {
-            const double *x = xc[q];
-            auto apply = [&](double (&M)[4], double (&V)[2]) {
-                const double nv0 = x[2] * V[0] + x[3] * V[1] + x[6], nv1 = x[4] * V[0] + x[5] * V[1] + x[7];
-                const double n00 = x[2] * M[0] + x[3] * M[2], n01 = x[2] * M[1] + x[3] * M[3];
-                const double n10 = x[4] * M[0] + x[5] * M[2], n11 = x[4] * M[1] + x[5] * M[3];
-                M[0] = n00; M[1] = n01; M[2] = n10; M[3] = n11; V[0] = nv0; V[1] = nv1;
-            };
-            if (q < w) { PB = x[0] * PB + x[1]; PA = x[0] * PA; apply(P, Pv); }
-            Bt = x[0] * Bt + x[1]; At = x[0] * At; apply(mt, vt);
-        }
-        Be = Ae * PB + Be; Ae = Ae * PA;
-        {
-            const double nv0 = e[0] * Pv[0] + e[1] * Pv[1] + ev[0], nv1 = e[2] * Pv[0] + e[3] * Pv[1] + ev[1];
-            const double n00 = e[0] * P[0] + e[1] * P[2], n01 = e[0] * P[1] + e[1] * P[3];
-            const double n10 = e[2] * P[0] + e[3] * P[2], n11 = e[2] * P[1] + e[3] * P[3];
-            e[0] = n00; e[1] = n01; e[2] = n10; e[3] = n11; ev[0] = nv0; ev[1] = nv1;
-        }
-        A = Ae; B = Be;
-#pragma unroll
-        for (int k = 0; k < 4; k++) m[k] = e[k];
-        v[0] = ev[0]; v[1] = ev[1];
-    }
-    // two independent scans of that kind in lockstep: one wave per SIMD pays every instruction's latency, and
-    // the two dependency chains fill each other's gaps; one exchange, one barrier
-    __device__ __forceinline__ void scan1x2(double &A, double &B, double &At, double &Bt, double &C, double &D, double &Ct, double &Dt) const
-    {
-#define PC_STEP(C_, R_) { const double A1 = pc_dpp<C_, R_>(A, 1.0), B1 = pc_dpp<C_, R_>(B, 0.0), C1 = pc_dpp<C_, R_>(C, 1.0), D1 = pc_dpp<C_, R_>(D, 0.0); \
-                          B = A * B1 + B; A = A * A1; D = C * D1 + D; C = C * C1; }
-        PC_SCAN_STEPS(PC_STEP)
-#undef PC_STEP
-        double Ae = pc_dpp<0x138, 0xf>(A, 1.0), Be = pc_dpp<0x138, 0xf>(B, 0.0), Ce = pc_dpp<0x138, 0xf>(C, 1.0), De = pc_dpp<0x138, 0xf>(D, 0.0);
-        if constexpr (NW == 1) {
-            At = __shfl(A, 63); Bt = __shfl(B, 63); Ct = __shfl(C, 63); Dt = __shfl(D, 63);
-        } else {
-            double (*xc)[8] = xbank();
-            if (lane == 63) { xc[w][0] = A; xc[w][1] = B; xc[w][2] = C; xc[w][3] = D; }
-            __syncthreads();
-            double PA = 1.0, PB = 0.0, PC = 1.0, PD = 0.0;
-            At = 1.0; Bt = 0.0; Ct = 1.0; Dt = 0.0;
-#pragma unroll
-            for (int q = 0; q < NW; q++) {
-                const double qa = xc[q][0], qb = xc[q][1], qc = xc[q][2], qd = xc[q][3];
-                if (q < w) { PB = qa * PB + qb; PA = qa * PA; PD = qc * PD + qd; PC = qc * PC; }
-                Bt = qa * Bt + qb; At = qa * At; Dt = qc * Dt + qd; Ct = qc * Ct;
-            }
-            Be = Ae * PB + Be; Ae = Ae * PA; De = Ce * PD + De; Ce = Ce * PC;
-        }
-        A = Ae; B = Be; C = Ce; D = De;
-    }
-    // maps x -> max(A x + B, C): same contract
-    __device__ __forceinline__ void scan_max(double &A, double &B, double &Cc, double &At, double &Bt, double &Ct) const
-    {
-#define PC_STEP(C_, R_) { const double A1 = pc_dpp<C_, R_>(A, 1.0), B1 = pc_dpp<C_, R_>(B, 0.0), C1 = pc_dpp<C_, R_>(Cc, -1.0e300); \
-                          Cc = fmax(A * C1 + B, Cc); B = A * B1 + B; A = A * A1; }
-        PC_SCAN_STEPS(PC_STEP)
-#undef PC_STEP
-        if constexpr (NW == 1) {
-            At = __shfl(A, 63); Bt = __shfl(B, 63); Ct = __shfl(Cc, 63);
-        } else {
-            double (*xc)[8] = xbank();
-            if (lane == 63) { xc[w][0] = A; xc[w][1] = B; xc[w][2] = Cc; }
-            __syncthreads();
-            At = 1.0; Bt = 0.0; Ct = -1.0e300;
-#pragma unroll
-            for (int q = 0; q < NW; q++) {
-                const double qa = xc[q][0], qb = xc[q][1], qc = xc[q][2];
-                Ct = fmax(qa * Ct + qb, qc); Bt = qa * Bt + qb; At = qa * At;
-            }
-        }
-    }
-    // 2x2 affine maps s -> M s + v: same contract as scan1 (m, v in: chunk map; out: exclusive), totals in mt, vt
-    __device__ __forceinline__ void scan2(double (&m)[4], double (&v)[2], double (&mt)[4], double (&vt)[2]) const
-    {
-#define PC_STEP(C_, R_) { \
-            const double p00 = pc_dpp<C_, R_>(m[0], 1.0), p01 = pc_dpp<C_, R_>(m[1], 0.0), p10 = pc_dpp<C_, R_>(m[2], 0.0), p11 = pc_dpp<C_, R_>(m[3], 1.0); \
-            const double q0 = pc_dpp<C_, R_>(v[0], 0.0), q1 = pc_dpp<C_, R_>(v[1], 0.0); \
-            const double nv0 = m[0] * q0 + m[1] * q1 + v[0], nv1 = m[2] * q0 + m[3] * q1 + v[1]; \
-            const double n00 = m[0] * p00 + m[1] * p10, n01 = m[0] * p01 + m[1] * p11; \
-            const double n10 = m[2] * p00 + m[3] * p10, n11 = m[2] * p01 + m[3] * p11; \
-            m[0] = n00; m[1] = n01; m[2] = n10; m[3] = n11; v[0] = nv0; v[1] = nv1; }
-        PC_SCAN_STEPS(PC_STEP)
-#undef PC_STEP
-        double e[4] = {pc_dpp<0x138, 0xf>(m[0], 1.0), pc_dpp<0x138, 0xf>(m[1], 0.0), pc_dpp<0x138, 0xf>(m[2], 0.0), pc_dpp<0x138, 0xf>(m[3], 1.0)};
-        double ev[2] = {pc_dpp<0x138, 0xf>(v[0], 0.0), pc_dpp<0x138, 0xf>(v[1], 0.0)};
-        if constexpr (NW == 1) {
-#pragma unroll
-            for (int k = 0; k < 4; k++) mt[k] = __shfl(m[k], 63);
-            vt[0] = __shfl(v[0], 63); vt[1] = __shfl(v[1], 63);
-        } else {
-            double (*xc)[8] = xbank();
-            if (lane == 63) {
-#pragma unroll
-                for (int k = 0; k < 4; k++) xc[w][k] = m[k];
-                xc[w][4] = v[0]; xc[w][5] = v[1];
-            }
-            __syncthreads();
-            double P[4] = {1.0, 0.0, 0.0, 1.0}, Pv[2] = {0.0, 0.0};
-            mt[0] = 1.0; mt[1] = 0.0; mt[2] = 0.0; mt[3] = 1.0; vt[0] = 0.0; vt[1] = 0.0;
-#pragma unroll
-            for (int q = 0; q < NW; q++) {
-                const double *x = xc[q];
-                auto apply = [&](double (&M)[4], double (&V)[2]) {
-                    const double nv0 = x[0] * V[0] + x[1] * V[1] + x[4], nv1 = x[2] * V[0] + x[3] * V[1] + x[5];
-                    const double n00 = x[0] * M[0] + x[1] * M[2], n01 = x[0] * M[1] + x[1] * M[3];
-                    const double n10 = x[2] * M[0] + x[3] * M[2], n11 = x[2] * M[1] + x[3] * M[3];
-                    M[0] = n00; M[1] = n01; M[2] = n10; M[3] = n11; V[0] = nv0; V[1] = nv1;
-                };
-                if (q < w) apply(P, Pv);
-                apply(mt, vt);
-            }
-            // exclusive of this thread = (wave-exclusive e) after (previous waves P)
-            const double nv0 = e[0] * Pv[0] + e[1] * Pv[1] + ev[0], nv1 = e[2] * Pv[0] + e[3] * Pv[1] + ev[1];
-            const double n00 = e[0] * P[0] + e[1] * P[2], n01 = e[0] * P[1] + e[1] * P[3];
-            const double n10 = e[2] * P[0] + e[3] * P[2], n11 = e[2] * P[1] + e[3] * P[3];
-            e[0] = n00; e[1] = n01; e[2] = n10; e[3] = n11; ev[0] = nv0; ev[1] = nv1;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) m[k] = e[k];
-        v[0] = ev[0]; v[1] = ev[1];
-    }
-    // exclusive prefix sum over the threads
-    __device__ __forceinline__ double scan_sum_excl(double x) const
-    {
-        double incl = x;
-#define PC_STEP(C_, R_) incl += pc_dpp<C_, R_>(incl, 0.0);
-        PC_SCAN_STEPS(PC_STEP)
-#undef PC_STEP
-        double ex = incl - x;
-        if constexpr (NW > 1) {
-            double (*xc)[8] = xbank();
-            if (lane == 63) xc[w][0] = incl;
-            __syncthreads();
-#pragma unroll
-            for (int q = 0; q < NW; q++) if (q < w) ex += xc[q][0];
-        }
-        return ex;
-    }
-    // value of thread t-1 (thread 0 gets `first`)
-    __device__ __forceinline__ float prev_thread(float v, float first) const
-    {
-        float p = __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), 0x138, 0xf, 0xf, false));   // wave_shr:1
-        if constexpr (NW > 1) {
-            double (*xc)[8] = xbank();
-            if (lane == 63) xc[w][6] = (double)v;
-            __syncthreads();
-            if (lane == 0 && w > 0) p = (float)xc[w - 1][6];
-        }
-        return t == 0 ? first : p;
-    }
-};
 
 // The outputs a thread of the tile owns: LC consecutive ones with four waves (the FIRs below then share one register
 // window of the input), the strided t + NT j otherwise.
@@ -502,6 +207,75 @@ __device__ __forceinline__ void slide(const Wg<NW> &g, float *w, int hist, int n
     g.sync();
     if (g.t < 64) for (int j = 0; j < 2; j++) { const int i = g.t + 64 * j; if (i < hist) w[i] = keep[j]; }
 }
+// the same for the AGC's rings, hist <= PH: read all, one barrier, write all -- the caller's barrier follows
+template <int NW, class T>
+__device__ __forceinline__ void keep_tail(const Wg<NW> &g, T *w, int hist, int n)
+{
+    constexpr int NT = Wg<NW>::NT;
+    T keep[PH / NT];
+#pragma unroll
+    for (int j = 0; j < PH / NT; j++) { const int i = g.t + NT * j; if (i < hist) keep[j] = w[n + i]; }
+    g.sync();
+#pragma unroll
+    for (int j = 0; j < PH / NT; j++) { const int i = g.t + NT * j; if (i < hist) w[i] = keep[j]; }
+}
+// FIR taps as PcLds holds them: reversed, four zeros in front, zeros behind
+template <int NT>
+__device__ __forceinline__ void stage_taps(float *h, const float *coef, int nt, int t)
+{
+    for (int i = t; i < PC_FIR_MAX + 17; i += NT) {
+        const int k = nt - 1 - (i - 4);
+        h[i] = (k >= 0 && k < nt) ? coef[k] : 0.f;
+    }
+}
+
+// A channel's output row: mono floats, or pairs (stereo audio with both halves alike, or complex samples)
+struct PcRow {
+    float *m; float2 *s; bool stereo;
+    static __device__ __forceinline__ PcRow of(const PcArgs &a, int ch)
+    {
+        const long orow = (long)(a.out_rows ? a.out_rows[ch] : ch) * a.out_stride;
+        return {a.out + orow, reinterpret_cast<float2 *>(a.out) + orow, (a.flags & PC_STEREO) != 0};
+    }
+    __device__ __forceinline__ void put(long i, float y) const { if (stereo) s[i] = make_float2(y, y); else m[i] = y; }
+    __device__ __forceinline__ float raw(long i) const { return stereo ? s[i].x : m[i]; }
+};
+
+// CFmDemod's squelch after a burst (fmdemod.cpp:128-151): sq = the average behind the burst; hysteresis around the threshold
+__device__ __forceinline__ int squelch_decide(double sq, double thresh, int squelched)
+{
+    if (0 == thresh) return 1;
+    if (squelched) return sq < (thresh - refc::FM_SQUELCH_HYSTERESIS) ? 0 : squelched;
+    return sq >= (thresh + refc::FM_SQUELCH_HYSTERESIS) ? 1 : squelched;
+}
+
+// The burst-parallel side kernels (AGC peaks, squelch maps / apply): one workgroup per (channel, group of bpw bursts).
+// Host: as few bursts per workgroup as still give every workgroup a slot in ONE round (four 256-thread workgroups per
+// CU at these kernels' 88-110 registers), so that taps, tables and zeroing are paid once per slot.
+static int pc_bursts_per_wg(const PcArgs &a)
+{
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const long slots = 4L * (cus > 0 ? cus : 256);
+    const int bpw = (int)(((long)a.channels * a.nbursts + slots - 1) / slots);
+    return bpw < 1 ? 1 : bpw;
+}
+__host__ __device__ __forceinline__ int pc_burst_groups(int nbursts, int bpw) { return (nbursts + bpw - 1) / bpw; }
+// a launch's arguments, with its slot of the workgroup trace where that is compiled in
+static PcArgs pc_traced(PcArgs a)
+{
+#ifdef CSDR_WG_TRACE
+    a.trace = wgtrace_next();
+#endif
+    return a;
+}
+struct PcBurstGroup { int ch, b0, b1; };                 // this workgroup's channel and bursts [b0, b1)
+__device__ __forceinline__ PcBurstGroup pc_burst_group(int nbursts, int bpw)
+{
+    const int ngrp = pc_burst_groups(nbursts, bpw);
+    const int ch = blockIdx.x / ngrp, b0 = (blockIdx.x % ngrp) * bpw;
+    return {ch, b0, b0 + bpw < nbursts ? b0 + bpw : nbursts};
+}
 
 // Thread 0 walks src[0..n) in order, f(value, index); the next eight values are fetched from LDS
 // while the current eight go through the recurrence, so no LDS latency sits on the dependent chain.
@@ -544,8 +318,7 @@ __device__ __forceinline__ double lin1_scan(const Wg<NW> &g, const float *x, int
                                             const double *apw, F emit)
 {
     constexpr int LC = Wg<NW>::LC;
-    const int base = LC * g.t;
-    int cnt = n - base; cnt = cnt < 0 ? 0 : (cnt > LC ? LC : cnt);
+    const int base = g.base(), cnt = g.count(n);
     float xv[LC];
     double loc[LC], p = 0.0;
 #pragma unroll
@@ -554,9 +327,9 @@ __device__ __forceinline__ double lin1_scan(const Wg<NW> &g, const float *x, int
         p = j < cnt ? a * p + gn * (double)xv[j] : p;
         loc[j] = p;
     }
-    double A = apw[cnt], B = p, At, Bt;
-    g.scan1(A, B, At, Bt);
-    const double S = A * s0 + B;                                     // state entering this thread's chunk
+    Aff1 m{apw[cnt], p}, tot;
+    g.scan(m, tot);
+    const double S = m(s0);                                          // state entering this thread's chunk
     if (EMIT) {
         double prev = S;
 #pragma unroll
@@ -568,18 +341,36 @@ __device__ __forceinline__ double lin1_scan(const Wg<NW> &g, const float *x, int
             }
         }
     }
-    return At * s0 + Bt;
+    return tot(s0);
 }
 
-// CSMeter (smeter.cpp:62-93) over one tile, final state only.  att is a plain averager; dec obeys
-// dec' = max(att', (1-da) dec + da mag), and maps x -> max(A x + B, C) are closed under composition.
+// CSMeter (smeter.cpp:62-93), final state only.  att is a plain averager (Aff1); dec obeys
+// dec' = max(att', (1-da) dec + da mag): one sample is the map AffMax{1-da, da mag, att'}.
+// From a thread's attack map and its maximum to the attack average entering its chunk; pk: then the maximum of the whole tile
+template <int NW>
+__device__ __forceinline__ double smeter_att_scan(const Wg<NW> &g, const PcSMeter &sm, Aff1 att, double &pk, double &att_end)
+{
+    Both<Aff1, Max> m{att, {pk}}, tot;
+    g.scan(m, tot);
+    pk = tot.q.v;
+    att_end = tot.p(sm.att_ave);
+    return m.p(sm.att_ave);
+}
+// ... and from the threads' decay maps, the attack average and the maximum of a tile to the meter's state behind it
+template <int NW>
+__device__ __forceinline__ void smeter_finish(const Wg<NW> &g, PcSMeter &sm, AffMax dec, double att_end, double pk)
+{
+    AffMax tot;
+    g.scan(dec, tot);
+    const double dec_end = tot(sm.dec_ave);
+    sm.att_ave = att_end; sm.dec_ave = dec_end; sm.ave_mag = dec_end; sm.peak_mag = fmax(sm.peak_mag, pk);
+}
 template <int NW>
 __device__ __forceinline__ void smeter_tile(const Wg<NW> &g, PcSMeter &sm, const float *db, int n, const double *apw_att)
 {
     constexpr int LC = Wg<NW>::LC;
     const double aa = sm.att_a, ia = 1.0 - sm.att_a, da = sm.dec_a, id = 1.0 - sm.dec_a;
-    const int base = LC * g.t;
-    int cnt = n - base; cnt = cnt < 0 ? 0 : (cnt > LC ? LC : cnt);
+    const int base = g.base(), cnt = g.count(n);
     float xv[LC];
     double loc[LC], p = 0.0, pk = -1.0e300;
 #pragma unroll
@@ -589,21 +380,13 @@ __device__ __forceinline__ void smeter_tile(const Wg<NW> &g, PcSMeter &sm, const
         loc[j] = p;
         if (j < cnt) pk = fmax(pk, (double)xv[j]);
     }
-    double A = apw_att[cnt], B = p, At, Bt;
-    g.scan1_max(A, B, At, Bt, pk);                                   // pk: now the maximum of the whole tile
-    const double S = A * sm.att_ave + B;
-    const double att_end = At * sm.att_ave + Bt;
-    double MA = 1.0, MB = 0.0, MC = -1.0e300, TA, TB, TC;            // chunk map of the decay average
+    double att_end;
+    const double S = smeter_att_scan(g, sm, {apw_att[cnt], p}, pk, att_end);
+    AffMax dec = AffMax::identity();                                 // chunk map of the decay average
 #pragma unroll
-    for (int j = 0; j < LC; j++) {
-        if (j < cnt) {
-            const double att = loc[j] + apw_att[j + 1] * S;          // updated attack average at this sample
-            MA = id * MA; MB = id * MB + da * (double)xv[j]; MC = fmax(id * MC + da * (double)xv[j], att);
-        }
-    }
-    g.scan_max(MA, MB, MC, TA, TB, TC);
-    const double dec_end = fmax(TA * sm.dec_ave + TB, TC);
-    sm.att_ave = att_end; sm.dec_ave = dec_end; sm.ave_mag = dec_end; sm.peak_mag = fmax(sm.peak_mag, pk);
+    for (int j = 0; j < LC; j++)
+        if (j < cnt) dec = AffMax{id, da * (double)xv[j], loc[j] + apw_att[j + 1] * S}.after(dec);   // (updated attack average)
+    smeter_finish(g, sm, dec, att_end, pk);
 }
 
 // CIir direct form II (iir.cpp:171-186) over x[0..n) in place.  State s = (w1, w2):
@@ -622,28 +405,36 @@ __device__ __forceinline__ void biquad_table(double *tab, const PcIir &f, int t)
         }
     }
 }
+// one sample of a thread's chunk, run from a zero state (w1, w2): the output without the homogeneous part; the state
+// moves only while the sample is one of the tile's (live)
+__device__ __forceinline__ double biquad_chunk_step(const PcIir &f, double xv, bool live, double &w1, double &w2)
+{
+    const double w0 = xv - f.a1 * w1 - f.a2 * w2;
+    const double y = f.b0 * w0 + f.b1 * w1 + f.b2 * w2;
+    if (live) { w2 = w1; w1 = w0; }
+    return y;
+}
+// the map of a chunk of cnt samples: M^cnt from a table of matrix powers, (v0, v1) = the chunk's zero-state response
+__device__ __forceinline__ Aff2 chunk_map2(const double *tab, int cnt, double v0, double v1)
+{
+    return {{tab[4 * cnt], tab[4 * cnt + 1], tab[4 * cnt + 2], tab[4 * cnt + 3]}, {v0, v1}};
+}
 template <int NW>
 __device__ __forceinline__ void biquad_scan(const Wg<NW> &g, float *x, int n, PcIir &f, const double *tab)
 {
     constexpr int LC = Wg<NW>::LC;
-    const int base = LC * g.t;
-    int cnt = n - base; cnt = cnt < 0 ? 0 : (cnt > LC ? LC : cnt);
+    const int base = g.base(), cnt = g.count(n);
     double y[LC], w1 = 0.0, w2 = 0.0;
 #pragma unroll
-    for (int j = 0; j < LC; j++) {
-        const double xv = j < cnt ? (double)x[base + j] : 0.0;
-        const double w0 = xv - f.a1 * w1 - f.a2 * w2;
-        y[j] = f.b0 * w0 + f.b1 * w1 + f.b2 * w2;
-        if (j < cnt) { w2 = w1; w1 = w0; }
-    }
-    double m[4] = {tab[4 * cnt], tab[4 * cnt + 1], tab[4 * cnt + 2], tab[4 * cnt + 3]}, v[2] = {w1, w2}, mt[4], vt[2];
-    g.scan2(m, v, mt, vt);
-    const double S1 = m[0] * f.w1a + m[1] * f.w2a + v[0], S2 = m[2] * f.w1a + m[3] * f.w2a + v[1];
+    for (int j = 0; j < LC; j++) y[j] = biquad_chunk_step(f, j < cnt ? (double)x[base + j] : 0.0, j < cnt, w1, w2);
+    Aff2 m = chunk_map2(tab, cnt, w1, w2), tot;
+    g.scan(m, tot);
+    double S1, S2;
+    m(f.w1a, f.w2a, S1, S2);
+    tot(f.w1a, f.w2a, f.w1a, f.w2a);                                 // (the old state goes in by value)
 #pragma unroll
     for (int j = 0; j < LC; j++)
         if (j < cnt) x[base + j] = (float)(y[j] + tab[68 + 2 * j] * S1 + tab[68 + 2 * j + 1] * S2);
-    const double nw1 = mt[0] * f.w1a + mt[1] * f.w2a + vt[0], nw2 = mt[2] * f.w1a + mt[3] * f.w2a + vt[1];
-    f.w1a = nw1; f.w2a = nw2;
 }
 
 // One-tile FM burst: the squelch average (lin1_scan without emit over sq[0..n)) and, in lockstep with it, the audio
@@ -656,27 +447,22 @@ __device__ __forceinline__ double sq_and_lowpass(const Wg<NW> &g, const float *s
                                                  double &w1n, double &w2n)
 {
     constexpr int LC = Wg<NW>::LC;
-    const int base = LC * g.t;
-    int cnt = n - base; cnt = cnt < 0 ? 0 : (cnt > LC ? LC : cnt);
+    const int base = g.base(), cnt = g.count(n);
     double p = 0.0, yy[LC], w1 = 0.0, w2 = 0.0;
 #pragma unroll
     for (int j = 0; j < LC; j++) {
         const float sv = j < cnt ? sq[base + j] : 0.f;
         p = j < cnt ? a * p + gn * (double)sv : p;
-        const double xv = j < cnt ? (double)x[base + j] : 0.0;
-        const double w0 = xv - f.a1 * w1 - f.a2 * w2;
-        yy[j] = f.b0 * w0 + f.b1 * w1 + f.b2 * w2;
-        if (j < cnt) { w2 = w1; w1 = w0; }
+        yy[j] = biquad_chunk_step(f, j < cnt ? (double)x[base + j] : 0.0, j < cnt, w1, w2);
     }
-    double A = apw[cnt], B = p, At, Bt;
-    double m[4] = {tab[4 * cnt], tab[4 * cnt + 1], tab[4 * cnt + 2], tab[4 * cnt + 3]}, v[2] = {w1, w2}, mt[4], vt[2];
-    g.scan1_2(A, B, At, Bt, m, v, mt, vt);
-    const double S1 = m[0] * f.w1a + m[1] * f.w2a + v[0], S2 = m[2] * f.w1a + m[3] * f.w2a + v[1];
+    Both<Aff1, Aff2> m{{apw[cnt], p}, chunk_map2(tab, cnt, w1, w2)}, tot;
+    g.scan(m, tot);
+    double S1, S2;
+    m.q(f.w1a, f.w2a, S1, S2);
 #pragma unroll
     for (int j = 0; j < LC; j++) y[j] = (float)(yy[j] + tab[68 + 2 * j] * S1 + tab[68 + 2 * j + 1] * S2);
-    w1n = mt[0] * f.w1a + mt[1] * f.w2a + vt[0];
-    w2n = mt[2] * f.w1a + mt[3] * f.w2a + vt[1];
-    return At * s0 + Bt;
+    tot.q(f.w1a, f.w2a, w1n, w2n);
+    return tot.p(s0);
 }
 
 // CAgc's attack / decay averagers (agc.cpp:233-262):  ave += alpha (pk - ave),  alpha = rise when
@@ -691,8 +477,7 @@ template <int NW, class F>
 __device__ __forceinline__ bool agc_ave_scan(const Wg<NW> &g, const float *pk, int n, double rise, double fall, double &ave, F emit)
 {
     constexpr int LC = Wg<NW>::LC;
-    const int base = LC * g.t;
-    int cnt = n - base; cnt = cnt < 0 ? 0 : (cnt > LC ? LC : cnt);
+    const int base = g.base(), cnt = g.count(n);
     const double ave0 = ave;
     float pv[LC];
     unsigned sel = 0;
@@ -702,17 +487,17 @@ __device__ __forceinline__ bool agc_ave_scan(const Wg<NW> &g, const float *pk, i
         if (j < cnt && (double)pv[j] > ave0) sel |= 1u << j;
     }
     for (int round = 0; round < PC_AGC_ROUNDS; round++) {
-        double A = 1.0, B = 0.0, At, Bt;
+        Aff1 m = Aff1::identity(), tot;
 #pragma unroll
         for (int j = 0; j < LC; j++) {
             if (j < cnt) {
                 const double al = (sel >> j & 1) ? rise : fall;
-                A = A - al * A;
-                B = B + al * ((double)pv[j] - B);
+                m.a = m.a - al * m.a;
+                m.b = m.b + al * ((double)pv[j] - m.b);
             }
         }
-        g.scan1(A, B, At, Bt);
-        double x = A * ave0 + B;
+        g.scan(m, tot);
+        double x = m(ave0);
         double val[LC];
         unsigned nsel = 0;
 #pragma unroll
@@ -727,7 +512,7 @@ __device__ __forceinline__ bool agc_ave_scan(const Wg<NW> &g, const float *pk, i
         if (!g.any(nsel != sel)) {
 #pragma unroll
             for (int j = 0; j < LC; j++) if (j < cnt) emit(base + j, val[j]);
-            ave = At * ave0 + Bt;
+            ave = tot(ave0);
             return true;
         }
         sel = nsel;
@@ -736,14 +521,13 @@ __device__ __forceinline__ bool agc_ave_scan(const Wg<NW> &g, const float *pk, i
 }
 
 // Both averagers (attack, decay) of a tile in the same rounds: their scans are independent, and run in lockstep
-// (Wg::scan1x2).  emit(i, attack_i, decay_i).
+// (Both<Aff1, Aff1>).  emit(i, attack_i, decay_i).
 template <int NW, class F>
 __device__ __forceinline__ bool agc_ave_scan2(const Wg<NW> &g, const float *pk, int n, double a_rise, double a_fall, double d_rise,
                                               double d_fall, double &att, double &dec, F emit)
 {
     constexpr int LC = Wg<NW>::LC;
-    const int base = LC * g.t;
-    int cnt = n - base; cnt = cnt < 0 ? 0 : (cnt > LC ? LC : cnt);
+    const int base = g.base(), cnt = g.count(n);
     const double att0 = att, dec0 = dec;
     float pv[LC];
     unsigned sa = 0, sd = 0;
@@ -754,17 +538,17 @@ __device__ __forceinline__ bool agc_ave_scan2(const Wg<NW> &g, const float *pk, 
         if (j < cnt && (double)pv[j] > dec0) sd |= 1u << j;
     }
     for (int round = 0; round < PC_AGC_ROUNDS; round++) {
-        double A = 1.0, B = 0.0, At, Bt, C = 1.0, D = 0.0, Ct, Dt;
+        Both<Aff1, Aff1> m = Both<Aff1, Aff1>::identity(), tot;
 #pragma unroll
         for (int j = 0; j < LC; j++) {
             if (j < cnt) {
                 const double al = (sa >> j & 1) ? a_rise : a_fall, dl = (sd >> j & 1) ? d_rise : d_fall;
-                A = A - al * A; B = B + al * ((double)pv[j] - B);
-                C = C - dl * C; D = D + dl * ((double)pv[j] - D);
+                m.p.a = m.p.a - al * m.p.a; m.p.b = m.p.b + al * ((double)pv[j] - m.p.b);
+                m.q.a = m.q.a - dl * m.q.a; m.q.b = m.q.b + dl * ((double)pv[j] - m.q.b);
             }
         }
-        g.scan1x2(A, B, At, Bt, C, D, Ct, Dt);
-        double x = A * att0 + B, y = C * dec0 + D;
+        g.scan(m, tot);
+        double x = m.p(att0), y = m.q(dec0);
         double va[LC], vd[LC];
         unsigned na = 0, nd = 0;
 #pragma unroll
@@ -781,7 +565,7 @@ __device__ __forceinline__ bool agc_ave_scan2(const Wg<NW> &g, const float *pk, 
         if (!g.any(na != sa || nd != sd)) {
 #pragma unroll
             for (int j = 0; j < LC; j++) if (j < cnt) emit(base + j, va[j], vd[j]);
-            att = At * att0 + Bt; dec = Ct * dec0 + Dt;
+            att = tot.p(att0); dec = tot.q(dec0);
             return true;
         }
         sa = na; sd = nd;
@@ -798,7 +582,7 @@ __device__ __forceinline__ bool agc_ave_scan2(const Wg<NW> &g, const float *pk, 
 // solved by a scan like the biquad.  The guess is then checked sample by sample (|e| < 1/2, f
 // inside the clamp); if it holds everywhere the result is the sequential one, otherwise (cycle slip,
 // acquisition, noise) the caller walks the tile.  emit(i, phi_before, f_after).
-// tab: M^k, k = 0..16 (4 doubles each)
+// tab: M^k, k = 0..16 (4 doubles each).  ph, fr are written only when the guess held (true).
 __device__ __forceinline__ void pll_table(double *tab, double alpha, double beta, int t)
 {
     if (t == 0) {
@@ -817,8 +601,7 @@ __device__ __forceinline__ bool pll_scan(const Wg<NW> &g, const float *th, int n
                                          double &ph, double &fr, const double *tab, F emit)
 {
     constexpr int LC = Wg<NW>::LC;
-    const int base = LC * g.t;
-    int cnt = n - base; cnt = cnt < 0 ? 0 : (cnt > LC ? LC : cnt);
+    const int base = g.base(), cnt = g.count(n);
     float tv[LC];
     bool zero = false;
 #pragma unroll
@@ -854,10 +637,10 @@ __device__ __forceinline__ bool pll_scan(const Wg<NW> &g, const float *th, int n
             v[0] = v[0] + v[1] + alpha * e;
         }
     }
-    double m[4] = {tab[4 * cnt], tab[4 * cnt + 1], tab[4 * cnt + 2], tab[4 * cnt + 3]}, mt[4], vt[2];
-    g.scan2(m, v, mt, vt);
-    double x0 = m[0] * ph + m[1] * fr + v[0];                        // state entering this thread's chunk
-    double x1 = m[2] * ph + m[3] * fr + v[1];
+    Aff2 m = chunk_map2(tab, cnt, v[0], v[1]), tot;
+    g.scan(m, tot);
+    double x0, x1;
+    m(ph, fr, x0, x1);                                               // state entering this thread's chunk
     bool bad = false;
 #pragma unroll
     for (int j = 0; j < LC; j++) {
@@ -871,7 +654,8 @@ __device__ __forceinline__ bool pll_scan(const Wg<NW> &g, const float *th, int n
         }
     }
     if (g.any(bad || zero)) return false;
-    const double nph = mt[0] * ph + mt[1] * fr + vt[0], nfr = mt[2] * ph + mt[3] * fr + vt[1];
+    double nph, nfr;
+    tot(ph, fr, nph, nfr);
     ph = nph - rint(nph); fr = nfr;
     return true;
 }
@@ -888,7 +672,7 @@ __device__ __forceinline__ bool pll_scan(const Wg<NW> &g, const float *th, int n
 // on top are for a wrap decision that differs late in the warm-up (measured on noise: 32 samples at rho = 0.47 sent
 // a quarter of the tiles to the one-thread walk, 48 none: 1.92 -> 0.45 ms for 85 idle receivers x 2^20 samples, against
 // 0.34 ms with carriers).
-// xp, xf: NT doubles of LDS each.  emit(i, phase_before, freq_after).
+// xp, xf: NT doubles of LDS each.  emit(i, phase_before, freq_after).  ph, fr are written only on success.
 __device__ __forceinline__ int pll_warm_len(double alpha, double beta)
 {
     const double tr = 2.0 - alpha - beta, det = 1.0 - alpha, disc = tr * tr - 4.0 * det;
@@ -902,25 +686,19 @@ __device__ __forceinline__ bool pll_overlap(const Wg<NW> &g, const float *th, in
                                             double hi, double &ph, double &fr, double *xp, double *xf, F emit)
 {
     constexpr int LC = Wg<NW>::LC;
-    const int base = LC * g.t;
-    int cnt = n - base; cnt = cnt < 0 ? 0 : (cnt > LC ? LC : cnt);
+    const int base = g.base(), cnt = g.count(n);
     int i = base - warm;
     double p = 0.0, f = 0.0;
     const bool exact = i <= 0;
     if (exact) { i = 0; p = ph; f = fr; }
-    auto step = [&](float v) {                                  // fmdemod.cpp:166-177, in turns
-        const double err = pll_theta_is_zero_code(v) ? pll_zero_err(v, p, 1.0) : -wrap_turn((double)v + p);
-        f = fmin(fmax(f + beta * err, lo), hi);
-        p = wrap_turn(p + f + alpha * err);
-    };
     if (cnt > 0) {
         float v = th[i];
-        for (; i < base; i++) { const float vn = th[i + 1]; step(v); v = vn; }
+        for (; i < base; i++) { const float vn = th[i + 1]; pll_step(v, p, f, alpha, beta, lo, hi, 1.0); v = vn; }
     }
     const double ps = p, fs = f;
 #pragma unroll
     for (int j = 0; j < LC; j++) {
-        if (j < cnt) { const double pb = p; step(th[base + j]); emit(base + j, pb, f); }
+        if (j < cnt) { const double pb = p; pll_step(th[base + j], p, f, alpha, beta, lo, hi, 1.0); emit(base + j, pb, f); }
     }
     xp[g.t] = p; xf[g.t] = f;
     g.sync();
@@ -934,6 +712,26 @@ __device__ __forceinline__ bool pll_overlap(const Wg<NW> &g, const float *th, in
     if (g.any(bad)) return false;
     if (n > 0) { ph = pe; fr = fe; }
     return true;
+}
+
+// The same loop where neither holds: thread 0 walks the tile sample by sample and every thread gets the end state.
+// ph, fr, lo, hi in radians, as the channel keeps them; emit(i, phase_before, freq_after) in turns.
+template <int NW, class F>
+__device__ __forceinline__ void pll_walk(const Wg<NW> &g, const float *th, int n, double alpha, double beta, double lo, double hi,
+                                         double sgn, double &ph, double &fr, F emit)
+{
+    g.sync();
+    if (g.t == 0) {
+        const double lo_t = lo * kInvTwoPiD, hi_t = hi * kInvTwoPiD;
+        double p = ph * kInvTwoPiD, f = fr * kInvTwoPiD;
+        seq_walk(th, n, [&](float v, int i) {
+            const double pb = p;
+            pll_step(v, p, f, alpha, beta, lo_t, hi_t, sgn);
+            emit(i, pb, f);
+        });
+        ph = p * kTwoPiD; fr = f * kTwoPiD;
+    }
+    ph = g.bcast0(ph, 0); fr = g.bcast0(fr, 1);
 }
 
 // pk[i] = max(E[i .. i+W1]), i < n, for E = S.mg[0 .. W1+n).  Chunks of 16: per-chunk prefix and
@@ -1012,459 +810,516 @@ __device__ __forceinline__ void sliding_max(const Wg<NW> &g, L &S, int W1, int n
 #ifndef CSDR_PC_LEAN_WAVES_PER_EU
 #define CSDR_PC_LEAN_WAVES_PER_EU 2
 #endif
+
+// What a thread of the walk knows about its launch and its channel: constant over the tile loop.
 template <int NW, bool LEAN>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 4 ? (LEAN ? CSDR_PC_LEAN_WAVES_PER_EU : CSDR_PC_WAVES_PER_EU) : 1)))
-void postchain_kernel(PcArgs a)
+struct PcThread {
+    static constexpr int NT = Wg<NW>::NT, LC = Wg<NW>::LC;
+    static constexpr bool kPrefetch = NW > 1;   // with several waves per channel a tile's samples are fetched into registers
+                                                // one tile ahead (a channel's workgroup usually has its CU to itself: nothing
+                                                // else would hide the HBM latency)
+    const PcArgs &a;
+    PcLds &S;
+    int t;
+    Wg<NW> g;
+    PcChannel &C;
+    float *g_dly, *g_mag;               // linear: last dly_n inputs, oldest first; last win_n-1 magnitudes
+    const float2 *in;
+    bool stereo;
+    PcRow row;
+    int mode;
+    bool do_sm, do_agc, agc_real, cpx_out;
+    bool defer;                         // FM with the squelch deferred: this walk ends at the raw audio (fm_squelch_launch
+                                        // does the rest, burst-parallel)
+    bool pre;                           // AGC peaks from agc_peaks_kernel: the walk neither computes nor keeps the window's
+                                        // log magnitudes
+    const float *pkrow;                 // ... but reads the channel's peaks from here
+    int D, W1, fm_warm;
+    const PcFir *fir;                   // the active demodulator's FIR, if it has one
+    int nt;
+    long total;
+};
+template <int NW, bool LEAN>
+__device__ __forceinline__ PcThread<NW, LEAN> pc_thread(const PcArgs &a, PcLds &S, int ch, int t)
 {
-    CSDR_WG_TRACE_SCOPE(a.trace, WGT_WALK);
-    using G = Wg<NW>;
-    constexpr int NT = G::NT, LC = G::LC;
-    extern __shared__ __attribute__((aligned(16))) unsigned char pc_smem[];
-    PcLds &S = *reinterpret_cast<PcLds *>(pc_smem);
-    const int ch = blockIdx.x, t = threadIdx.x;
-    // A channel's bursts are a sequential walk: this kernel is bound by its own latency, not by throughput, and
-    // in the batch chain it shares CUs with the down-converter of other groups / the next call, whose 12-16 waves
-    // per CU would otherwise take most issue slots.  Highest issue priority for these few waves costs the
-    // streaming kernel next to nothing and keeps the walk at the speed it has alone.
-    if (a.out_rows && a.out_rows[ch] < 0) return;      // muted row (its receiver has moved on): uniform per workgroup
-    __builtin_amdgcn_s_setprio(3);
-    const G g{t, t & 63, t >> 6, &S.sy};
     PcChannel &C = a.chan[ch];
-    float *g_dly = a.agc_dly + (long)ch * PC_AGC_RING * 2;      // linear: last dly_n inputs, oldest first
-    float *g_mag = a.agc_mag + (long)ch * PC_AGC_RING;          // linear: last win_n-1 magnitudes
-    const float2 *in = reinterpret_cast<const float2 *>(a.in) + (long)ch * a.in_stride;
     const bool stereo = a.flags & PC_STEREO;
-    const long orow = (long)(a.out_rows ? a.out_rows[ch] : ch) * a.out_stride;
-    float *outm = a.out ? a.out + orow : nullptr;                               // mono
-    float2 *outs = a.out ? reinterpret_cast<float2 *>(a.out) + orow : nullptr;  // stereo / complex
+    const PcRow row = a.out ? PcRow::of(a, ch) : PcRow{nullptr, nullptr, stereo};
     const int mode = (a.flags & PC_DO_DEMOD) ? C.mode : PC_MODE_NONE;
     const bool do_sm = !LEAN && (a.flags & PC_DO_SMETER), do_agc = a.flags & PC_DO_AGC, agc_real = !LEAN && (a.flags & PC_AGC_REAL);
-    const bool cpx_out = stereo || mode == PC_MODE_NONE;
-    // FM with the squelch deferred: this walk ends at the raw audio (fm_squelch_launch does the rest, burst-parallel)
     const bool defer = LEAN ? mode == PC_MODE_FM : ((a.flags & PC_FM_DEFER) && mode == PC_MODE_FM && a.burst <= 16384);
-    // AGC peaks from agc_peaks_kernel: the walk neither computes nor keeps the window's log magnitudes
     const bool pre = LEAN ? (do_agc && C.agc.on) : ((a.flags & PC_AGC_PRE) && do_agc && C.agc.on && !agc_real);
     const float *pkrow = pre ? a.pkbuf + (long)ch * a.nbursts * a.burst : nullptr;
-
-    // scalar state, identical on every thread
-    PcSMeter sm = C.sm;
-    PcAgc agc = C.agc;
-    const int D = agc.dly_n > 0 ? agc.dly_n : 1, W1 = agc.win_n > 0 ? agc.win_n - 1 : 0;
-    double am_z1 = C.am.z1;
-    double sam_z1 = C.sam.z1, sam_y1 = C.sam.y1, sam_ph = C.sam.phase, sam_fr = C.sam.freq;
-    double fm_ph = C.fm.phase, fm_fr = C.fm.freq, fm_dc = C.fm.err_dc, fm_sq = C.fm.sq_ave;
-    int fm_squelched = C.fm.squelched;
-    PcIir lp = C.fm.lp;
+    const int D = C.agc.dly_n > 0 ? C.agc.dly_n : 1, W1 = C.agc.win_n > 0 ? C.agc.win_n - 1 : 0;
     const int fm_warm = mode == PC_MODE_FM ? pll_warm_len(C.fm.alpha, C.fm.beta) : 0;
-
-    // histories -> LDS
-    if (do_agc && agc.on) {
-        for (int i = t; i < D; i += NT) S.dl[i] = make_float2(g_dly[2 * i], g_dly[2 * i + 1]);
-        if constexpr (!LEAN) if (!pre) for (int i = t; i < W1; i += NT) S.mg[i] = g_mag[i];
-    }
     const PcFir *fir = mode == PC_MODE_AM ? &C.am.fir : mode == PC_MODE_SAM ? &C.sam.fir : mode == PC_MODE_FM ? &C.fm.hp : nullptr;
-    const int nt = fir ? fir->ntaps : 1;
+    return {a, S, t, {t, t & 63, t >> 6, &S.sy}, C,
+            a.agc_dly + (long)ch * PC_AGC_RING * 2, a.agc_mag + (long)ch * PC_AGC_RING,
+            reinterpret_cast<const float2 *>(a.in) + (long)ch * a.in_stride,
+            stereo, row, mode, do_sm, do_agc, agc_real, stereo || mode == PC_MODE_NONE, defer, pre, pkrow,
+            D, W1, fm_warm, fir, fir ? fir->ntaps : 1, (long)a.nbursts * a.burst};
+}
+
+#ifdef PC_PROFILE
+#define PC_TICK(k) do { const unsigned long long now_ = __builtin_readcyclecounter(); st.tk[k] += now_ - st.tlast; st.tlast = now_; } while (0)
+#else
+#define PC_TICK(k)
+#endif
+// This thread's own registers: arrays, kept apart from the scalars of PcState so that those become values at once.
+template <int NW>
+struct PcRegs {
+    float lp_y[Wg<NW>::LC];             // one-tile FM burst: its low-passed audio, kept until the squelch decision
+    float2 nxt[Wg<NW>::LC];             // the prefetched tile
+    float nxp[Wg<NW>::LC];              // PC_AGC_PRE: the tile's peaks travel with its samples
+};
+// The running state of the channel, identical on every thread, in the order the kernel fills it from PcChannel
+struct PcState {
+    PcSMeter sm;
+    PcAgc agc;
+    double am_z1;
+    double sam_z1, sam_y1, sam_ph, sam_fr;
+    double fm_ph, fm_fr, fm_dc, fm_sq;
+    int fm_squelched;
+    PcIir lp;
+    double lp_w1, lp_w2;                // one-tile FM burst: the low-pass state behind it, kept until the squelch decision
+#ifdef PC_PROFILE
+    unsigned long long tk[16], tlast;   // (tk: zero from the kernel's initialiser)
+#endif
+};
+
+// AGC rings, FIR taps and delay line, power / biquad / PLL tables -> LDS
+template <int NW, bool LEAN>
+__device__ __forceinline__ void pc_stage_histories(const PcThread<NW, LEAN> &c, const PcState &st)
+{
+    constexpr int NT = Wg<NW>::NT;
+    PcLds &S = c.S; const PcChannel &C = c.C; const PcFir *fir = c.fir;
+    const int t = c.t, mode = c.mode, nt = c.nt;
+    if (c.do_agc && st.agc.on) {
+        for (int i = t; i < c.D; i += NT) S.dl[i] = make_float2(c.g_dly[2 * i], c.g_dly[2 * i + 1]);
+        if constexpr (!LEAN) if (!c.pre) for (int i = t; i < c.W1; i += NT) S.mg[i] = c.g_mag[i];
+    }
     if (fir) {
-        for (int i = t; i < PC_FIR_MAX + 17; i += NT) {
-            const int k = nt - 1 - (i - 4);                      // reversed, four zeros in front, zeros behind
-            const bool in = k >= 0 && k < nt;
-            S.h0[i] = in ? ((mode == PC_MODE_FM || !stereo) ? fir->coef[k] : fir->icoef[k]) : 0.f;
-            S.h1[i] = in ? fir->qcoef[k] : 0.f;
-        }
+        stage_taps<NT>(S.h0, (mode == PC_MODE_FM || !c.stereo) ? fir->coef : fir->icoef, nt, t);
+        stage_taps<NT>(S.h1, fir->qcoef, nt, t);
         // behind the tile the FIR window reads up to three more samples: zeros, never written again
         for (int i = t; i < PT + PC_FIR_MAX + 17; i += NT) { S.w0[i] = 0.f; S.w1[i] = 0.f; }
-        g.sync();
-        for (int i = t; i < nt - 1; i += NT) { S.w0[i] = (mode == PC_MODE_FM || (mode == PC_MODE_AM && !stereo)) ? fir->zreal[i] : fir->zr[i]; S.w1[i] = fir->zi[i]; }
+        c.g.sync();
+        for (int i = t; i < nt - 1; i += NT) { S.w0[i] = (mode == PC_MODE_FM || (mode == PC_MODE_AM && !c.stereo)) ? fir->zreal[i] : fir->zr[i]; S.w1[i] = fir->zi[i]; }
     }
-    pow_table(S.pw_sm, 1.0 - sm.att_a, t);
+    pow_table(S.pw_sm, 1.0 - st.sm.att_a, t);
     static_assert(refc::AM_DC_ALPHA == refc::SAM_DC_ALPHA, "one table of DC-blocker powers serves AM and SAM");
     pow_table(S.pw_dc, refc::AM_DC_ALPHA, t);
     pow_table(S.pw_sq, 1.0 - C.fm.sq_alpha, t);
     pow_table(S.pw_fd, 1.0 - C.fm.dc_alpha, t);
-    biquad_table(S.bq, lp, t);
+    biquad_table(S.bq, st.lp, t);
     if (mode == PC_MODE_FM) pll_table(S.pm, C.fm.alpha, C.fm.beta, t);
     if (mode == PC_MODE_SAM) pll_table(S.pm, C.sam.alpha, C.sam.beta, t);
-    g.sync();
+    c.g.sync();
+}
 
-    // with several waves per channel a tile's samples are fetched into registers one tile ahead (a
-    // channel's workgroup usually has its CU to itself: nothing else would hide the HBM latency)
-    constexpr bool kPrefetch = NW > 1;
-    float2 nxt[LC];
-    float nxp[LC];                                        // PC_AGC_PRE: the tile's peaks travel with its samples
-    const long total = (long)a.nbursts * a.burst;
-    auto fetch = [&](long g0, int cnt) {
+// cnt samples (and their peaks) from position g0 of the channel's input into this thread's registers
+template <int NW, bool LEAN>
+__device__ __forceinline__ void pc_fetch(const PcThread<NW, LEAN> &c, PcRegs<NW> &r, long g0, int cnt)
+{
+    constexpr int NT = Wg<NW>::NT, LC = Wg<NW>::LC;
 #pragma unroll
-        for (int j = 0; j < LC; j++) { const int i = t + NT * j; if (i < cnt) { nxt[j] = in[g0 + i]; if (pre) nxp[j] = pkrow[g0 + i]; } }
-    };
-    if (kPrefetch && total > 0) fetch(0, a.burst < PT ? a.burst : PT);
-#ifdef PC_PROFILE
-    unsigned long long tk[16] = {0}, tlast = __builtin_readcyclecounter();
-#define PC_TICK(k) do { const unsigned long long now_ = __builtin_readcyclecounter(); tk[k] += now_ - tlast; tlast = now_; } while (0)
-#else
-#define PC_TICK(k)
-#endif
-    float lp_y[LC];                                       // one-tile FM burst: its low-passed audio, kept until the squelch decision
-    double lp_w1 = 0.0, lp_w2 = 0.0;
+    for (int j = 0; j < LC; j++) { const int i = c.t + NT * j; if (i < cnt) { r.nxt[j] = c.in[g0 + i]; if (c.pre) r.nxp[j] = c.pkrow[g0 + i]; } }
+}
+// the tile at sample t0 of its burst (gi of the call) -> x[0..n), and the next one into the registers
+template <int NW, bool LEAN>
+__device__ __forceinline__ void pc_load_tile(const PcThread<NW, LEAN> &c, PcRegs<NW> &r, float2 *x, int n, long gi, int t0)
+{
+    constexpr int NT = Wg<NW>::NT, LC = Wg<NW>::LC;
+    const PcArgs &a = c.a; const int t = c.t;
+    if (c.kPrefetch) {
 #pragma unroll
-    for (int j = 0; j < LC; j++) lp_y[j] = 0.f;
-    for (int b = 0; b < a.nbursts; b++) {
+        for (int j = 0; j < LC; j++) { const int i = t + NT * j; if (i < n) { x[i] = r.nxt[j]; if (c.pre) c.S.pk[i] = r.nxp[j]; } }
+        const long gn = gi + n;                                // bursts are contiguous: the next tile follows
+        if (gn < c.total) {
+            const int left = a.burst - ((t0 + n) % a.burst);
+            pc_fetch(c, r, gn, left < PT ? left : PT);
+        }
+    } else {
+        for (int i = t; i < n; i += NT) x[i] = c.in[gi + i];
+    }
+    c.g.sync();
+}
+
+// S-meter (smeter.cpp:62-93)
+template <int NW, bool LEAN>
+__device__ __forceinline__ void pc_smeter_stage(const PcThread<NW, LEAN> &c, PcState &st, const float2 *x, int n)
+{
+    constexpr int NT = Wg<NW>::NT; PcLds &S = c.S;
+    if constexpr (!LEAN) if (c.do_sm) {
+        for (int i = c.t; i < n; i += NT) {
+            const float pw = (x[i].x * x[i].x + x[i].y * x[i].y) * refc::SM_INV_MAX_PWR_F;
+            S.w2[i] = pw > 0.f ? 10.0f * log10f(pw) : -500.0f;
+        }
+        c.g.sync();
+        smeter_tile(c.g, st.sm, S.w2, n, S.pw_sm);
+        c.g.sync();
+    }
+}
+
+// AGC (agc.cpp:174-296 / 301-401): x[0..n) in, the AGC output in place
+template <int NW, bool LEAN>
+__device__ __forceinline__ void pc_agc_stage(const PcThread<NW, LEAN> &c, PcState &st, float2 *x, int n, long gi)
+{
+    constexpr int NT = Wg<NW>::NT, LC = Wg<NW>::LC;
+    PcLds &S = c.S; PcAgc &agc = st.agc; const Wg<NW> &g = c.g; const int t = c.t;
+    if (!c.do_agc) return;
+    if (!agc.on) {
+        const float gm = (float)agc.manual_gain;
+        for (int i = t; i < n; i += NT) { x[i].x *= gm; x[i].y *= gm; }
+        g.sync();
+    } else {
+        if (c.pre) {
+            if (!c.kPrefetch) { for (int i = t; i < n; i += NT) S.pk[i] = c.pkrow[gi + i]; g.sync(); }
+        } else if constexpr (!LEAN) {
+            float *mg = S.mg + c.W1;
+            for (int i = t; i < n; i += NT) {
+                float m = fabsf(x[i].x);
+                if (!c.agc_real) { const float mi = fabsf(x[i].y); if (mi > m) m = mi; }
+                mg[i] = log10f(m + refc::AGC_MIN_CONSTANT_F) - refc::AGC_LOG10_MAX_AMPLITUDE_F;
+            }
+            g.sync();
+            // sliding maximum: pk[i] = max E[i .. i+W1], E = [W1 history | tile] = S.mg
+            PC_TICK(2);
+            sliding_max(g, S, c.W1, n);
+            PC_TICK(3);
+            keep_tail(g, S.mg, c.W1, n);                      // the last W1 magnitudes are the next tile's history
+            g.sync();
+        }
+        PC_TICK(4);
+        // attack / decay averagers -> log gain argument max(att, dec) per sample in S.pk
+        {
+            double att = agc.attack_ave, dec = agc.decay_ave;
+            bool ok = !agc.hang;                              // the hang timer is a counter: walked
+            if constexpr (NW == 4) {           // (16 samples per thread would not fit the registers twice)
+                if (ok) ok = agc_ave_scan2(g, S.pk, n, agc.att_rise, agc.att_fall, agc.dec_rise, agc.dec_fall, att, dec,
+                                           [&](int i, double va, double vd) { S.pk[i] = fmaxf((float)va, (float)vd); });
+            } else {
+                if (ok) ok = agc_ave_scan(g, S.pk, n, agc.att_rise, agc.att_fall, att,
+                                          [&](int i, double v) { S.w2[i] = (float)v; });
+                if (ok) ok = agc_ave_scan(g, S.pk, n, agc.dec_rise, agc.dec_fall, dec,
+                                          [&](int i, double v) { S.pk[i] = fmaxf(S.w2[i], (float)v); });
+            }
+            if (ok) { agc.attack_ave = att; agc.decay_ave = dec; }
+            else {
+                g.sync();
+                att = agc.attack_ave; dec = agc.decay_ave;
+                int timer = agc.hang_timer;
+                if (t == 0) {
+                    const double ar = agc.att_rise, af = agc.att_fall, dr = agc.dec_rise, df = agc.dec_fall;
+                    const bool hang = agc.hang;
+                    const int hang_time = agc.hang_time;
+                    float *dst = S.pk;
+                    seq_walk(S.pk, n, [&](float v, int i) {
+                        const double pk = v;
+                        const double da = pk - att, dd = pk - dec;
+                        att = att + (da > 0.0 ? ar : af) * da;
+                        const bool up = dd > 0.0, hold = hang && !up && timer < hang_time;
+                        dec = dec + (up ? dr : (hold ? 0.0 : df)) * dd;
+                        if (hang) timer = up ? 0 : (hold ? timer + 1 : timer);
+                        dst[i] = (float)fmax(att, dec);
+                    });
+                }
+                agc.attack_ave = g.bcast0(att, 0); agc.decay_ave = g.bcast0(dec, 1);
+                agc.hang_timer = (int)g.bcast0((double)timer, 2);
+            }
+        }
+        g.sync();
+        PC_TICK(5);
+        // gain law + delay line: out[i] = in[i - D] * gain[i]; S.dl = [D old | n new]
+        const float knee = (float)agc.knee, slm1 = (float)(agc.gain_slope - 1.0), fixed_gain = (float)agc.fixed_gain;
+        float2 outv[LC];
+#pragma unroll
+        for (int j = 0; j < LC; j++) {
+            const int i = t + NT * j;
+            if (i < n) {
+                const float m = S.pk[i];
+                const float gv = (m <= knee) ? fixed_gain : 0.7f * exp10f(m * slm1);
+                const float2 d = S.dl[i];
+                outv[j] = make_float2(d.x * gv, d.y * gv);
+            }
+        }
+        keep_tail(g, S.dl, c.D, n);
+#pragma unroll
+        for (int j = 0; j < LC; j++) { const int i = t + NT * j; if (i < n) x[i] = outv[j]; }
+        g.sync();
+    }
+}
+
+// no demodulator, or SSB / CW: the AGC output is the audio (ssbdemod.cpp:48-53)
+template <int NW, bool LEAN>
+__device__ __forceinline__ void pc_ssb_tile(const PcThread<NW, LEAN> &c, const float2 *x, int n, long gi)
+{
+    if (c.a.out)
+        for (int i = c.t; i < n; i += Wg<NW>::NT) { if (c.cpx_out) c.row.s[gi + i] = x[i]; else c.row.m[gi + i] = x[i].x; }
+    c.g.sync();
+}
+
+// CAmDemod (amdemod.cpp:66-104)
+template <int NW, bool LEAN>
+__device__ __forceinline__ void pc_am_tile(const PcThread<NW, LEAN> &c, PcState &st, const float2 *x, int n, long gi)
+{
+    constexpr int NT = Wg<NW>::NT, LC = Wg<NW>::LC;
+    PcLds &S = c.S; const Wg<NW> &g = c.g; const int t = c.t, nt = c.nt;
+    float *w = S.w0 + (nt - 1);
+    for (int i = t; i < n; i += NT) w[i] = sqrtf(x[i].x * x[i].x + x[i].y * x[i].y);
+    g.sync();
+    // DC block z0 = x + 0.99 z1, out = z0 - z1 (amdemod.cpp:70-80)
+    st.am_z1 = lin1_scan<true>(g, w, n, refc::AM_DC_ALPHA, 1.0, st.am_z1, S.pw_dc,
+                               [&](int i, float, double z0, double z1) { w[i] = (float)(z0 - z1); });
+    g.sync();
+    float acc[LC], acq[LC];
+    fir_blk<NW>(S.h0, nt, S.w0, t, acc);
+    if (c.stereo) {
+        fir_blk<NW>(S.h1, nt, S.w0, t, acq);
+#pragma unroll
+        for (int j = 0; j < LC; j++) { const int i = pc_out_index<NW>(t, j); if (i < n) c.row.s[gi + i] = make_float2(acc[j], acq[j]); }
+    } else {
+#pragma unroll
+        for (int j = 0; j < LC; j++) { const int i = pc_out_index<NW>(t, j); if (i < n) c.row.m[gi + i] = acc[j]; }
+    }
+    g.sync();
+    slide(g, S.w0, nt - 1, n);
+    g.sync();
+}
+
+// CFmDemod (fmdemod.cpp:113-236) up to the end-of-burst squelch
+template <int NW, bool LEAN>
+__device__ __forceinline__ void pc_fm_tile(const PcThread<NW, LEAN> &c, PcState &st, PcRegs<NW> &r, const float2 *x, int n, long gi)
+{
+    constexpr int NT = Wg<NW>::NT, LC = Wg<NW>::LC;
+    PcLds &S = c.S; const PcArgs &a = c.a; const Wg<NW> &g = c.g; const int t = c.t, nt = c.nt;
+    float *th = S.w1 + (nt - 1), *au = S.w0 + (nt - 1);
+    const PcFm &F = c.C.fm;
+    const auto to_au = [&](int i, double, double f) { au[i] = (float)f; };           // NCO frequency, turns per sample
+    double ph = st.fm_ph * kInvTwoPiD, fr = st.fm_fr * kInvTwoPiD;                   // (the solvers move them only when they succeed)
+    bool scanned = pll_scan(g, th, n, F.alpha, F.beta, F.lo * kInvTwoPiD, F.hi * kInvTwoPiD, ph, fr, S.pm, to_au);
+    if (!scanned && c.fm_warm <= PC_PLL_WARM_MAX && !(a.flags & PC_PLL_SEQ)) {       // unlocked: overlapped exact walks, verified
+        g.sync();
+        ph = wrap_turn(ph);
+        scanned = pll_overlap(g, th, n, c.fm_warm, F.alpha, F.beta, F.lo * kInvTwoPiD, F.hi * kInvTwoPiD, ph, fr,
+                              reinterpret_cast<double *>(&S.rt[0][0]), reinterpret_cast<double *>(S.w2), to_au);
+    }
+    if (scanned) { st.fm_ph = ph * kTwoPiD; st.fm_fr = fr * kTwoPiD; }
+    else pll_walk(g, th, n, F.alpha, F.beta, F.lo, F.hi, 1.0, st.fm_ph, st.fm_fr, to_au);
+    g.sync();
+    PC_TICK(8);
+    {   // audio = (freq - its running mean) * gain  (fmdemod.cpp:178-186): the mean is linear
+        const double og = F.out_gain * kTwoPiD;
+        st.fm_dc = kTwoPiD * lin1_scan<true>(g, au, n, 1.0 - F.dc_alpha, F.dc_alpha, st.fm_dc * kInvTwoPiD, S.pw_fd,
+                    [&](int i, float f, double dc, double) { au[i] = (float)(((double)f - dc) * og); });
+    }
+    g.sync();
+    PC_TICK(9);
+    // raw audio to the output row; squelch is decided at the end of the burst (a burst of one tile
+    // keeps it in LDS instead: the low-pass at the end of the burst reads it from there)
+    if (a.burst > PT || c.defer)
+        for (int i = t; i < n; i += NT) c.row.put(gi + i, au[i]);
+    if constexpr (!LEAN) if (a.burst <= 16384 && !c.defer) {                     // MAX_SQBUF_SIZE
+        float acc[LC];
+        fir_blk<NW>(S.h0, nt, S.w0, t, acc);
+#pragma unroll
+        for (int j = 0; j < LC; j++) S.w2[pc_out_index<NW>(t, j) & (PT - 1)] = fabsf(acc[j]);
+        g.sync();
+        if constexpr (NW == 4) {
+            if (a.burst <= PT) st.fm_sq = sq_and_lowpass(g, S.w2, au, n, 1.0 - F.sq_alpha, F.sq_alpha, st.fm_sq, S.pw_sq, st.lp, S.bq,
+                                                         r.lp_y, st.lp_w1, st.lp_w2);
+            else st.fm_sq = lin1_scan<false>(g, S.w2, n, 1.0 - F.sq_alpha, F.sq_alpha, st.fm_sq, S.pw_sq,
+                                             [](int, float, double, double) {});
+        } else
+        st.fm_sq = lin1_scan<false>(g, S.w2, n, 1.0 - F.sq_alpha, F.sq_alpha, st.fm_sq, S.pw_sq,
+                                    [](int, float, double, double) {});
+    }
+    g.sync();
+    PC_TICK(10);
+    if (!c.defer) {
+        slide(g, S.w0, nt - 1, n);
+        g.sync();
+    }
+    PC_TICK(11);
+}
+
+// CSamDemod (samdemod.cpp:78-158)
+template <int NW, bool LEAN>
+__device__ __forceinline__ void pc_sam_tile(const PcThread<NW, LEAN> &c, PcState &st, const float2 *x, int n, long gi)
+{
+    constexpr int NT = Wg<NW>::NT, LC = Wg<NW>::LC;
+    PcLds &S = c.S; const Wg<NW> &g = c.g; const int t = c.t, nt = c.nt; const bool stereo = c.stereo;
+    float *th = S.w1 + (nt - 1), *au = S.w0 + (nt - 1);
+    const PcSam &M = c.C.sam;
+    const double sgn = stereo ? 1.0 : -1.0;
+    // in psi = sgn phi, g = sgn f the loop has the FM form with theta as is
+    double ps = sgn * st.sam_ph * kInvTwoPiD, gf = sgn * st.sam_fr * kInvTwoPiD;
+    const double l0 = M.lo * kInvTwoPiD, h0 = M.hi * kInvTwoPiD;
+    if (pll_scan(g, th, n, M.alpha, M.beta, sgn > 0 ? l0 : -h0, sgn > 0 ? h0 : -l0, ps, gf, S.pm,
+                 [&](int i, double p, double) { S.w2[i] = (float)(sgn * (p - rint(p))); })) {
+        st.sam_ph = sgn * ps * kTwoPiD; st.sam_fr = sgn * gf * kTwoPiD;
+    } else pll_walk(g, th, n, M.alpha, M.beta, M.lo, M.hi, sgn, st.sam_ph, st.sam_fr,
+                           [&](int i, double p, double) { S.w2[i] = (float)p; });     // phase used for this sample (turns)
+    g.sync();
+    // rotated sample tr + j ti = |x| e^{j(theta + sgn phi)}
+    for (int i = t; i < n; i += NT) {
+        const float r = sqrtf(x[i].x * x[i].x + x[i].y * x[i].y);
+        float sn, cs;
+        sincospif(2.0f * (th[i] + (float)sgn * S.w2[i]), &sn, &cs);
+        au[i] = r * cs;                                   // tr
+        th[i] = r * sn;                                   // ti
+    }
+    g.sync();
+    // DC blocks
+    st.sam_z1 = lin1_scan<true>(g, au, n, refc::SAM_DC_ALPHA, 1.0, st.sam_z1, S.pw_dc,
+                                [&](int i, float, double z0, double z1) { au[i] = (float)(z0 - z1); });
+    if (stereo)
+        st.sam_y1 = lin1_scan<true>(g, th, n, refc::SAM_DC_ALPHA, 1.0, st.sam_y1, S.pw_dc,
+                                    [&](int i, float, double y0, double y1) { th[i] = (float)(y0 - y1); });
+    g.sync();
+    if (!stereo) {
+        for (int i = t; i < n; i += NT) c.row.m[gi + i] = au[i];
+    } else {
+        float ar[LC], ai[LC];
+        fir_blk<NW>(S.h0, nt, S.w0, t, ar);
+        fir_blk<NW>(S.h1, nt, S.w1, t, ai);
+#pragma unroll
+        for (int j = 0; j < LC; j++) {                    // lower sideband left, upper right
+            const int i = pc_out_index<NW>(t, j);
+            if (i < n) c.row.s[gi + i] = make_float2(ar[j] + ai[j], ar[j] - ai[j]);
+        }
+        g.sync();
+        slide(g, S.w0, nt - 1, n);
+        slide(g, S.w1, nt - 1, n);
+    }
+    g.sync();
+}
+
+// end of burst b: FM squelch decision (fmdemod.cpp:128-151), then zeros or the audio low-pass over the burst
+template <int NW, bool LEAN>
+__device__ __forceinline__ void pc_fm_burst_end(const PcThread<NW, LEAN> &c, PcState &st, const PcRegs<NW> &r, int b)
+{
+    constexpr int NT = Wg<NW>::NT, LC = Wg<NW>::LC;
+    PcLds &S = c.S; const PcArgs &a = c.a; const Wg<NW> &g = c.g; const int t = c.t;
+    if constexpr (!LEAN) if (c.mode == PC_MODE_FM && a.burst <= 16384 && !c.defer) {
+        st.fm_squelched = squelch_decide(st.fm_sq, c.C.fm.sq_thresh, st.fm_squelched);
+        const long g0 = (long)b * a.burst;
+        g.sync();
         for (int t0 = 0; t0 < a.burst; t0 += PT) {
             const int n = (a.burst - t0) < PT ? (a.burst - t0) : PT;
-            const long gi = (long)b * a.burst + t0;
-            float2 *x = S.dl + ((do_agc && agc.on) ? D : 0);           // tile samples (AGC: behind the delay history)
-            if (kPrefetch) {
+            if (st.fm_squelched) {
+                for (int i = t; i < n; i += NT) c.row.put(g0 + t0 + i, 0.f);
+            } else if (NW == 4 && a.burst <= PT) {                    // the low-pass ran with the squelch average: commit it
 #pragma unroll
-                for (int j = 0; j < LC; j++) { const int i = t + NT * j; if (i < n) { x[i] = nxt[j]; if (pre) S.pk[i] = nxp[j]; } }
-                const long gn = gi + n;                                // bursts are contiguous: the next tile follows
-                if (gn < total) {
-                    const int left = a.burst - ((t0 + n) % a.burst);
-                    fetch(gn, left < PT ? left : PT);
+                for (int j = 0; j < LC; j++) {
+                    const int i = LC * t + j;
+                    if (i < n) c.row.put(g0 + i, r.lp_y[j]);
                 }
-            } else {
-                for (int i = t; i < n; i += NT) x[i] = in[gi + i];
-            }
-            g.sync();
-            PC_TICK(0);
-            // ---------------- S-meter (smeter.cpp:62-93) ----------------
-            if constexpr (!LEAN) if (do_sm) {
-                for (int i = t; i < n; i += NT) {
-                    const float pw = (x[i].x * x[i].x + x[i].y * x[i].y) * refc::SM_INV_MAX_PWR_F;
-                    S.w2[i] = pw > 0.f ? 10.0f * log10f(pw) : -500.0f;
-                }
+                st.lp.w1a = st.lp_w1; st.lp.w2a = st.lp_w2;
+            } else {                                                  // low-pass biquad over the burst
+                if (a.burst > PT) { for (int i = t; i < n; i += NT) S.w2[i] = c.row.raw(g0 + t0 + i); }
+                else { const float *au = S.w0 + (c.nt - 1); for (int i = t; i < n; i += NT) S.w2[i] = au[i]; }
                 g.sync();
-                smeter_tile(g, sm, S.w2, n, S.pw_sm);
+                biquad_scan(g, S.w2, n, st.lp, S.bq);
                 g.sync();
-            }
-            PC_TICK(1);
-            // ---------------- AGC (agc.cpp:174-296 / 301-401) ----------------
-            if (do_agc) {
-                if (!agc.on) {
-                    const float gm = (float)agc.manual_gain;
-                    for (int i = t; i < n; i += NT) { x[i].x *= gm; x[i].y *= gm; }
-                    g.sync();
-                } else {
-                    if (pre) {
-                        if (!kPrefetch) { for (int i = t; i < n; i += NT) S.pk[i] = pkrow[gi + i]; g.sync(); }
-                    } else if constexpr (!LEAN) {
-                        float *mg = S.mg + W1;
-                        for (int i = t; i < n; i += NT) {
-                            float m = fabsf(x[i].x);
-                            if (!agc_real) { const float mi = fabsf(x[i].y); if (mi > m) m = mi; }
-                            mg[i] = log10f(m + refc::AGC_MIN_CONSTANT_F) - refc::AGC_LOG10_MAX_AMPLITUDE_F;
-                        }
-                        g.sync();
-                        // sliding maximum: pk[i] = max E[i .. i+W1], E = [W1 history | tile] = S.mg
-                        PC_TICK(2);
-                        sliding_max(g, S, W1, n);
-                        PC_TICK(3);
-                        // the last W1 magnitudes are the next tile's history: read all, one barrier, write all
-                        {
-                            float keepm[PH / NT];
-#pragma unroll
-                            for (int j = 0; j < PH / NT; j++) { const int i = t + NT * j; if (i < W1) keepm[j] = S.mg[n + i]; }
-                            g.sync();
-#pragma unroll
-                            for (int j = 0; j < PH / NT; j++) { const int i = t + NT * j; if (i < W1) S.mg[i] = keepm[j]; }
-                            g.sync();
-                        }
-                    }
-                    PC_TICK(4);
-                    // attack / decay averagers -> log gain argument max(att, dec) per sample in S.pk
-                    {
-                        double att = agc.attack_ave, dec = agc.decay_ave;
-                        bool ok = !agc.hang;                              // the hang timer is a counter: walked
-                        if constexpr (NW == 4) {           // (16 samples per thread would not fit the registers twice)
-                            if (ok) ok = agc_ave_scan2(g, S.pk, n, agc.att_rise, agc.att_fall, agc.dec_rise, agc.dec_fall, att, dec,
-                                                       [&](int i, double va, double vd) { S.pk[i] = fmaxf((float)va, (float)vd); });
-                        } else {
-                            if (ok) ok = agc_ave_scan(g, S.pk, n, agc.att_rise, agc.att_fall, att,
-                                                      [&](int i, double v) { S.w2[i] = (float)v; });
-                            if (ok) ok = agc_ave_scan(g, S.pk, n, agc.dec_rise, agc.dec_fall, dec,
-                                                      [&](int i, double v) { S.pk[i] = fmaxf(S.w2[i], (float)v); });
-                        }
-                        if (ok) { agc.attack_ave = att; agc.decay_ave = dec; }
-                        else {
-                            g.sync();
-                            att = agc.attack_ave; dec = agc.decay_ave;
-                            int timer = agc.hang_timer;
-                            if (t == 0) {
-                                const double ar = agc.att_rise, af = agc.att_fall, dr = agc.dec_rise, df = agc.dec_fall;
-                                const bool hang = agc.hang;
-                                const int hang_time = agc.hang_time;
-                                float *dst = S.pk;
-                                seq_walk(S.pk, n, [&](float v, int i) {
-                                    const double pk = v;
-                                    const double da = pk - att, dd = pk - dec;
-                                    att = att + (da > 0.0 ? ar : af) * da;
-                                    const bool up = dd > 0.0, hold = hang && !up && timer < hang_time;
-                                    dec = dec + (up ? dr : (hold ? 0.0 : df)) * dd;
-                                    if (hang) timer = up ? 0 : (hold ? timer + 1 : timer);
-                                    dst[i] = (float)fmax(att, dec);
-                                });
-                            }
-                            agc.attack_ave = g.bcast0(att, 0); agc.decay_ave = g.bcast0(dec, 1);
-                            agc.hang_timer = (int)g.bcast0((double)timer, 2);
-                        }
-                    }
-                    g.sync();
-                    PC_TICK(5);
-                    // gain law + delay line: out[i] = in[i - D] * gain[i]; S.dl = [D old | n new]
-                    const float knee = (float)agc.knee, slm1 = (float)(agc.gain_slope - 1.0), fixed_gain = (float)agc.fixed_gain;
-                    float2 outv[LC];
-#pragma unroll
-                    for (int j = 0; j < LC; j++) {
-                        const int i = t + NT * j;
-                        if (i < n) {
-                            const float m = S.pk[i];
-                            const float gv = (m <= knee) ? fixed_gain : 0.7f * exp10f(m * slm1);
-                            const float2 d = S.dl[i];
-                            outv[j] = make_float2(d.x * gv, d.y * gv);
-                        }
-                    }
-                    float2 keepd[PH / NT];
-#pragma unroll
-                    for (int j = 0; j < PH / NT; j++) { const int i = t + NT * j; if (i < D) keepd[j] = S.dl[n + i]; }
-                    g.sync();
-#pragma unroll
-                    for (int j = 0; j < PH / NT; j++) { const int i = t + NT * j; if (i < D) S.dl[i] = keepd[j]; }
-#pragma unroll
-                    for (int j = 0; j < LC; j++) { const int i = t + NT * j; if (i < n) x[i] = outv[j]; }
-                    g.sync();
-                }
-            }
-            PC_TICK(6);
-            // x[0..n) now holds the AGC output (or the input); x = S.dl + D
-            // ---------------- demodulators ----------------
-            if (mode == PC_MODE_NONE || mode >= PC_MODE_USB) {
-                if (a.out) {
-                    for (int i = t; i < n; i += NT) {
-                        if (cpx_out) outs[gi + i] = x[i];
-                        else outm[gi + i] = x[i].x;                       // ssbdemod.cpp:48-53
-                    }
-                }
+                for (int i = t; i < n; i += NT) c.row.put(g0 + t0 + i, S.w2[i]);
                 g.sync();
-            } else if (mode == PC_MODE_AM) {
-                float *w = S.w0 + (nt - 1);
-                for (int i = t; i < n; i += NT) w[i] = sqrtf(x[i].x * x[i].x + x[i].y * x[i].y);
-                g.sync();
-                // DC block z0 = x + 0.99 z1, out = z0 - z1 (amdemod.cpp:70-80)
-                am_z1 = lin1_scan<true>(g, w, n, refc::AM_DC_ALPHA, 1.0, am_z1, S.pw_dc,
-                                        [&](int i, float, double z0, double z1) { w[i] = (float)(z0 - z1); });
-                g.sync();
-                float acc[LC], acq[LC];
-                fir_blk<NW>(S.h0, nt, S.w0, t, acc);
-                if (stereo) {
-                    fir_blk<NW>(S.h1, nt, S.w0, t, acq);
-#pragma unroll
-                    for (int j = 0; j < LC; j++) { const int i = pc_out_index<NW>(t, j); if (i < n) outs[gi + i] = make_float2(acc[j], acq[j]); }
-                } else {
-#pragma unroll
-                    for (int j = 0; j < LC; j++) { const int i = pc_out_index<NW>(t, j); if (i < n) outm[gi + i] = acc[j]; }
-                }
-                g.sync();
-                slide(g, S.w0, nt - 1, n);
-                g.sync();
-            } else {
-                // PLL modes: theta = arg(x) for the whole tile, in turns
-                float *th = S.w1 + (nt - 1), *au = S.w0 + (nt - 1);
-                for (int i = t; i < n; i += NT) th[i] = pll_theta_of(x[i].x, x[i].y);
-                g.sync();
-                PC_TICK(7);
-                if (mode == PC_MODE_FM) {
-                    const PcFm &F = C.fm;
-                    bool scanned;
-                    {
-                        double ph = fm_ph * kInvTwoPiD, fr = fm_fr * kInvTwoPiD;
-                        scanned = pll_scan(g, th, n, F.alpha, F.beta, F.lo * kInvTwoPiD, F.hi * kInvTwoPiD, ph, fr, S.pm,
-                                           [&](int i, double, double f) { au[i] = (float)f; });
-                        if (scanned) { fm_ph = ph * kTwoPiD; fm_fr = fr * kTwoPiD; }
-                    }
-                    if (!scanned && fm_warm <= PC_PLL_WARM_MAX && !(a.flags & PC_PLL_SEQ)) {       // unlocked: overlapped exact walks, verified
-                        g.sync();
-                        double ph = fm_ph * kInvTwoPiD, fr = fm_fr * kInvTwoPiD;
-                        ph = wrap_turn(ph);
-                        scanned = pll_overlap(g, th, n, fm_warm, F.alpha, F.beta, F.lo * kInvTwoPiD, F.hi * kInvTwoPiD, ph, fr,
-                                              reinterpret_cast<double *>(&S.rt[0][0]), reinterpret_cast<double *>(S.w2),
-                                              [&](int i, double, double f) { au[i] = (float)f; });
-                        if (scanned) { fm_ph = ph * kTwoPiD; fm_fr = fr * kTwoPiD; }
-                    }
-                    if (!scanned) {
-                        g.sync();
-                        if (t == 0) {
-                            // phase, frequency and error in turns: wrapping is a - rint(a)
-                            const double beta = F.beta, alpha = F.alpha, hi = F.hi * kInvTwoPiD, lo = F.lo * kInvTwoPiD;
-                            double ph = fm_ph * kInvTwoPiD, fr = fm_fr * kInvTwoPiD;
-                            seq_walk(th, n, [&](float v, int i) {              // fmdemod.cpp:166-177
-                                const double err = pll_theta_is_zero_code(v) ? pll_zero_err(v, ph, 1.0) : -wrap_turn((double)v + ph);
-                                fr = fmin(fmax(fr + beta * err, lo), hi);
-                                ph = wrap_turn(ph + fr + alpha * err);
-                                au[i] = (float)fr;                             // NCO frequency, turns per sample
-                            });
-                            fm_ph = ph * kTwoPiD; fm_fr = fr * kTwoPiD;
-                        }
-                        fm_ph = g.bcast0(fm_ph, 0); fm_fr = g.bcast0(fm_fr, 1);
-                    }
-                    g.sync();
-                    PC_TICK(8);
-                    {   // audio = (freq - its running mean) * gain  (fmdemod.cpp:178-186): the mean is linear
-                        const double og = F.out_gain * kTwoPiD;
-                        fm_dc = kTwoPiD * lin1_scan<true>(g, au, n, 1.0 - F.dc_alpha, F.dc_alpha, fm_dc * kInvTwoPiD, S.pw_fd,
-                                    [&](int i, float f, double dc, double) { au[i] = (float)(((double)f - dc) * og); });
-                    }
-                    g.sync();
-                    PC_TICK(9);
-                    // raw audio to the output row; squelch is decided at the end of the burst (a burst of one tile
-                    // keeps it in LDS instead: the low-pass at the end of the burst reads it from there)
-                    if (a.burst > PT || defer)
-                        for (int i = t; i < n; i += NT) { if (stereo) outs[gi + i] = make_float2(au[i], au[i]); else outm[gi + i] = au[i]; }
-                    if constexpr (!LEAN) if (a.burst <= 16384 && !defer) {                     // MAX_SQBUF_SIZE
-                        float acc[LC];
-                        fir_blk<NW>(S.h0, nt, S.w0, t, acc);
-#pragma unroll
-                        for (int j = 0; j < LC; j++) S.w2[pc_out_index<NW>(t, j) & (PT - 1)] = fabsf(acc[j]);
-                        g.sync();
-                        if constexpr (NW == 4) {
-                            if (a.burst <= PT) fm_sq = sq_and_lowpass(g, S.w2, au, n, 1.0 - F.sq_alpha, F.sq_alpha, fm_sq, S.pw_sq, lp, S.bq,
-                                                                      lp_y, lp_w1, lp_w2);
-                            else fm_sq = lin1_scan<false>(g, S.w2, n, 1.0 - F.sq_alpha, F.sq_alpha, fm_sq, S.pw_sq,
-                                                          [](int, float, double, double) {});
-                        } else
-                        fm_sq = lin1_scan<false>(g, S.w2, n, 1.0 - F.sq_alpha, F.sq_alpha, fm_sq, S.pw_sq,
-                                                 [](int, float, double, double) {});
-                    }
-                    g.sync();
-                    PC_TICK(10);
-                    if (!defer) {
-                        slide(g, S.w0, nt - 1, n);
-                        g.sync();
-                    }
-                    PC_TICK(11);
-                } else {                                                  // SAM, samdemod.cpp:78-158
-                    const PcSam &M = C.sam;
-                    const double sgn = stereo ? 1.0 : -1.0;
-                    bool scanned;
-                    {   // in psi = sgn phi, g = sgn f the loop has the FM form with theta as is
-                        double ps = sgn * sam_ph * kInvTwoPiD, gf = sgn * sam_fr * kInvTwoPiD;
-                        const double l0 = M.lo * kInvTwoPiD, h0 = M.hi * kInvTwoPiD;
-                        scanned = pll_scan(g, th, n, M.alpha, M.beta, sgn > 0 ? l0 : -h0, sgn > 0 ? h0 : -l0, ps, gf, S.pm,
-                                           [&](int i, double p, double) { S.w2[i] = (float)(sgn * (p - rint(p))); });
-                        if (scanned) { sam_ph = sgn * ps * kTwoPiD; sam_fr = sgn * gf * kTwoPiD; }
-                    }
-                    if (!scanned) {
-                        g.sync();
-                        if (t == 0) {
-                            const double beta = M.beta, alpha = M.alpha, hi = M.hi * kInvTwoPiD, lo = M.lo * kInvTwoPiD;
-                            double ph = sam_ph * kInvTwoPiD, fr = sam_fr * kInvTwoPiD;
-                            seq_walk(th, n, [&](float v, int i) {
-                                S.w2[i] = (float)ph;                          // phase used for this sample (turns)
-                                const double err = pll_theta_is_zero_code(v) ? pll_zero_err(v, ph, sgn) : -sgn * wrap_turn((double)v + sgn * ph);
-                                fr = fmin(fmax(fr + beta * err, lo), hi);
-                                ph = wrap_turn(ph + fr + alpha * err);
-                            });
-                            sam_ph = ph * kTwoPiD; sam_fr = fr * kTwoPiD;
-                        }
-                        sam_ph = g.bcast0(sam_ph, 0); sam_fr = g.bcast0(sam_fr, 1);
-                    }
-                    g.sync();
-                    // rotated sample tr + j ti = |x| e^{j(theta + sgn phi)}
-                    for (int i = t; i < n; i += NT) {
-                        const float r = sqrtf(x[i].x * x[i].x + x[i].y * x[i].y);
-                        float sn, cs;
-                        sincospif(2.0f * (th[i] + (float)sgn * S.w2[i]), &sn, &cs);
-                        au[i] = r * cs;                                   // tr
-                        th[i] = r * sn;                                   // ti
-                    }
-                    g.sync();
-                    // DC blocks
-                    sam_z1 = lin1_scan<true>(g, au, n, refc::SAM_DC_ALPHA, 1.0, sam_z1, S.pw_dc,
-                                             [&](int i, float, double z0, double z1) { au[i] = (float)(z0 - z1); });
-                    if (stereo)
-                        sam_y1 = lin1_scan<true>(g, th, n, refc::SAM_DC_ALPHA, 1.0, sam_y1, S.pw_dc,
-                                                 [&](int i, float, double y0, double y1) { th[i] = (float)(y0 - y1); });
-                    g.sync();
-                    if (!stereo) {
-                        for (int i = t; i < n; i += NT) outm[gi + i] = au[i];
-                    } else {
-                        float ar[LC], ai[LC];
-                        fir_blk<NW>(S.h0, nt, S.w0, t, ar);
-                        fir_blk<NW>(S.h1, nt, S.w1, t, ai);
-#pragma unroll
-                        for (int j = 0; j < LC; j++) {                    // lower sideband left, upper right
-                            const int i = pc_out_index<NW>(t, j);
-                            if (i < n) outs[gi + i] = make_float2(ar[j] + ai[j], ar[j] - ai[j]);
-                        }
-                        g.sync();
-                        slide(g, S.w0, nt - 1, n);
-                        slide(g, S.w1, nt - 1, n);
-                    }
-                    g.sync();
-                }
-            }
-        }
-        // ---------------- end of burst: FM squelch decision (fmdemod.cpp:128-151) ----------------
-        if constexpr (!LEAN) if (mode == PC_MODE_FM && a.burst <= 16384 && !defer) {
-            const PcFm &F = C.fm;
-            if (0 == F.sq_thresh) fm_squelched = 1;
-            else if (fm_squelched) { if (fm_sq < (F.sq_thresh - refc::FM_SQUELCH_HYSTERESIS)) fm_squelched = 0; }
-            else { if (fm_sq >= (F.sq_thresh + refc::FM_SQUELCH_HYSTERESIS)) fm_squelched = 1; }
-            const long g0 = (long)b * a.burst;
-            g.sync();
-            for (int t0 = 0; t0 < a.burst; t0 += PT) {
-                const int n = (a.burst - t0) < PT ? (a.burst - t0) : PT;
-                if (fm_squelched) {
-                    for (int i = t; i < n; i += NT) { if (stereo) outs[g0 + t0 + i] = make_float2(0.f, 0.f); else outm[g0 + t0 + i] = 0.f; }
-                } else if (NW == 4 && a.burst <= PT) {                    // the low-pass ran with the squelch average: commit it
-#pragma unroll
-                    for (int j = 0; j < LC; j++) {
-                        const int i = LC * t + j;
-                        if (i < n) { if (stereo) outs[g0 + i] = make_float2(lp_y[j], lp_y[j]); else outm[g0 + i] = lp_y[j]; }
-                    }
-                    lp.w1a = lp_w1; lp.w2a = lp_w2;
-                } else {                                                  // low-pass biquad over the burst
-                    if (a.burst > PT) { for (int i = t; i < n; i += NT) S.w2[i] = stereo ? outs[g0 + t0 + i].x : outm[g0 + t0 + i]; }
-                    else { const float *au = S.w0 + (nt - 1); for (int i = t; i < n; i += NT) S.w2[i] = au[i]; }
-                    g.sync();
-                    biquad_scan(g, S.w2, n, lp, S.bq);
-                    g.sync();
-                    for (int i = t; i < n; i += NT) { const float y = S.w2[i]; if (stereo) outs[g0 + t0 + i] = make_float2(y, y); else outm[g0 + t0 + i] = y; }
-                    g.sync();
-                }
             }
         }
     }
+}
 
-    PC_TICK(12);
-#ifdef PC_PROFILE
-    if (blockIdx.x == 0 && t == 0)
-        printf("pcprof mode %d: load %llu smeter %llu agcmag %llu slmax %llu histmove %llu aver %llu gain %llu atan %llu pll %llu dc %llu sqfir %llu slide %llu burstend %llu\n",
-               mode, tk[0], tk[1], tk[2], tk[3], tk[4], tk[5], tk[6], tk[7], tk[8], tk[9], tk[10], tk[11], tk[12]);
-#endif
-    // ---------------- write the state back ----------------
-    g.sync();
-    if (do_agc && agc.on) {
-        for (int i = t; i < D; i += NT) { g_dly[2 * i] = S.dl[i].x; g_dly[2 * i + 1] = S.dl[i].y; }
-        if (pre) { const float *tail = a.magtail + (long)ch * PC_AGC_RING; for (int i = t; i < W1; i += NT) g_mag[i] = tail[i]; }
-        else if constexpr (!LEAN) for (int i = t; i < W1; i += NT) g_mag[i] = S.mg[i];
+// write the state back
+template <int NW, bool LEAN>
+__device__ __forceinline__ void pc_store_state(const PcThread<NW, LEAN> &c, const PcState &st, int ch)
+{
+    constexpr int NT = Wg<NW>::NT;
+    PcLds &S = c.S; PcChannel &C = c.C; const int t = c.t, mode = c.mode;
+    c.g.sync();
+    if (c.do_agc && st.agc.on) {
+        for (int i = t; i < c.D; i += NT) { c.g_dly[2 * i] = S.dl[i].x; c.g_dly[2 * i + 1] = S.dl[i].y; }
+        if (c.pre) { const float *tail = c.a.magtail + (long)ch * PC_AGC_RING; for (int i = t; i < c.W1; i += NT) c.g_mag[i] = tail[i]; }
+        else if constexpr (!LEAN) for (int i = t; i < c.W1; i += NT) c.g_mag[i] = S.mg[i];
     }
-    if (fir && !defer) {
-        PcFir *fw = const_cast<PcFir *>(fir);
-        for (int i = t; i < nt - 1; i += NT) {
-            if (mode == PC_MODE_FM || (mode == PC_MODE_AM && !stereo)) fw->zreal[i] = S.w0[i];
+    if (c.fir && !c.defer) {
+        PcFir *fw = const_cast<PcFir *>(c.fir);
+        for (int i = t; i < c.nt - 1; i += NT) {
+            if (mode == PC_MODE_FM || (mode == PC_MODE_AM && !c.stereo)) fw->zreal[i] = S.w0[i];
             else { fw->zr[i] = S.w0[i]; fw->zi[i] = mode == PC_MODE_AM ? S.w0[i] : S.w1[i]; }
         }
     }
     // each stage writes only its own state: the stages of one channel may run as separate,
     // concurrent launches (S-meter | AGC | demodulator pipeline of the batch chain)
     if (t == 0) {
-        if (do_sm) C.sm = sm;
-        if (do_agc) C.agc = agc;
-        if (mode == PC_MODE_AM) C.am.z1 = am_z1;
-        if (mode == PC_MODE_SAM) { C.sam.z1 = sam_z1; C.sam.y1 = sam_y1; C.sam.phase = sam_ph; C.sam.freq = sam_fr; }
+        if (c.do_sm) C.sm = st.sm;
+        if (c.do_agc) C.agc = st.agc;
+        if (mode == PC_MODE_AM) C.am.z1 = st.am_z1;
+        if (mode == PC_MODE_SAM) { C.sam.z1 = st.sam_z1; C.sam.y1 = st.sam_y1; C.sam.phase = st.sam_ph; C.sam.freq = st.sam_fr; }
         if (mode == PC_MODE_FM) {
-            C.fm.phase = fm_ph; C.fm.freq = fm_fr; C.fm.err_dc = fm_dc;
-            if (!defer) { C.fm.sq_ave = fm_sq; C.fm.squelched = fm_squelched; C.fm.lp = lp; }   // else: fm_squelch_decide_kernel's
+            C.fm.phase = st.fm_ph; C.fm.freq = st.fm_fr; C.fm.err_dc = st.fm_dc;
+            if (!c.defer) { C.fm.sq_ave = st.fm_sq; C.fm.squelched = st.fm_squelched; C.fm.lp = st.lp; }   // else: fm_squelch_decide_kernel's
         }
     }
+}
+
+template <int NW, bool LEAN>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 4 ? (LEAN ? CSDR_PC_LEAN_WAVES_PER_EU : CSDR_PC_WAVES_PER_EU) : 1)))
+void postchain_kernel(PcArgs a)
+{
+    CSDR_WG_TRACE_SCOPE(a.trace, WGT_WALK);
+    extern __shared__ __attribute__((aligned(16))) unsigned char pc_smem[];
+    PcLds &S = *reinterpret_cast<PcLds *>(pc_smem);
+    const int ch = blockIdx.x;
+    // A channel's bursts are a sequential walk: this kernel is bound by its own latency, not by throughput, and
+    // in the batch chain it shares CUs with the down-converter of other groups / the next call, whose 12-16 waves
+    // per CU would otherwise take most issue slots.  Highest issue priority for these few waves costs the
+    // streaming kernel next to nothing and keeps the walk at the speed it has alone.
+    if (a.out_rows && a.out_rows[ch] < 0) return;      // muted row (its receiver has moved on): uniform per workgroup
+    __builtin_amdgcn_s_setprio(3);
+    const PcThread<NW, LEAN> c = pc_thread<NW, LEAN>(a, S, ch, threadIdx.x);
+    const PcChannel &C = c.C;
+    PcState st{C.sm, C.agc, C.am.z1, C.sam.z1, C.sam.y1, C.sam.phase, C.sam.freq, C.fm.phase, C.fm.freq, C.fm.err_dc, C.fm.sq_ave,
+               C.fm.squelched, C.fm.lp, 0.0, 0.0};
+    PcRegs<NW> r;
+    pc_stage_histories(c, st);
+    if (c.kPrefetch && c.total > 0) pc_fetch(c, r, 0, a.burst < PT ? a.burst : PT);
+#ifdef PC_PROFILE
+    st.tlast = __builtin_readcyclecounter();
+#endif
+#pragma unroll
+    for (int j = 0; j < c.LC; j++) r.lp_y[j] = 0.f;
+    for (int b = 0; b < a.nbursts; b++) {
+        for (int t0 = 0; t0 < a.burst; t0 += PT) {
+            const int n = (a.burst - t0) < PT ? (a.burst - t0) : PT;
+            const long gi = (long)b * a.burst + t0;
+            float2 *x = S.dl + ((c.do_agc && st.agc.on) ? c.D : 0);       // tile samples (AGC: behind the delay history)
+            pc_load_tile(c, r, x, n, gi, t0);
+            PC_TICK(0);
+            pc_smeter_stage(c, st, x, n);
+            PC_TICK(1);
+            pc_agc_stage(c, st, x, n, gi);
+            PC_TICK(6);
+            // x[0..n) now holds the AGC output (or the input)
+            if (c.mode == PC_MODE_NONE || c.mode >= PC_MODE_USB) pc_ssb_tile(c, x, n, gi);
+            else if (c.mode == PC_MODE_AM) pc_am_tile(c, st, x, n, gi);
+            else {                                                        // PLL modes: theta = arg(x) for the whole tile, in turns
+                float *th = S.w1 + (c.nt - 1);
+                for (int i = c.t; i < n; i += c.NT) th[i] = pll_theta_of(x[i].x, x[i].y);
+                c.g.sync();
+                PC_TICK(7);
+                if (c.mode == PC_MODE_FM) pc_fm_tile(c, st, r, x, n, gi);
+                else pc_sam_tile(c, st, x, n, gi);
+            }
+        }
+        pc_fm_burst_end(c, st, r, b);
+    }
+    PC_TICK(12);
+#ifdef PC_PROFILE
+    if (blockIdx.x == 0 && c.t == 0)
+        printf("pcprof mode %d: load %llu smeter %llu agcmag %llu slmax %llu histmove %llu aver %llu gain %llu atan %llu pll %llu dc %llu sqfir %llu slide %llu burstend %llu\n",
+               c.mode, st.tk[0], st.tk[1], st.tk[2], st.tk[3], st.tk[4], st.tk[5], st.tk[6], st.tk[7], st.tk[8], st.tk[9], st.tk[10], st.tk[11], st.tk[12]);
+#endif
+    pc_store_state(c, st, ch);
 }
 
 // =====================================================================================================
@@ -1482,9 +1337,8 @@ void agc_peaks_kernel(PcArgs a)
     constexpr int NT = G::NT;
     extern __shared__ __attribute__((aligned(16))) unsigned char pc_smem[];
     PreLds &S = *reinterpret_cast<PreLds *>(pc_smem);
-    const int ngrp = (a.nbursts + a.pre_bpw - 1) / a.pre_bpw;
-    const int t = threadIdx.x, ch = blockIdx.x / ngrp, b0 = (blockIdx.x % ngrp) * a.pre_bpw;
-    const int b1 = b0 + a.pre_bpw < a.nbursts ? b0 + a.pre_bpw : a.nbursts;
+    const PcBurstGroup bg = pc_burst_group(a.nbursts, a.pre_bpw);
+    const int t = threadIdx.x, ch = bg.ch, b0 = bg.b0, b1 = bg.b1;
     if (a.out_rows && a.out_rows[ch] < 0) return;
     const PcChannel &C = a.chan[ch];
     if (!C.agc.on) return;                               // uniform per workgroup
@@ -1513,15 +1367,8 @@ void agc_peaks_kernel(PcArgs a)
         g.sync();
         sliding_max(g, S, W1, n);
         for (int i = t; i < n; i += NT) pkrow[pos + i] = S.pk[i];
-        {   // the last W1 magnitudes are the next tile's window: read all, one barrier, write all
-            float keepm[PH / NT];
-#pragma unroll
-            for (int j = 0; j < PH / NT; j++) { const int i = t + NT * j; if (i < W1) keepm[j] = S.mg[n + i]; }
-            g.sync();
-#pragma unroll
-            for (int j = 0; j < PH / NT; j++) { const int i = t + NT * j; if (i < W1) S.mg[i] = keepm[j]; }
-            g.sync();
-        }
+        keep_tail(g, S.mg, W1, n);                       // the last W1 magnitudes are the next tile's window
+        g.sync();
         pos += n;
     }
     if (p1 == total) {                                   // the window the next call starts with
@@ -1534,16 +1381,9 @@ hipError_t agc_peaks_launch(const PcArgs &a, hipStream_t stream)
 {
     static_assert(sizeof(PreLds) <= 40 * 1024, "four peaks workgroups per CU");
     PcArgs b = a;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const long slots = 4L * (cus > 0 ? cus : 256);
-    b.pre_bpw = (int)(((long)a.channels * a.nbursts + slots - 1) / slots);
-    if (b.pre_bpw < 1) b.pre_bpw = 1;
-    const int ngrp = (a.nbursts + b.pre_bpw - 1) / b.pre_bpw;
-#ifdef CSDR_WG_TRACE
-    b.trace = wgtrace_next();
-#endif
-    hipLaunchKernelGGL(agc_peaks_kernel, dim3(a.channels * ngrp), dim3(256), sizeof(PreLds), stream, b);
+    b.pre_bpw = pc_bursts_per_wg(a);
+    const int ngrp = pc_burst_groups(a.nbursts, b.pre_bpw);
+    hipLaunchKernelGGL(agc_peaks_kernel, dim3(a.channels * ngrp), dim3(256), sizeof(PreLds), stream, pc_traced(b));
     return hipGetLastError();
 }
 
@@ -1592,29 +1432,21 @@ void smeter_call_kernel(PcArgs a)
         const float *run = S.db + base + t;              // = index(base + j) for j < 32
         double p = 0.0, pk = -1.0e300;
         for (int j = 0; j < cnt; j++) { const double x = (double)run[j]; p = ia * p + aa * x; pk = fmax(pk, x); }
-        double A = S.pw[cnt], B = p, At, Bt;
-        g.scan1_max(A, B, At, Bt, pk);
-        double att = A * sm.att_ave + B;                 // attack average entering this thread's run
-        const double att_end = At * sm.att_ave + Bt;
-        double MA = 1.0, MB = 0.0, MC = -1.0e300, TA, TB, TC;
+        double att_end;
+        double att = smeter_att_scan(g, sm, {S.pw[cnt], p}, pk, att_end);    // attack average entering this thread's run
+        AffMax dec = AffMax::identity();
         for (int j = 0; j < cnt; j++) {
             const double x = (double)run[j];
             att = ia * att + aa * x;
-            MA = id * MA; MB = id * MB + da * x; MC = fmax(id * MC + da * x, att);
+            dec = AffMax{id, da * x, att}.after(dec);
         }
-        g.scan_max(MA, MB, MC, TA, TB, TC);
-        const double dec_end = fmax(TA * sm.dec_ave + TB, TC);
-        sm.att_ave = att_end; sm.dec_ave = dec_end; sm.ave_mag = dec_end; sm.peak_mag = fmax(sm.peak_mag, pk);
+        smeter_finish(g, sm, dec, att_end, pk);
     }
     if (t == 0) C.sm = sm;
 }
 hipError_t smeter_call_launch(const PcArgs &a, hipStream_t stream)
 {
-    PcArgs b = a;
-#ifdef CSDR_WG_TRACE
-    b.trace = wgtrace_next();
-#endif
-    hipLaunchKernelGGL(smeter_call_kernel, dim3(a.channels), dim3(256), 0, stream, b);
+    hipLaunchKernelGGL(smeter_call_kernel, dim3(a.channels), dim3(256), 0, stream, pc_traced(a));
     return hipGetLastError();
 }
 
@@ -1630,28 +1462,24 @@ hipError_t smeter_call_launch(const PcArgs &a, hipStream_t stream)
 //      steps), the decision of every burst, the filter state each open burst starts from; the channel's state;
 //   3. fm_squelch_apply_kernel, one workgroup per (channel, burst): zeros, or the low-pass from that start state.
 // =====================================================================================================
+// a tile's two maps (p: the squelch average, q: the low-pass state), as sq_and_lowpass builds them
 template <int NW>
-__device__ __forceinline__ void sq_lp_maps(const Wg<NW> &g, const float *sq, const float *x, int n, double a, double gn,
-                                           const double *apw, const PcIir &f, const double *tab,
-                                           double &At, double &Bt, double (&mt)[4], double (&vt)[2])
+__device__ __forceinline__ Both<Aff1, Aff2> sq_lp_maps(const Wg<NW> &g, const float *sq, const float *x, int n, double a, double gn,
+                                                       const double *apw, const PcIir &f, const double *tab)
 {
     constexpr int LC = Wg<NW>::LC;
-    const int base = LC * g.t;
-    int cnt = n - base; cnt = cnt < 0 ? 0 : (cnt > LC ? LC : cnt);
+    const int base = g.base(), cnt = g.count(n);
     double p = 0.0, w1 = 0.0, w2 = 0.0;
 #pragma unroll
     for (int j = 0; j < LC; j++) {
         const float sv = j < cnt ? sq[base + j] : 0.f;
         p = j < cnt ? a * p + gn * (double)sv : p;
-        const double xv = j < cnt ? (double)x[base + j] : 0.0;
-        const double w0 = xv - f.a1 * w1 - f.a2 * w2;
-        if (j < cnt) { w2 = w1; w1 = w0; }
+        (void)biquad_chunk_step(f, j < cnt ? (double)x[base + j] : 0.0, j < cnt, w1, w2);
     }
-    double A = apw[cnt], B = p;
-    double m[4] = {tab[4 * cnt], tab[4 * cnt + 1], tab[4 * cnt + 2], tab[4 * cnt + 3]}, v[2] = {w1, w2};
-    g.scan1_2(A, B, At, Bt, m, v, mt, vt);
+    Both<Aff1, Aff2> m{{apw[cnt], p}, chunk_map2(tab, cnt, w1, w2)}, tot;
+    g.scan(m, tot);
+    return tot;
 }
-
 
 __global__ __launch_bounds__(256)
 void fm_squelch_maps_kernel(PcArgs a)
@@ -1661,24 +1489,16 @@ void fm_squelch_maps_kernel(PcArgs a)
     constexpr int NT = G::NT, LC = G::LC;
     extern __shared__ __attribute__((aligned(16))) unsigned char pc_smem[];
     SqLds &S = *reinterpret_cast<SqLds *>(pc_smem);
-    const int ngrp = (a.nbursts + a.sq_bpw - 1) / a.sq_bpw;
-    const int t = threadIdx.x, ch = blockIdx.x / ngrp, b0 = (blockIdx.x % ngrp) * a.sq_bpw;
-    const int b1 = b0 + a.sq_bpw < a.nbursts ? b0 + a.sq_bpw : a.nbursts;
+    const PcBurstGroup bg = pc_burst_group(a.nbursts, a.sq_bpw);
+    const int t = threadIdx.x, ch = bg.ch, b0 = bg.b0, b1 = bg.b1;
     if (a.out_rows && a.out_rows[ch] < 0) return;
     const PcChannel &C = a.chan[ch];
     if (C.mode != PC_MODE_FM) return;                    // uniform per workgroup
     const G g{t, t & 63, t >> 6, &S.sy};
-    const bool stereo = a.flags & PC_STEREO;
-    const long orow = (long)(a.out_rows ? a.out_rows[ch] : ch) * a.out_stride;
-    const float *outm = a.out + orow;
-    const float2 *outs = reinterpret_cast<const float2 *>(a.out) + orow;
-    auto raw = [&](long i) -> float { return stereo ? outs[i].x : outm[i]; };
+    const PcRow row = PcRow::of(a, ch);
     const PcFir &fir = C.fm.hp;
     const int nt = fir.ntaps;
-    for (int i = t; i < PC_FIR_MAX + 17; i += NT) {
-        const int k = nt - 1 - (i - 4);                  // reversed, four zeros in front, zeros behind (as in the walk)
-        S.h0[i] = (k >= 0 && k < nt) ? fir.coef[k] : 0.f;
-    }
+    stage_taps<NT>(S.h0, fir.coef, nt, t);
     for (int i = t; i < PT + PC_FIR_MAX + 17; i += NT) S.w0[i] = 0.f;
     pow_table(S.pw_sq, 1.0 - C.fm.sq_alpha, t);
     PcIir lp = C.fm.lp;
@@ -1690,7 +1510,7 @@ void fm_squelch_maps_kernel(PcArgs a)
         const long g0 = (long)b0 * a.burst;
         for (int i = t; i < nt - 1; i += NT) {
             const long k = g0 - (nt - 1) + i;
-            S.w0[i] = k >= 0 ? raw(k) : fir.zreal[i];    // (k < 0 only for burst 0: burst >= PC_FIR_MAX > ntaps - 1)
+            S.w0[i] = k >= 0 ? row.raw(k) : fir.zreal[i];   // (k < 0 only for burst 0: burst >= PC_FIR_MAX > ntaps - 1)
         }
     }
     float *au = S.w0 + (nt - 1);
@@ -1699,12 +1519,12 @@ void fm_squelch_maps_kernel(PcArgs a)
     const long first = (long)b0 * a.burst, end = (long)b1 * a.burst;
     auto fetch = [&](long p) {
 #pragma unroll
-        for (int j = 0; j < LC; j++) { const long i = p + t + NT * j; nx[j] = i < end ? raw(i) : 0.f; }
+        for (int j = 0; j < LC; j++) { const long i = p + t + NT * j; nx[j] = i < end ? row.raw(i) : 0.f; }
     };
     fetch(first);
     for (int b = b0; b < b1; b++) {
         const long g0 = (long)b * a.burst;
-        double A_tot = 1.0, B_tot = 0.0, M_tot[4] = {1.0, 0.0, 0.0, 1.0}, v_tot[2] = {0.0, 0.0};
+        Both<Aff1, Aff2> burst = Both<Aff1, Aff2>::identity();
         for (int t0 = 0; t0 < a.burst; t0 += PT) {
             const int n = (a.burst - t0) < PT ? (a.burst - t0) : PT;
 #pragma unroll
@@ -1716,22 +1536,13 @@ void fm_squelch_maps_kernel(PcArgs a)
 #pragma unroll
             for (int j = 0; j < LC; j++) S.w2[pc_out_index<4>(t, j) & (PT - 1)] = fabsf(acc[j]);
             g.sync();
-            double At, Bt, mt[4], vt[2];
-            sq_lp_maps(g, S.w2, au, n, 1.0 - C.fm.sq_alpha, C.fm.sq_alpha, S.pw_sq, lp, S.bq, At, Bt, mt, vt);
             // this tile's maps behind what the burst has so far
-            B_tot = At * B_tot + Bt; A_tot = At * A_tot;
-            const double n0 = mt[0] * M_tot[0] + mt[1] * M_tot[2], n1 = mt[0] * M_tot[1] + mt[1] * M_tot[3];
-            const double n2 = mt[2] * M_tot[0] + mt[3] * M_tot[2], n3 = mt[2] * M_tot[1] + mt[3] * M_tot[3];
-            const double u0 = mt[0] * v_tot[0] + mt[1] * v_tot[1] + vt[0], u1 = mt[2] * v_tot[0] + mt[3] * v_tot[1] + vt[1];
-            M_tot[0] = n0; M_tot[1] = n1; M_tot[2] = n2; M_tot[3] = n3; v_tot[0] = u0; v_tot[1] = u1;
+            burst = sq_lp_maps(g, S.w2, au, n, 1.0 - C.fm.sq_alpha, C.fm.sq_alpha, S.pw_sq, lp, S.bq).after(burst);
             g.sync();
             slide(g, S.w0, nt - 1, n);                   // the next tile's / burst's delay line
             g.sync();
         }
-        if (t == 0) {
-            double *r = a.sqbuf + ((long)ch * a.nbursts + b) * PC_SQ_REC;
-            r[0] = A_tot; r[1] = B_tot; r[2] = M_tot[0]; r[3] = M_tot[1]; r[4] = M_tot[2]; r[5] = M_tot[3]; r[6] = v_tot[0]; r[7] = v_tot[1];
-        }
+        if (t == 0) burst.put(a.sqbuf + ((long)ch * a.nbursts + b) * PC_SQ_REC);
     }
 }
 
@@ -1743,10 +1554,7 @@ void fm_squelch_decide_kernel(PcArgs a)
     if (a.out_rows && a.out_rows[ch] < 0) return;
     PcChannel &C = a.chan[ch];
     if (C.mode != PC_MODE_FM) return;
-    const bool stereo = a.flags & PC_STEREO;
-    const long orow = (long)(a.out_rows ? a.out_rows[ch] : ch) * a.out_stride;
-    const float *outm = a.out + orow;
-    const float2 *outs = reinterpret_cast<const float2 *>(a.out) + orow;
+    const PcRow row = PcRow::of(a, ch);
     PcFm &F = C.fm;
     // the high-pass delay line after the call: the last ntaps-1 raw audio samples (the apply kernel has not run yet)
     const int nt = F.hp.ntaps;
@@ -1754,7 +1562,7 @@ void fm_squelch_decide_kernel(PcArgs a)
     float keep = 0.f;
     if (t < nt - 1) {
         const long k = total - (nt - 1) + t;
-        keep = k >= 0 ? (stereo ? outs[k].x : outm[k]) : F.hp.zreal[t + (int)total];
+        keep = k >= 0 ? row.raw(k) : F.hp.zreal[t + (int)total];
     }
     __syncthreads();
     if (t < nt - 1) F.hp.zreal[t] = keep;
@@ -1777,9 +1585,7 @@ void fm_squelch_decide_kernel(PcArgs a)
             for (int b = 0; b < cn; b++) {
                 const double *r = rec[b];
                 sq = r[0] * sq + r[1];
-                if (0 == F.sq_thresh) sqd = 1;                                  // fmdemod.cpp:128-151
-                else if (sqd) { if (sq < (F.sq_thresh - refc::FM_SQUELCH_HYSTERESIS)) sqd = 0; }
-                else { if (sq >= (F.sq_thresh + refc::FM_SQUELCH_HYSTERESIS)) sqd = 1; }
+                sqd = squelch_decide(sq, F.sq_thresh, sqd);
                 res[b][0] = (double)sqd; res[b][1] = w1; res[b][2] = w2;
                 if (!sqd) {                                                     // the low-pass runs on open bursts only
                     const double nw1 = r[2] * w1 + r[3] * w2 + r[6], nw2 = r[4] * w1 + r[5] * w2 + r[7];
@@ -1804,17 +1610,13 @@ void fm_squelch_apply_kernel(PcArgs a)
     constexpr int NT = G::NT;
     extern __shared__ __attribute__((aligned(16))) unsigned char pc_smem[];
     SqLds &S = *reinterpret_cast<SqLds *>(pc_smem);
-    const int ngrp = (a.nbursts + a.sq_bpw - 1) / a.sq_bpw;
-    const int t = threadIdx.x, ch = blockIdx.x / ngrp, b0 = (blockIdx.x % ngrp) * a.sq_bpw;
-    const int b1 = b0 + a.sq_bpw < a.nbursts ? b0 + a.sq_bpw : a.nbursts;
+    const PcBurstGroup bg = pc_burst_group(a.nbursts, a.sq_bpw);
+    const int t = threadIdx.x, ch = bg.ch, b0 = bg.b0, b1 = bg.b1;
     if (a.out_rows && a.out_rows[ch] < 0) return;
     const PcChannel &C = a.chan[ch];
     if (C.mode != PC_MODE_FM) return;
     const G g{t, t & 63, t >> 6, &S.sy};
-    const bool stereo = a.flags & PC_STEREO;
-    const long orow = (long)(a.out_rows ? a.out_rows[ch] : ch) * a.out_stride;
-    float *outm = a.out + orow;
-    float2 *outs = reinterpret_cast<float2 *>(a.out) + orow;
+    const PcRow row = PcRow::of(a, ch);
     PcIir lp = C.fm.lp;
     biquad_table(S.bq, lp, t);
     g.sync();
@@ -1822,17 +1624,17 @@ void fm_squelch_apply_kernel(PcArgs a)
         const double *r = a.sqbuf + ((long)ch * a.nbursts + b) * PC_SQ_REC;
         const long g0 = (long)b * a.burst;
         if (r[8] != 0.0) {                               // squelched: zeros (fmdemod.cpp:139-143); uniform per workgroup
-            for (int i = t; i < a.burst; i += NT) { if (stereo) outs[g0 + i] = make_float2(0.f, 0.f); else outm[g0 + i] = 0.f; }
+            for (int i = t; i < a.burst; i += NT) row.put(g0 + i, 0.f);
             continue;
         }
         lp.w1a = r[9]; lp.w2a = r[10];
         for (int t0 = 0; t0 < a.burst; t0 += PT) {
             const int n = (a.burst - t0) < PT ? (a.burst - t0) : PT;
-            for (int i = t; i < n; i += NT) S.w2[i] = stereo ? outs[g0 + t0 + i].x : outm[g0 + t0 + i];
+            for (int i = t; i < n; i += NT) S.w2[i] = row.raw(g0 + t0 + i);
             g.sync();
             biquad_scan(g, S.w2, n, lp, S.bq);
             g.sync();
-            for (int i = t; i < n; i += NT) { const float y = S.w2[i]; if (stereo) outs[g0 + t0 + i] = make_float2(y, y); else outm[g0 + t0 + i] = y; }
+            for (int i = t; i < n; i += NT) row.put(g0 + t0 + i, S.w2[i]);
             g.sync();
         }
     }
@@ -1841,27 +1643,12 @@ void fm_squelch_apply_kernel(PcArgs a)
 hipError_t fm_squelch_launch(const PcArgs &a, hipStream_t stream)
 {
     static_assert(sizeof(SqLds) <= 20 * 1024, "eight squelch workgroups per CU");
-    // bursts per workgroup: as few as still give every workgroup a slot in ONE round (four 256-thread workgroups per
-    // CU at these kernels' 105-122 registers), so that taps, tables and zeroing are paid once per slot
     PcArgs b = a;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const long slots = 4L * (cus > 0 ? cus : 256);
-    b.sq_bpw = (int)(((long)a.channels * a.nbursts + slots - 1) / slots);
-    if (b.sq_bpw < 1) b.sq_bpw = 1;
-    const int ngrp = (a.nbursts + b.sq_bpw - 1) / b.sq_bpw;
-#ifdef CSDR_WG_TRACE
-    b.trace = wgtrace_next();
-#endif
-    hipLaunchKernelGGL(fm_squelch_maps_kernel, dim3(a.channels * ngrp), dim3(256), sizeof(SqLds), stream, b);
-#ifdef CSDR_WG_TRACE
-    b.trace = wgtrace_next();
-#endif
-    hipLaunchKernelGGL(fm_squelch_decide_kernel, dim3(a.channels), dim3(64), 0, stream, b);
-#ifdef CSDR_WG_TRACE
-    b.trace = wgtrace_next();
-#endif
-    hipLaunchKernelGGL(fm_squelch_apply_kernel, dim3(a.channels * ngrp), dim3(256), sizeof(SqLds), stream, b);
+    b.sq_bpw = pc_bursts_per_wg(a);
+    const int ngrp = pc_burst_groups(a.nbursts, b.sq_bpw);
+    hipLaunchKernelGGL(fm_squelch_maps_kernel, dim3(a.channels * ngrp), dim3(256), sizeof(SqLds), stream, pc_traced(b));
+    hipLaunchKernelGGL(fm_squelch_decide_kernel, dim3(a.channels), dim3(64), 0, stream, pc_traced(b));
+    hipLaunchKernelGGL(fm_squelch_apply_kernel, dim3(a.channels * ngrp), dim3(256), sizeof(SqLds), stream, pc_traced(b));
     return hipGetLastError();
 }
 
@@ -1890,8 +1677,6 @@ hipError_t filter_leaf_launch(PcFir *fir, PcIir *iir, const float *in, float *ou
     return hipGetLastError();
 }
 
-// waves per channel: four when the channels alone cannot fill the chip, else one.
-// CSDR_POSTCHAIN_WAVES=1|4|8 overrides (measurements: 4 beats 8 on 256 channels, 3.8 vs 4.1 ms).
 // CSMeter::GetAve / GetPeak (dsp/smeter.cpp:98-112) of every channel of a unit at once, without moving the
 // channel state: ave[row] = average + 5 dB, peak[row] = peak + 5 dB and the peak is reset to 0 as GetPeak
 // does.  rows: optional output index of each channel.
@@ -1927,28 +1712,21 @@ static hipError_t pc_launch_nw(const PcArgs &a, hipStream_t stream)
         hipError_t e = CSDR_MAX_LDS_ONCE((&postchain_kernel<NW, LEAN>), sizeof(PcLds));
         if (e != hipSuccess) return e;
     }
-    PcArgs b = a;
-#ifdef CSDR_WG_TRACE
-    b.trace = wgtrace_next();
-#endif
-    hipLaunchKernelGGL((postchain_kernel<NW, LEAN>), dim3(a.channels), dim3(64 * NW), sizeof(PcLds), stream, b);
+    hipLaunchKernelGGL((postchain_kernel<NW, LEAN>), dim3(a.channels), dim3(64 * NW), sizeof(PcLds), stream, pc_traced(a));
     return hipGetLastError();
 }
 hipError_t postchain_launch(const PcArgs &a, hipStream_t stream)
 {
+    // waves per channel: four when the channels alone cannot fill the chip, else one; CSDR_POSTCHAIN_WAVES=1|4 overrides
     static int forced = -1;
     if (forced < 0) { const char *env = getenv("CSDR_POSTCHAIN_WAVES"); forced = env ? atoi(env) : 0; }
     int nw = a.channels <= 1024 ? 4 : 1;
-    if (forced == 1 || forced == 4 || forced == 8) nw = forced;
+    if (forced == 1 || forced == 4) nw = forced;
     // the lean walk (four waves): no S-meter in the launch, AGC peaks precomputed for every receiver that has the AGC
     // on, the squelch of every FM receiver deferred -- the caller (PcUnit::run) says so with PC_LEAN
     static const bool lean_ok = !(getenv("CSDR_PC_LEAN") && atoi(getenv("CSDR_PC_LEAN")) == 0);
     if (nw == 4 && (a.flags & PC_LEAN) && lean_ok) return pc_launch_nw<4, true>(a, stream);
-    switch (nw) {
-    case 8:  return pc_launch_nw<8, false>(a, stream);
-    case 4:  return pc_launch_nw<4, false>(a, stream);
-    default: return pc_launch_nw<1, false>(a, stream);
-    }
+    return nw == 4 ? pc_launch_nw<4, false>(a, stream) : pc_launch_nw<1, false>(a, stream);
 }
 
 }  // namespace csdr
