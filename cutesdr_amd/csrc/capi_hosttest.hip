@@ -254,7 +254,8 @@ void *csdr__host_scope_create(void)
     return s;
 }
 void csdr__host_scope_destroy(void *h) { delete (HostScope *)h; }
-// what: 0 screen (v = w, v2 = h), 1 span, 2 display rate, 3 trigger mode, 4 level, 5 vertical range, 6 reset, 7 time_plot_done
+// what: 0 screen (v = w, v2 = h), 1 span, 2 display rate, 3 trigger mode, 4 level, 5 vertical range, 6 reset, 7 time_plot_done,
+// 8 OnTimeDisplay(v), 9 OnEnablePeak(v)
 void csdr__host_scope_slot(void *h, int what, int v, int v2)
 {
     HostScope &s = *(HostScope *)h;
@@ -266,6 +267,8 @@ void csdr__host_scope_slot(void *h, int what, int v, int v2)
     case 4: s.ch.level = v; break;
     case 5: s.ch.vert = v; break;
     case 6: s.ch.reset(s.w); break;
+    case 8: s.ch.on_time_display(v, s.w); break;        // OnTimeDisplay(v != 0)
+    case 9: s.ch.on_enable_peak(v); break;
     default: s.ch.time_plot_done(); break;
     }
 }
@@ -274,12 +277,16 @@ long long csdr__host_scope_put(void *h, const float *re, const float *im, int n,
 {
     HostScope &s = *(HostScope *)h;
     sc::ChanParam par;
-    s.ch.prepare(n, fs, s.w, par);
+    s.ch.prepare(n, fs, s.w, par, s.h, im != nullptr);
     sc::ChanState &st = s.st;
     int *ring = s.ring, *screen = s.screen;
     const int w = s.w;
-    if (par.flags & sc::F_RESET) memset(ring, 0, sizeof(s.ring));
+    if (par.flags & (sc::F_RESET | sc::F_PEAK)) memset(ring, 0, sizeof(s.ring));     // Reset :555-560, OnEnablePeak :336-341
     sc::apply_flags(st, par.flags);
+    if (par.view == sc::VIEW_FFT) {                      // the frames are the device's; the counters as the kernel sets them
+        if (par.n > 0) { st.skipcounter = par.cnt_end; st.emits += (unsigned)par.count; }
+        return st.emits;
+    }
     if (par.n > 0) {
         const sc::Plan pl = sc::make_plan(st.inpos, st.pos, par.pix, par.sr, w, par.n);
         const long long E = pl.emits;
@@ -323,5 +330,46 @@ void csdr__host_scope_get(void *h, long long *state7, int *screen_re, int *scree
     memcpy(screen_re, s.screen, sizeof(int) * s.w); memcpy(screen_im, s.screen + sc::kMaxW, sizeof(int) * s.w);
 }
 int csdr__host_scope_sat_int(double x) { return sc::sat_int(x); }
+
+// ---- the FFT view's host-side pieces (scope_host.hpp)
+// the used frames of n samples entered at m_FftBufPos = pos with the skip counter at cnt: out6 = {frames that complete,
+// first used one, step, count, m_FftBufPos afterwards, skip counter afterwards}
+void csdr__host_scope_fft_plan(int pos, long long cnt, int skip, long long n, long long *out6)
+{
+    const sc::FftPlan p = sc::fft_plan(pos, cnt, skip, n);
+    out6[0] = p.frames; out6[1] = p.first; out6[2] = p.step; out6[3] = p.count; out6[4] = p.pos_end; out6[5] = p.cnt_end;
+}
+// m_DisplaySkipValue and m_Span of the FFT view at a display rate and sample rate
+void csdr__host_scope_fft_settings(int display_rate, double sr, int *skip, int *span)
+{
+    *skip = sc::fft_skip_value(display_rate, sr); *span = sc::fft_span(sr);
+}
+// what one receiver's settings hold: out8 = {view, skip value, m_Span, m_FftBufPos, skip counter, carry buffer, pending
+// flags, m_PeakOn}
+void csdr__host_scope_fft_chan(void *h, long long *out8)
+{
+    const sc::Chan &k = ((HostScope *)h)->ch;
+    out8[0] = k.view; out8[1] = k.skip; out8[2] = k.fspan; out8[3] = k.fpos; out8[4] = k.fcnt; out8[5] = k.fcur;
+    out8[6] = k.flags; out8[7] = k.peak_on;
+}
+// completing frame j of a call entered with `fill` carried samples, as scope_fft_kernel loads it: carry [fill] and row
+// [n] complex fp32 (interleaved; cpx == 0: row is real fp32 and goes in as (x, 0)) -> out [2048] complex fp32
+void csdr__host_scope_fft_frame(const float *carry, int fill, const float *row, int cpx, long long j, float *out)
+{
+    for (int i = 0; i < sc::kFftN; i++) {
+        const long long s = sc::fft_source(j, i, fill);
+        if (s < 0) { out[2 * i] = carry[2 * (s + fill)]; out[2 * i + 1] = carry[2 * (s + fill) + 1]; }
+        else if (cpx) { out[2 * i] = row[2 * s]; out[2 * i + 1] = row[2 * s + 1]; }
+        else { out[2 * i] = row[s]; out[2 * i + 1] = 0.f; }
+    }
+}
+// DrawFftPlot's GetScreenIntegerFFTData of bels[2048] (display order) for a receiver whose last Reset saw the rate fs
+// and left m_Span = span: out [w] pixels, map4 = {m_BinMin, m_BinMax, the "more bins than pixels" branch, h}
+void csdr__host_scope_fft_map(int span, int cpx, double fs, int w, int h, const double *bels, int *out, int *map4)
+{
+    const sc::FftMap m = sc::make_fft_map(span, cpx, fs, w, h);
+    for (int x = 0; x < w; x++) out[x] = sc::fft_pixel(m, w, x, [&](int i) { return bels[i]; });
+    map4[0] = m.bin_min; map4[1] = m.bin_max; map4[2] = m.bins; map4[3] = m.h;
+}
 
 }  // extern "C"

@@ -8,6 +8,13 @@
 // modulo w.  A sweep that is entered in the middle (state inpos, pos; possibly with a pixel time changed since by
 // OnHorzSpan) emits pixel p at input position max(k(p), inpos).  k(p) is taken from ceil(p * pix * sr) and corrected
 // with the reference's own fp64 comparison, so it is the reference's index whatever that product rounds to.
+//
+// The FFT view (DisplayData's frequency branch :594-611 / :654-672, DrawFftPlot :1005-1068) has no data-dependent frame
+// logic at all: given m_FftBufPos, the skip counter, the skip value and n, the frames of a call that reach
+// PutInDisplayFFT are an arithmetic progression (fft_plan), sample i of such a frame lies in the carried partial
+// frame or in the call's row (fft_source), and the bels -> pixel mapping of GetScreenIntegerFFTData (dsp/fft.cpp:
+// 308-410) is a pure function of a few integers (make_fft_map, fft_pixel).  The host keeps position and counter of an
+// FFT-view receiver itself (sc::Chan) and hands the kernel the progression.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <climits>
@@ -20,7 +27,11 @@ constexpr int kMaxW = 2048;                              // TB_MAX_SCREENSIZE (g
 constexpr double kMaxSweep = 1073741824.0;               // samples of one sweep: m_TimeInPos is an int
 enum { TRIG_OFF = 0, TRIG_PNORM = 1, TRIG_PSINGLE = 2, TRIG_NNORM = 3, TRIG_NSINGLE = 4 };
 enum { ST_WAIT = 0, ST_CAPTURE = 1, ST_DISPLAY = 2, ST_WAITDISPLAY = 3 };
-enum { F_RESET = 1, F_REARM = 2 };
+enum { F_RESET = 1, F_REARM = 2, F_PEAK = 4 };         // F_PEAK: OnEnablePeak's clearing (:334-343)
+enum { VIEW_TIME = 0, VIEW_FFT = 1 };
+constexpr int kFftN = 2048;                              // TEST_FFTSIZE
+constexpr double kFftMaxRate = 2147483632.0;             // an FFT-view receiver: (qint32)fs and the + 5 of :537-538 stay in an int
+constexpr double kFftMaxdB = 10.0, kFftMindB = -170.0;   // m_MaxdB (:96) and m_MaxdB - TB_VERT_DIVS (18) * m_dBStepSize (:98, :1257)
 
 // (int) of a sample (:623-625): saturating, NaN gives 0 (the reference's conversion is undefined there)
 __host__ __device__ inline int sat_int(double x)
@@ -122,10 +133,97 @@ __host__ __device__ inline FreeRun free_run(long long cnt, int skip, long long m
     return r;
 }
 
+// ---- the FFT view
+// m_DisplaySkipValue as Reset and OnDisplayRate compute it in this view (:257, :570), truncated into the qint32
+inline int fft_skip_value(int display_rate, double sr) { return sat_int(sr / (double)((long long)kFftN * display_rate)); }
+// m_Span (:537-538): (qint32)fs, then rounded to a multiple of ten with C's remainder; sr < kFftMaxRate
+inline int fft_span(double sr)
+{
+    const int s = sat_int(sr);
+    return s - (s + 5) % 10 + 5;
+}
+// The frames that complete in a call of n samples entered at m_FftBufPos = pos with the skip counter at cnt (:597-610):
+// frame j (0-based among them) is used when `++cnt >= skip` holds at its end.  The counter goes back to 0 at a used
+// frame, so the used ones are first, first + step, ... (count of them); pos_end and cnt_end are the members afterwards.
+struct FftPlan { long long frames, first, step, count, cnt_end; int pos_end; };
+__host__ __device__ inline FftPlan fft_plan(int pos, long long cnt, int skip, long long n)
+{
+    FftPlan p;
+    const long long avail = (long long)pos + n;
+    p.frames = avail / kFftN;
+    p.pos_end = (int)(avail - p.frames * kFftN);
+    p.step = skip > 1 ? skip : 1;
+    const long long m = (long long)skip - cnt > 1 ? (long long)skip - cnt : 1;   // the first increment that reaches skip
+    p.first = m - 1;
+    if (p.frames > p.first) {
+        p.count = (p.frames - 1 - p.first) / p.step + 1;
+        p.cnt_end = p.frames - 1 - (p.first + (p.count - 1) * p.step);
+    } else {
+        p.count = 0;
+        p.cnt_end = cnt + p.frames;
+    }
+    return p;
+}
+// sample i of completing frame j of a call entered with `fill` carried samples: its index in the carry (the return
+// value is < 0: index + fill) or in the call's row (>= 0)
+__host__ __device__ inline long long fft_source(long long j, int i, int fill) { return j * kFftN + i - fill; }
+
+// GetScreenIntegerFFTData's integers (dsp/fft.cpp:323-345) for DrawFftPlot's call (:1026-1043): start = -m_Span/2 for a
+// frame completed by a complex put, else 0, stop = m_Span/2 (C's division), fs the rate of the last Reset
+struct FftMap { int bin_min, bin_max, bins, h; double gain, off; };   // bins: the "more FFT points than plot points" branch
+__host__ __device__ inline FftMap make_fft_map(int span, int cpx, double fs, int w, int h)
+{
+    FftMap m;
+    const int start = cpx ? -span / 2 : 0, stop = span / 2, maxbin = kFftN - 1;
+    m.bin_min = sat_int((double)start * (double)kFftN / fs) + kFftN / 2;
+    m.bin_max = sat_int((double)stop * (double)kFftN / fs) + kFftN / 2;
+    if (m.bin_min < 0) m.bin_min = 0;
+    if (m.bin_min >= maxbin) m.bin_min = maxbin;
+    if (m.bin_max < 0) m.bin_max = 0;
+    if (m.bin_max >= maxbin) m.bin_max = maxbin;
+    m.bins = (m.bin_max - m.bin_min) > w;
+    m.h = h;
+    m.off = kFftMaxdB / 10.0;
+    m.gain = -10.0 / (kFftMaxdB - kFftMindB);
+    return m;
+}
+__host__ __device__ inline int fft_level(const FftMap &m, double bel)                        // fft.cpp:369-373
+{
+    const int y = sat_int((double)m.h * m.gain * (bel - m.off));
+    return y < 0 ? 0 : (y > m.h ? m.h : y);
+}
+// pixel x < w of the screen; bel(i) is m_pFFTAveBuf[i] as a double.  In the bins branch a pixel shows the smallest y of
+// the bins i with ((i - bin_min) * w) / (bin_max - bin_min) == x (:364-389: x never decreases along i, so "first bin of
+// a pixel sets it, a smaller one replaces it" is that minimum); those bins are d = i - bin_min in
+// [ceil(x r / w), ceil((x + 1) r / w) - 1], r = bin_max - bin_min > w: never empty.  Bin bin_max maps to x = w, which
+// the reference writes past the screen (OutBuf[w]); it is dropped.  Else pixel x shows bin bin_min + (x r) / w (:394-406).
+template <class B> __host__ __device__ inline int fft_pixel(const FftMap &m, int w, int x, B bel)
+{
+    const int r = m.bin_max - m.bin_min;
+    if (!m.bins) return fft_level(m, bel(m.bin_min + (x * r) / w));
+    const int lo = (x * r + w - 1) / w, hi = ((x + 1) * r + w - 1) / w - 1;
+    int y = INT_MAX;
+    for (int d = lo; d <= hi; d++) { const int v = fft_level(m, bel(m.bin_min + d)); y = v < y ? v : y; }
+    return y;
+}
+
 // what a put hands to the kernel per receiver (host, one pinned slot per launch)
 struct ChanParam {
     double pix, sr;
     int n, skip, level, mode, flags, vert;
+    // the FFT view (view == VIEW_FFT): the call's used frames first, first + step, ... (count) among the `frames` that
+    // complete, entered with `fill` samples in carry buffer `cur`; position and counter afterwards; the mapping
+    int view, h;
+    int fill, cur, frames, first, step, count, pos_end, cnt_end;
+    FftMap map;
+};
+
+// what the FFT view keeps on the device per receiver beside carries, bels, screen and peak
+struct FftState {
+    int pos;                             // m_FftBufPos
+    int total;                           // CFft::m_TotalCount since the last Reset
+    int cpx;                             // the last drawn frame was mapped as complex (m_CurrentDataIsCpx at that draw)
+    int pad;
 };
 
 // data-dependent state of one receiver, on the device
@@ -209,21 +307,49 @@ struct Chan {
     int skip = 0;
     int flags = 0;                                                              // applied by the next put, in stream order
     unsigned seen = 0;                                                          // emits already reported by get_emits
+    int view = VIEW_TIME;                // m_TimeDisplay (deviation: the constructor's default is the FFT view, :110)
+    int peak_on = 0;                     // m_PeakOn: kept and reported only
+    int fspan = 0;                       // m_Span
+    double ffs = 1.0;                    // the rate CFft::SetFFTParams got at the last Reset (:535)
+    int fpos = 0, fcur = 0;              // m_FftBufPos and the carry buffer that holds those samples
+    long long fcnt = -2;                 // m_DisplaySkipCounter while the receiver is in the FFT view
 
-    void derive(int w) { skip = skip_value(span, rate, sr); pix = pixel_time(span, w); }
-    void on_display_rate(int r) { rate = r; skip = skip_value(span, rate, sr); }                // :247-254
-    void on_horz_span(int s, int w) { span = s; skip = skip_value(span, rate, sr); pix = pixel_time(span, w); }    // :270-279
-    void reset(int w) { derive(w); flags |= F_RESET; }                                          // :541-548, :555-565, :574
+    int skip_now() const { return view == VIEW_FFT ? fft_skip_value(rate, sr) : skip_value(span, rate, sr); }
+    void derive(int w) { skip = skip_now(); pix = pixel_time(span, w); }
+    void on_display_rate(int r) { rate = r; skip = skip_now(); }                                // :247-258
+    void on_horz_span(int s, int w)                                                             // :270-279
+    {
+        span = s;
+        if (view == VIEW_TIME) { skip = skip_now(); pix = pixel_time(span, w); }
+    }
+    void reset(int w)                                                                           // :535-538, :541-548, :555-574
+    {
+        derive(w);
+        ffs = sr; fspan = sr < kFftMaxRate ? fft_span(sr) : 0; fpos = 0; fcnt = -2;
+        flags |= F_RESET;
+    }
     void on_trigger_mode(int m, int w) { mode = m; reset(w); }                                  // :288-292
+    void on_time_display(int timemode, int w) { view = timemode ? VIEW_TIME : VIEW_FFT; reset(w); }   // :282-286
+    void on_enable_peak(int on) { peak_on = on; flags |= F_PEAK; }                              // :334-343
     void time_plot_done() { if (mode != TRIG_PSINGLE && mode != TRIG_NSINGLE) flags |= F_REARM; }   // :995-999
     // the settings of one put of n samples at rate fs; takes the pending flags with it
-    void prepare(int n, double fs, int w, ChanParam &p)
+    void prepare(int n, double fs, int w, ChanParam &p, int h = 100, int cpx = 0)
     {
         p.n = n;
         if (n > 0 && sr != fs) { sr = fs; reset(w); p.n = 0; }      // :587-592: reset, and the call's samples are not used
         p.pix = pix; p.sr = sr; p.skip = skip; p.level = level; p.mode = mode; p.vert = vert;
         p.flags = flags;
         flags = 0;
+        p.view = view; p.h = h;
+        p.fill = fpos; p.cur = fcur; p.frames = p.first = p.count = 0; p.step = 1; p.pos_end = fpos; p.cnt_end = (int)fcnt;
+        p.map = make_fft_map(fspan, cpx, ffs, w, h);
+        if (view == VIEW_FFT && p.n > 0) {
+            const FftPlan f = fft_plan(fpos, fcnt, skip, p.n);
+            p.frames = (int)f.frames; p.count = (int)f.count;
+            if (f.count > 0) { p.first = (int)f.first; p.step = (int)(f.count > 1 ? f.step : 1); }
+            fpos = p.pos_end = f.pos_end; fcnt = f.cnt_end; p.cnt_end = (int)f.cnt_end;
+            if (f.frames > 0) fcur ^= 1;                 // the new partial frame goes into the other carry buffer
+        }
     }
 };
 

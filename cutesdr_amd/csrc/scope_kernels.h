@@ -12,8 +12,25 @@ struct ScopeArgs {
     int *ring;                               // [channels][2][kMaxW]: m_TimeBuf1/2
     int *screen;                             // [channels][2][kMaxW]: m_TimeScrnBuf1/2
     int w, channels;
+    // the FFT view
+    sc::FftState *fst;                       // [channels]
+    float *carry;                            // [channels][2][kFftN] complex fp32: m_FftInBuf, two buffers switched per put
+    float *bels;                             // [channels][kFftN]: m_pFFTAveBuf of the last used frame
+    int *fscreen, *peak;                     // [channels][kMaxW] each: the last drawn y, m_FftPkBuf
+    const float *win, *tw1, *tw2;            // the 2048-point tables of spectrum_passes.hpp: window, W_2048^i, W_1024^(i k)
+    float kc; double kb;                     // CFft's K_C and K_B / 10 at 2048 points, dB compensation 0
+    int max_count;                           // the largest number of used frames of a receiver in this call
 };
+// the put of every receiver: one launch, and one more for the used frames of the FFT-view receivers when there are any
 hipError_t scope_put_launch(const ScopeArgs &a, int cpx, hipStream_t s);
+
+struct ScopeFftScreenArgs {
+    const int *fscreen, *peak;               // [channels][kMaxW]
+    const sc::ChanParam *par;                // [channels]: view
+    int *out; long long out_stride;          // [channels][2][out_stride]: screen, peak
+    int w, channels;
+};
+hipError_t scope_fft_screens_launch(const ScopeFftScreenArgs &a, hipStream_t s);
 
 struct ScopeScreenArgs {
     const int *screen;                       // [channels][2][kMaxW]

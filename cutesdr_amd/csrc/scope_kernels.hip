@@ -11,6 +11,18 @@
 //     TRIG_OFF:         the same w emissions rotated by Post (m_TrigBufPos = 0, d at screen position 0)
 // with zeros for emissions before the reset (Reset clears the ring).  Emissions before this call come from the
 // carried ring; their slots are overwritten only by emissions >= d.
+//
+// The FFT view (DisplayData's frequency branch :594-611 / :654-672, DrawFftPlot :1005-1068).  CTestBench runs its CFft
+// with an average of 1 (SetFFTAve(0), :132; dsp/fft.cpp:103-113), so the bels after a used frame depend on that frame
+// alone, and the peak hold is a per-pixel minimum, which commutes: the work item is one (receiver, used frame), a
+// workgroup of ONE wave that holds the 2048-point frame as 64 lanes x 32 points (spectrum_passes.hpp, K3's transform).
+// scope_put_kernel stays the launch in front: for an FFT-view receiver it applies the flags (peak back to h, ring
+// zeroed), appends the call's tail to the carried partial frame and brings the counters up to date, all from the
+// host's plan (sc::ChanParam) -- so a peak reset lands before this put's minima.  The new partial frame goes into the
+// OTHER of two carry buffers, so the frame that begins in the old one can be read by scope_fft_kernel afterwards.
+#define CSDR_FMA_BFLY 1
+#define CSDR_PLAIN_CONST_FMA 1
+#include "spectrum_passes.hpp"
 #include "scope_kernels.h"
 
 namespace csdr {
@@ -36,11 +48,39 @@ template <int CPX> __global__ __launch_bounds__(kThreads) void scope_put_kernel(
     int *ring = a.ring + (size_t)c * 2 * sc::kMaxW, *screen = a.screen + (size_t)c * 2 * sc::kMaxW;
     __shared__ unsigned long long s_first;
 
-    if (par.flags & sc::F_RESET) {                       // Reset(), :555-560
+    if (par.flags & (sc::F_RESET | sc::F_PEAK)) {        // Reset() :555-560, OnEnablePeak :336-341: in either view
+        int *peak = a.peak + (size_t)c * sc::kMaxW;
         for (int i = tid; i < 2 * sc::kMaxW; i += kThreads) ring[i] = 0;
+        for (int i = tid; i < sc::kMaxW; i += kThreads) peak[i] = par.h;
+        if (par.flags & sc::F_RESET) {                   // ResetFFT (:573; dsp/fft.cpp:248-259), m_FftBufPos = 0 (:536)
+            float *bels = a.bels + (size_t)c * sc::kFftN;
+            for (int i = tid; i < sc::kFftN; i += kThreads) bels[i] = 0.f;
+            if (tid == 0) { a.fst[c].pos = 0; a.fst[c].total = 0; }
+        }
         __syncthreads();
     }
     sc::apply_flags(st, par.flags);
+    if (par.view == sc::VIEW_FFT) {                      // :594-611 / :654-672 without the frames: scope_fft_kernel's
+        if (par.n > 0) {
+            const float *row = a.rows + (size_t)c * (size_t)a.stride * (CPX ? 2 : 1);
+            float2 *carry = (float2 *)a.carry + (size_t)c * 2 * sc::kFftN;
+            // no frame completes: the samples join the partial frame; else the tail after the last complete frame
+            // starts the other buffer
+            float2 *dst = par.frames == 0 ? carry + (size_t)par.cur * sc::kFftN + par.fill : carry + (size_t)(par.cur ^ 1) * sc::kFftN;
+            const int cnt = par.frames == 0 ? par.n : par.pos_end, from = par.n - cnt;
+            for (int i = tid; i < cnt; i += kThreads)
+                dst[i] = CPX ? ((const float2 *)row)[from + i] : make_float2(row[from + i], 0.f);
+            if (tid == 0) {
+                sc::FftState f = a.fst[c];
+                f.pos = par.pos_end; f.total += par.count;
+                if (par.count > 0) f.cpx = CPX;
+                a.fst[c] = f;
+                st.skipcounter = par.cnt_end; st.emits += (unsigned)par.count;     // emit NewFftData, :607
+            }
+        }
+        if ((par.flags || par.n > 0) && tid == 0) a.state[c] = st;
+        return;
+    }
     const long long n = par.n;
     if (n <= 0) {
         if (par.flags && tid == 0) a.state[c] = st;
@@ -116,12 +156,99 @@ __global__ __launch_bounds__(256) void scope_screens_kernel(ScopeScreenArgs a)
     }
 }
 
+// One used frame of one FFT-view receiver: blockIdx.y the receiver, blockIdx.x the frame's number k among the call's
+// used frames (a receiver with fewer leaves at once: the counts differ by receiver only where the skip values do).
+// Load (frame first + k step of the frames that complete; the call's first may begin in the carry), window and I/Q
+// swap (dsp/fft.cpp:267-288), K3's transform, |X|^2, log10f(p + K_C) + K_B in K3's epilogue arithmetic (an average of
+// 1: mean = p / 1), the bels in display order into LDS, then one lane per pixel reduces to y (sc::fft_pixel) and a plain
+// vector atomicMin folds it into the peak.  The receiver's last used frame also writes the screen and the 2048 bels.
+using FftCfg = SpecCfg<11>;
+template <int CPX> __global__ __launch_bounds__(FftCfg::T) void scope_fft_kernel(ScopeArgs a)
+{
+    constexpr int N = sc::kFftN, R0 = FftCfg::R0, G = FftCfg::G;
+    static_assert(FftCfg::N == N && FftCfg::T == 64, "one wave per frame");
+    const int c = blockIdx.y, k = blockIdx.x, t = threadIdx.x;
+    const sc::ChanParam &par = a.par[c];
+    if (par.view != sc::VIEW_FFT || k >= par.count) return;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    v2f *lds = reinterpret_cast<v2f *>(smem_raw);
+    v2f *tw2 = lds + FftCfg::LDS_DATA;
+    for (int i = t; i < 1024; i += FftCfg::T) tw2[i] = reinterpret_cast<const v2f *>(a.tw2)[i];
+    v2f w1[G];
+#pragma unroll
+    for (int e = 0; e < G; e++) w1[e] = reinterpret_cast<const v2f *>(a.tw1)[FftCfg::col(t, e)];
+    const long long j = (long long)par.first + (long long)k * par.step;          // < par.frames
+    const int fill = par.fill;
+    const v2f *carry = reinterpret_cast<const v2f *>(a.carry) + ((size_t)c * 2 + par.cur) * N;
+    const float *row = a.rows + (size_t)c * (size_t)a.stride * (CPX ? 2 : 1);
+    v2f x[32];
+#pragma unroll
+    for (int e = 0; e < G; e++)
+#pragma unroll
+        for (int n1 = 0; n1 < R0; n1++) {
+            const int i = 1024 * n1 + FftCfg::col(t, e);
+            const long long s = sc::fft_source(j, i, fill);                      // < par.n: frame j completes in the call
+            v2f v;
+            if (s < 0) v = carry[s + fill];
+            else if (CPX) v = reinterpret_cast<const v2f *>(row)[s];
+            else v = v2f{row[s], 0.f};
+            const float w = a.win[i];
+            x[e * R0 + n1] = v2f{w * v.y, w * v.x};                              // I/Q swapped, fft.cpp:280-281
+        }
+    fft_fwd_passes<11>(x, lds, tw2, w1);
+    __syncthreads();                                     // pass C has read its rows: the bels take their place
+    float *bel = reinterpret_cast<float *>(smem_raw);
+    const bool last = k == par.count - 1;
+    float *out = a.bels + (size_t)c * N;
+    int tt = t;
+    asm volatile("" : "+v"(tt));
+    const int k0 = tt >> 5, k1 = tt & 31;
+    static_for<0, 32>([&](auto Rr) {
+        constexpr int r = Rr.value;
+        const int d = ((k0 + R0 * (k1 + 32 * r)) + N / 2) & (N - 1);             // display order, fft.cpp:564-589
+        const float p = x[r].x * x[r].x + x[r].y * x[r].y;
+        const float b = (float)((double)log10f(p + a.kc) + a.kb);      // sum - sum + p, over a count of 1
+        bel[d] = b;
+        if (last) out[d] = b;
+    });
+    __syncthreads();
+    const sc::FftMap map = par.map;
+    int *peak = a.peak + (size_t)c * sc::kMaxW, *screen = a.fscreen + (size_t)c * sc::kMaxW;
+    for (int px = t; px < a.w; px += FftCfg::T) {
+        const int y = sc::fft_pixel(map, a.w, px, [&](int i) { return (double)bel[i]; });
+        atomicMin(&peak[px], y);                                                 // :1050-1051
+        if (last) screen[px] = y;
+    }
+}
+
+// every FFT-view receiver's last screen and its peak trace; a time-view receiver's rows are left alone
+__global__ __launch_bounds__(256) void scope_fft_screens_kernel(ScopeFftScreenArgs a)
+{
+    const int c = blockIdx.x;
+    if (a.par[c].view != sc::VIEW_FFT) return;
+    for (int i = threadIdx.x; i < 2 * a.w; i += 256) {
+        const int k = i >= a.w, x = k ? i - a.w : i;
+        a.out[((size_t)c * 2 + k) * (size_t)a.out_stride + x] = (k ? a.peak : a.fscreen)[(size_t)c * sc::kMaxW + x];
+    }
+}
+
 }  // namespace
 
 hipError_t scope_put_launch(const ScopeArgs &a, int cpx, hipStream_t s)
 {
     if (cpx) hipLaunchKernelGGL(scope_put_kernel<1>, dim3(a.channels), dim3(kThreads), 0, s, a);
     else hipLaunchKernelGGL(scope_put_kernel<0>, dim3(a.channels), dim3(kThreads), 0, s, a);
+    if (a.max_count > 0) {
+        const dim3 grid(a.max_count, a.channels);
+        if (cpx) hipLaunchKernelGGL(scope_fft_kernel<1>, grid, dim3(FftCfg::T), FftCfg::LDS_BYTES, s, a);
+        else hipLaunchKernelGGL(scope_fft_kernel<0>, grid, dim3(FftCfg::T), FftCfg::LDS_BYTES, s, a);
+    }
+    return hipGetLastError();
+}
+
+hipError_t scope_fft_screens_launch(const ScopeFftScreenArgs &a, hipStream_t s)
+{
+    hipLaunchKernelGGL(scope_fft_screens_kernel, dim3(a.channels), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

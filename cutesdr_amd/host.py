@@ -1292,7 +1292,8 @@ class TestGenBatch(_Obj):
 
 class ScopeBatch(_Obj):
     """C independent CTestBench oscilloscopes (gui/testbench.cpp:583-695, :819-898: the time view of DisplayData with
-    ChkForTrigger), one per receiver, reading the batch chain's fp32 rows on the device.  Setters as the reference's
+    ChkForTrigger; OnTimeDisplay(False) moves a receiver into the FFT view with its peak hold, :594-611, :1005-1068),
+    one per receiver, reading the batch chain's fp32 rows on the device.  Setters as the reference's
     slots; channel < 0: every receiver.  Trigger modes as the reference's: 0 off, 1 / 2 positive edge normal / single,
     3 / 4 negative edge normal / single."""
     _destroy = "csdr_scope_batch_destroy"
@@ -1380,3 +1381,40 @@ class ScopeBatch(_Obj):
             self.h, C.c_void_p(out.data_ptr()), out.stride(1), C.c_void_p(y.data_ptr()) if y is not None else None,
             y.stride(1) if y is not None else 0, C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)),
             "csdr_scope_batch_get_screens_all")
+
+    # ---- the FFT view (gui/testbench.cpp:594-611, :654-672, :1005-1068)
+    def OnTimeDisplay(self, timemode, channel=-1):
+        """True: the time view, False: the FFT view; a Reset of the receiver (:282-286)"""
+        check(lib().csdr_scope_batch_set_time_display(self.h, channel, 1 if timemode else 0), "csdr_scope_batch_set_time_display")
+
+    def OnEnablePeak(self, on, channel=-1):
+        """peak buffer back to h, m_TimeBuf1/2 zeroed (:334-343)"""
+        check(lib().csdr_scope_batch_enable_peak(self.h, channel, 1 if on else 0), "csdr_scope_batch_enable_peak")
+
+    def get_fft_screen(self, channel):
+        """(the last drawn frame's y, m_FftPkBuf, mapped-as-complex) of one receiver, int32 [w] each"""
+        scr, pk = np.zeros(self.w, dtype=np.int32), np.zeros(self.w, dtype=np.int32)
+        cpx = check(lib().csdr_scope_batch_get_fft_screen(self.h, channel, _vp(scr), _vp(pk)), "csdr_scope_batch_get_fft_screen")
+        return scr, pk, bool(cpx)
+
+    def get_fft_ave(self, channel):
+        """m_pFFTAveBuf of the last used frame: 2048 bels in display order"""
+        out = np.zeros(2048, dtype=np.float32)
+        check(lib().csdr_scope_batch_get_fft_ave(self.h, channel, _vp(out)), "csdr_scope_batch_get_fft_ave")
+        return out
+
+    def get_fft_state(self, channel):
+        """m_FftBufPos, m_DisplaySkipCounter, m_DisplaySkipValue, m_TotalCount since the last Reset"""
+        out = np.zeros(4, dtype=np.int64)
+        check(lib().csdr_scope_batch_get_fft_state(self.h, channel, _vp(out)), "csdr_scope_batch_get_fft_state")
+        return out
+
+    def get_fft_screens_all(self, out):
+        """out: int32 device tensor [channels, 2, >= w] (screen, peak); the rows of time-view receivers are left alone;
+        asynchronous on the current stream"""
+        import torch
+        assert out.is_cuda and out.dtype == torch.int32 and out.shape[0] >= self.channels and out.shape[1] == 2
+        assert out.stride(2) == 1 and out.stride(0) == 2 * out.stride(1)
+        check(lib().csdr_scope_batch_get_fft_screens_all(
+            self.h, C.c_void_p(out.data_ptr()), out.stride(1), C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)),
+            "csdr_scope_batch_get_fft_screens_all")

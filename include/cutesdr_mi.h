@@ -686,7 +686,7 @@ int csdr_ingest_spurcal_packets(int device, const void *d_packets, int channels,
  *
  * Deliberate deviations: a sample rate different from the last call's resets the receiver BEFORE the call's first
  * sample (the reference queues a Qt signal whose arrival time is undefined, :361-365); own generator instead of rand().
- * Out of scope: a drop-in CTestBench class (it is a QDialog), DisplayData's FFT view (its time view is the scope below), the USE_FILE playback
+ * Out of scope: a drop-in CTestBench class (it is a QDialog), the USE_FILE playback
  * kludge, a generator that emits datagrams, fusing the generator into the down-converter's loads, a shard form (a
  * shard host makes one generator per device, as for the batch sound sink).
  * -------------------------------------------------------------------------------------- */
@@ -751,9 +751,43 @@ int csdr_testgen_batch_generate_real(csdr_testgen_batch *t, float *d_out, long l
  * saturates at the ends of int32 and gives 0 for a NaN (undefined in the reference).  (4) The vertical mapping uses a
  * 64-bit product (the reference's 2*c*v overflows 32 bits for large v), its result saturates to int32, and a
  * vertical range of 0 gives y = h/2 (the reference divides by 0).
- * Out of scope: the FFT view and its peak hold, the TYPEMONO16 / TYPESTEREO16 overloads (the mono one reads
- * pBuf[i<<1], past its buffer), a drop-in CTestBench class (it is a QDialog), an automatic re-arm inside a call, a
- * shard form (a shard host makes one scope per device, as for the batch sound sink), painting.
+ *
+ * The FFT view: the frequency branch of DisplayData (:594-611, :654-672), DrawFftPlot (:1005-1068), OnEnablePeak
+ * (:334-343) and OnTimeDisplay (:282-286), per receiver.  Deviation (5): a new object is in the TIME view (the
+ * constructor's default is m_TimeDisplay = false, :110); set_time_display(s, channel, 0) moves a receiver into the FFT
+ * view.  Every put takes each receiver down the branch of its own view.
+ *   Frame carry.  Samples are appended to m_FftInBuf at m_FftBufPos, real rows as (x, 0), complex rows as they are
+ * (:599, :659-660).  At 2048 (TEST_FFTSIZE) the position returns to 0 (:600-602); then `if (++m_DisplaySkipCounter >=
+ * m_DisplaySkipValue)` sets the counter to 0 and the frame is used: PutInDisplayFFT, emit NewFftData (:603-608).  There
+ * is no `> 2` clause in this view (that one is TRIG_OFF's).  The counter is the member the time view uses; Reset puts
+ * it to -2, so the first complete frame after a reset is never used.
+ *   Skip value.  m_DisplaySkipValue = fs / (2048 * m_DisplayRate), truncated into the qint32, computed by Reset (:570)
+ * and OnDisplayRate (:257) from the rate known at that moment; set_horz_span only stores the span in this view (:272-273).
+ *   Reset (:535-538, :550-557, :570-574): SetFFTParams(2048, FALSE, 0.0, fs) and ResetFFT (the bels go to 0), frame
+ * position 0, peak buffer = h for every pixel, m_Span = (qint32)fs, then m_Span - (m_Span + 5) % 10 + 5, skip value as
+ * above, counter -2 -- beside the time-view part above, which stays as it is, in either view.  set_time_display stores
+ * the view and is a Reset (:282-286).  Deviation (1) holds here too: a call whose rate differs from the last call's
+ * resets the receiver and drops that call's samples.
+ *   The transform is CFft at 2048 points with SetFFTAve(0) (:128-132), an average size of 1 (dsp/fft.cpp:103-113): the
+ * running sum is sum - sum + p, so every used frame stands alone and the bels after a frame depend on that frame only.
+ * Window, I/Q swap, K_B, K_C and display order as csdr_fft_batch's (dsp/fft.cpp:267-288, :562-589).
+ *   Draw.  Deviation (6): NewFftData is a queued signal and the GUI draws some time later; here every used frame is
+ * drawn at once, at the moment it is used (the idealisation time_plot_done makes for the time view).  A draw is
+ * GetScreenIntegerFFTData(h, w, m_MaxdB = 10, m_MindB = -170, start, stop) with stop = m_Span / 2 and start = -m_Span /
+ * 2 if the put that completed the frame was complex (m_NewDataIsCpx), else 0, in C's integer division (:1026-1043);
+ * m_MindB is -170 because DrawFreqOverlay sets m_MaxdB - 18 * m_dBStepSize (:1257) before anything can be drawn, and
+ * the reference has no slot that changes either value.  Then peak[i] = min(peak[i], y[i]) for i < w (:1046-1052),
+ * whether or not the peak trace is shown; the screen is the last drawn frame's y.  OutBuf[w], which the reference
+ * writes in the "more bins than pixels" branch, is dropped.  With these start / stop values every pixel below w
+ * receives a bin in both branches, so no pixel is ever left over.
+ *   enable_peak (OnEnablePeak): the peak buffer goes back to h and m_TimeBuf1/2 are zeroed -- a receiver in the time
+ * view loses its ring, as in the reference; the flag itself is kept and only reported.
+ *   An FFT-view receiver needs sample_rate < 2^31 - 16 ((qint32)fs and the + 5): CSDR_EINVAL before any state changes.
+ *
+ * Out of scope: the TYPEMONO16 / TYPESTEREO16 overloads in either view (the mono one reads pBuf[i<<1], past its
+ * buffer), a drop-in CTestBench class (it is a QDialog), an automatic re-arm inside a call, a shard form (a shard host
+ * makes one scope per device, as for the batch sound sink), painting and overlays, a setter for the dB range (the
+ * reference has none).
  * -------------------------------------------------------------------------------------- */
 typedef struct csdr_scope_batch csdr_scope_batch;
 /* NULL without a HIP device (no CPU fallback); channels 1..4096 */
@@ -784,7 +818,7 @@ int csdr_scope_batch_put_cpx(csdr_scope_batch *s, const float *d_rows, long long
 /* DrawTimePlot's re-arm (:995-999): the state goes back to WAIT unless the mode is one of the two single ones;
  * applied in stream order by the next put */
 int csdr_scope_batch_time_plot_done(csdr_scope_batch *s, int channel);
-/* NewTimeData emits of every receiver since the last get_emits into h_emits[channels]; waits for the last put only
+/* NewTimeData (FFT view: NewFftData) emits of every receiver since the last get_emits into h_emits[channels]; waits for the last put only
  * (its event, on a stream of the object's own) */
 int csdr_scope_batch_get_emits(csdr_scope_batch *s, int *h_emits);
 /* host copy of m_TimeScrnBuf1/2, w entries each; waits as get_emits does */
@@ -798,6 +832,23 @@ int csdr_scope_batch_get_state(csdr_scope_batch *s, int channel, long long *stat
  * Asynchronous on `stream`, behind the puts before it. */
 int csdr_scope_batch_get_screens_all(csdr_scope_batch *s, int *d_out, long long out_stride, int *d_y, long long vert_stride,
                                      void *stream);
+/* OnTimeDisplay (:282-286): timemode != 0 the time view, 0 the FFT view; a Reset() of the receiver, applied in stream
+ * order by the next put.  CSDR_EINVAL, before any state changes, when the receiver's current rate does not fit the view */
+int csdr_scope_batch_set_time_display(csdr_scope_batch *s, int channel, int timemode);
+/* OnEnablePeak (:334-343): peak buffer back to h, m_TimeBuf1/2 zeroed, in either view; applied by the next put */
+int csdr_scope_batch_enable_peak(csdr_scope_batch *s, int channel, int on);
+/* host copies of the last drawn frame's y and of m_FftPkBuf, w entries each; returns 1 if that frame was mapped as
+ * complex (start = -m_Span / 2), 0 as real, < 0 on error; waits as get_emits does.  Before the first draw the screen is
+ * all 0 and the peak all h */
+int csdr_scope_batch_get_fft_screen(csdr_scope_batch *s, int channel, int *screen, int *peak);
+/* m_pFFTAveBuf of the last used frame: 2048 bels in display order, as csdr_fft_batch_get_ave; 0 after a Reset */
+int csdr_scope_batch_get_fft_ave(csdr_scope_batch *s, int channel, float *out2048);
+/* m_FftBufPos, m_DisplaySkipCounter, m_DisplaySkipValue, CFft's m_TotalCount since the last Reset; waits as get_emits does */
+int csdr_scope_batch_get_fft_state(csdr_scope_batch *s, int channel, long long *state4);
+/* every FFT-view receiver's last drawn y and peak buffer into d_out = device [channels][2][out_stride] int32 (screen,
+ * peak; the first w entries of a row, the rest untouched; out_stride >= w).  The rows of a receiver in the time view are
+ * left untouched.  Asynchronous on `stream`, behind the puts before it. */
+int csdr_scope_batch_get_fft_screens_all(csdr_scope_batch *s, int *d_out, long long out_stride, void *stream);
 
 #ifdef __cplusplus
 }
