@@ -34,8 +34,67 @@ template <int R, int SIGN> static void host_dft_middle(const float *in, float *o
     static_for<0, R / 4>([&](auto I) { dit_tail_middle<I.value, R, SIGN>(x); });
     for (int r = 0; r < R / 2; r++) { out[2 * r] = x[R / 4 + r].x; out[2 * r + 1] = x[R / 4 + r].y; }
 }
+// host builds of the radix-4 tail groups (dit_tail_r4 / dit_tail_middle_r4).  One group: in4 = the group's four points
+// A, B, C, D (positions I, I + R/4, I + R/2, I + 3R/4 of the network in front of its last two stages), out4 = the same
+// positions afterwards (middle: only positions 1 and 2 are finished, 0 and 3 come back as they went in)
+template <int R, int SIGN> static int host_tail_r4(int i, int middle, const float *in4, float *out4)
+{
+    int done = -1;
+    static_for<0, R / 4>([&](auto I) {
+        if (I.value != i) return;
+        constexpr int Q = R / 4;
+        v2f x[R];
+        for (int p = 0; p < R; p++) x[p] = v2f{0.0f, 0.0f};
+        for (int q = 0; q < 4; q++) x[I.value + q * Q] = v2f{in4[2 * q], in4[2 * q + 1]};
+        if (middle) dit_tail_middle_r4<I.value, R, SIGN>(x); else dit_tail_r4<I.value, R, SIGN>(x);
+        for (int q = 0; q < 4; q++) { out4[2 * q] = x[I.value + q * Q].x; out4[2 * q + 1] = x[I.value + q * Q].y; }
+        done = 0;
+    });
+    return done;
+}
+// in: R complex points in NATURAL order; out: their unnormalised DFT of sign `sign` as the 16384-point real-gain kernel's
+// register networks compute it: head groups, (R = 32: the middle stage,) radix-4 tail groups -- all R rows, or (middle)
+// rows R/4 ... 3R/4 - 1 from the pruned groups
+template <int R, int SIGN> static void host_dft_r4(int middle, const float *in, float *out)
+{
+    v2f x[R];
+    for (int n = 0; n < R; n++) x[bitrev<R>(n)] = v2f{in[2 * n], in[2 * n + 1]};
+    static_for<0, R / 4>([&](auto G) { dit_head4<G.value, R, SIGN>(x); });
+    if constexpr (R == 32) dit_single<8, 32, SIGN>(x);
+    if (middle) {
+        static_for<0, R / 4>([&](auto I) { dit_tail_middle_r4<I.value, R, SIGN>(x); });
+        for (int r = 0; r < R / 2; r++) { out[2 * r] = x[R / 4 + r].x; out[2 * r + 1] = x[R / 4 + r].y; }
+    } else {
+        static_for<0, R / 4>([&](auto I) { dit_tail_r4<I.value, R, SIGN>(x); });
+        for (int r = 0; r < R; r++) { out[2 * r] = x[r].x; out[2 * r + 1] = x[r].y; }
+    }
+}
 
 extern "C" {
+
+int csdr__host_dit_tail_r4(int r, int sign, int i, int middle, const float *in4, float *out4)
+{
+    if (r == 16) return sign > 0 ? host_tail_r4<16, +1>(i, middle, in4, out4) : host_tail_r4<16, -1>(i, middle, in4, out4);
+    if (r == 32) return sign > 0 ? host_tail_r4<32, +1>(i, middle, in4, out4) : host_tail_r4<32, -1>(i, middle, in4, out4);
+    return -1;
+}
+int csdr__host_dft_r4(int r, int sign, int middle, const float *in, float *out)
+{
+    if (r == 16 && sign > 0) host_dft_r4<16, +1>(middle, in, out);
+    else if (r == 16) host_dft_r4<16, -1>(middle, in, out);
+    else if (r == 32 && sign > 0) host_dft_r4<32, +1>(middle, in, out);
+    else if (r == 32) host_dft_r4<32, -1>(middle, in, out);
+    else return -1;
+    return 0;
+}
+// the factors of a unit twiddle the radix-4 groups are built from: e^{sign j 2 pi k/32} = j^rot m (1 + j tau)
+int csdr__host_tw_factors(int k, int sign, double *m, double *tau)
+{
+    const TwFactors f = tw_factors(k, sign);
+    *m = f.m; *tau = f.tau;
+    return f.rot;
+}
+int csdr__host_fastfir2_radix4(void) { return fastfir2_radix4(); }
 
 int csdr__host_fastfir_design(int n, double flo, double fhi, double off, double fs, double *h_out)
 {

@@ -55,6 +55,10 @@ namespace csdr {
 #ifndef K1_HREG2K
 #define K1_HREG2K 8         // ... at N = 2048 (the sixteen base twiddles are fetched where they are used: 0 / 4 / 8 resident measured 0.710 / 0.697 / 0.689 ms)
 #endif
+#ifndef K1_RADIX4
+#define K1_RADIX4 1         // real-gain kernel: the last two stages of every register network as radix-4 groups on shared
+                            // products (fft_core.hpp: dit_tail_r4), eleven packed instructions a group instead of twelve
+#endif
 static_assert(K1_TWREG >= 0 && K1_TWREG <= 16, "K1_TWREG");
 
 #define CSDR_SB() __builtin_amdgcn_sched_barrier(0)
@@ -189,6 +193,7 @@ struct K1Cfg {
     static constexpr bool W1_RESIDENT = R0 > K1_W1_FETCH_MAX_R0;    // the base twiddles stay in registers for the whole run
     static constexpr int HREG = RG ? 0 : (LOG2N == 12 ? K1_HREG4K : (LOG2N == 11 ? K1_HREG2K : K1_HREG));   // resident float4 of H
     static constexpr int TWREG = RG ? K1_TWREG : 0;      // pass twiddles k1 = 1 ... TWREG of F2 / I2 that stay in registers
+    static constexpr bool R4 = RG && K1_RADIX4 != 0;     // tail groups in the radix-4 form (other rounding order: this kernel only)
 
     // the register arrays a thread carries through the block loop
     using Y = v2f[G][R0];                   // F1 / I3: the R0 points of this thread's G columns
@@ -306,15 +311,15 @@ template <int LOG2N> __device__ __forceinline__ void k1_load_w1(const K1Thread &
 //
 // The last stage, the twiddles and the stores, four float4 per group, stored one group behind.
 // N = 16384: tail group i finishes rows k0 = i, i+4, i+8, i+12; rows above 8 take conj(power 16 - k0) (K1Cfg::TWS)
-template <int LOG2N> __device__ __forceinline__ void k1_f1_rows16(const K1Thread &c, typename K1Cfg<LOG2N>::Y &y, typename K1Cfg<LOG2N>::Pw &pw)
+template <int LOG2N, bool RG> __device__ __forceinline__ void k1_f1_rows16(const K1Thread &c, typename K1Cfg<LOG2N>::Y &y, typename K1Cfg<LOG2N>::Pw &pw)
 {
     using Cfg = K1Cfg<LOG2N>;
     constexpr int R0 = Cfg::R0;
     v4f wv[16];                                    // row k0 at [k0]
     one_group_behind<R0 / 4>([&](auto Ii) {
         constexpr int i = Ii.value;
-        dit_tail<i, R0, +1>(y[0]);
-        dit_tail<i, R0, +1>(y[1]);
+        dit_tail_sel<K1Cfg<LOG2N, RG>::R4, i, R0, +1>(y[0]);
+        dit_tail_sel<K1Cfg<LOG2N, RG>::R4, i, R0, +1>(y[1]);
         static_for<0, 4>([&](auto P) {
             constexpr int k0 = i + 4 * P.value;
             if constexpr (k0 > R0 / 2) {
@@ -384,7 +389,7 @@ template <int LOG2N> __device__ __forceinline__ void k1_f1_rows84(const K1Thread
         });
     });
 }
-template <int LOG2N> __device__ __forceinline__ void k1_pass_f1(const K1Thread &c, int b, K1Half &oldh, K1Half &newh, typename K1Cfg<LOG2N>::Pw &pw)
+template <int LOG2N, bool RG> __device__ __forceinline__ void k1_pass_f1(const K1Thread &c, int b, K1Half &oldh, K1Half &newh, typename K1Cfg<LOG2N>::Pw &pw)
 {
     using Cfg = K1Cfg<LOG2N>;
     constexpr int R0 = Cfg::R0, G = Cfg::G, HALF = Cfg::HALF;
@@ -409,7 +414,7 @@ template <int LOG2N> __device__ __forceinline__ void k1_pass_f1(const K1Thread &
     k1_load_half<LOG2N>(c.r_in, c.voff, (b + 1 < c.nblocks ? b + 1 : c.nblocks - 1) * (Cfg::L * 8), oldh.v);
     CSDR_SB();
     CSDR_PRIO(0);
-    if constexpr (R0 == 16) k1_f1_rows16<LOG2N>(c, y, pw);
+    if constexpr (R0 == 16) k1_f1_rows16<LOG2N, RG>(c, y, pw);
     else if constexpr (R0 == 2) k1_f1_rows2<LOG2N>(c, y);
     else k1_f1_rows84<LOG2N>(c, y, pw);
 }
@@ -438,7 +443,7 @@ __device__ __forceinline__ void k1_f2_tail_shared(const K1Thread &c, v2f (&x)[32
         constexpr int s = St.value, i = tws_group(s);
         if constexpr (s < 7 && tws_opens(s + 1)) load_set(int_c<tws_set(s + 1)>{});
         if constexpr (!RG) { k1_fetch_h<LOG2N, 2 * s>(c, hv); k1_fetch_h<LOG2N, 2 * s + 1>(c, hv); }
-        dit_tail<i, 32, +1>(x);
+        dit_tail_sel<K1Cfg<LOG2N, RG>::R4, i, 32, +1>(x);
         static_for<0, 4>([&](auto P) {
             constexpr int k1 = i + 8 * P.value;
             if constexpr (k1 != 0 && k1 <= 16) x[k1] = cmul(x[k1], tw[tws_set_of(k1)][tws_slot_of(k1)]);
@@ -531,7 +536,7 @@ __device__ __forceinline__ void k1_pass_f3(const K1Thread &c, v2f (&x)[32], type
     // group g: multiply by H (folded into that group's first butterflies) and go straight on
     static_for<0, 8>([&](auto Ii) {
         constexpr int i = Ii.value, g = bitrev<8>(i);
-        dit_tail<i, 32, +1>(x);
+        dit_tail_sel<K1Cfg<LOG2N, RG>::R4, i, 32, +1>(x);
         // times H: the products of the odd inputs ride in the FMA butterflies of the inverse's first stage
         y[4 * g] = x[i]; y[4 * g + 1] = x[i + 16]; y[4 * g + 2] = x[i + 8]; y[4 * g + 3] = x[i + 24];
         if constexpr (RG)
@@ -549,8 +554,8 @@ __device__ __forceinline__ void k1_pass_f3(const K1Thread &c, v2f (&x)[32], type
     v4f wv[16];
     one_group_behind<4>([&](auto Q) {
         constexpr int q = Q.value;
-        dit_tail<2 * q, 32, -1>(x);
-        dit_tail<2 * q + 1, 32, -1>(x);
+        dit_tail_sel<K1Cfg<LOG2N, RG>::R4, 2 * q, 32, -1>(x);
+        dit_tail_sel<K1Cfg<LOG2N, RG>::R4, 2 * q + 1, 32, -1>(x);
         static_for<0, 4>([&](auto P) {
             constexpr int j = q + 4 * P.value;
             wv[j] = store_operand(x[2 * j], x[2 * j + 1]);
@@ -625,7 +630,7 @@ template <int LOG2N, bool RG> __device__ __forceinline__ void k1_pass_i2(const K
     else k1_i2_head_plain<LOG2N, RG>(c, x, twr);
     dit_single<8, 32, -1>(x);
     CSDR_SB();
-    one_group_behind_st8<8>([&](auto I) { dit_tail<I.value, 32, -1>(x); }, [&](auto I) {
+    one_group_behind_st8<8>([&](auto I) { dit_tail_sel<K1Cfg<LOG2N, RG>::R4, I.value, 32, -1>(x); }, [&](auto I) {
         static_for<0, 4>([&](auto P) {
             constexpr int n1 = I.value + 8 * P.value;
             lds_st8(c.col + 34 * n1, x[n1]);
@@ -645,8 +650,8 @@ template <int LOG2N, bool RG> __device__ __forceinline__ void k1_i3_rows16(const
         constexpr int i = I.value;
         if constexpr (RG) {
             // the scale by P left out the response's delay of N/4 samples: output row n1 is row n1 + 4
-            dit_tail_middle<i, R0, -1>(y[0]);     // only rows 4..11 of the inverse transform are kept
-            dit_tail_middle<i, R0, -1>(y[1]);
+            dit_tail_middle_sel<K1Cfg<LOG2N, RG>::R4, i, R0, -1>(y[0]);     // only rows 4..11 of the inverse transform are kept
+            dit_tail_middle_sel<K1Cfg<LOG2N, RG>::R4, i, R0, -1>(y[1]);
             sv[2 * i] = store_operand(y[0][i + 4], y[1][i + 4]);
             sv[2 * i + 1] = store_operand(y[0][i + 8], y[1][i + 8]);
         } else {
@@ -846,7 +851,7 @@ template <int LOG2N, bool RG> __device__ __forceinline__ void fastfir_os2_body(c
     auto one_block = [&](const int b, K1Half &oldh, K1Half &newh) {
         CSDR_SB();
         CSDR_PRIO(1);
-        k1_pass_f1<LOG2N>(c, b, oldh, newh, pw);
+        k1_pass_f1<LOG2N, RG>(c, b, oldh, newh, pw);
         CSDR_STAMP(0);                             // F1 (and the loop-carried moves)
         k1_block_barrier<LOG2N>();
         CSDR_STAMP(1);                             // barrier after F1
@@ -962,6 +967,7 @@ hipError_t fastfir2_launch(int log2n, const FastFirArgs &a, hipStream_t stream, 
 }
 
 int fastfir2_twreg() { return K1_TWREG; }
+int fastfir2_radix4() { return K1Cfg<14, true>::R4 ? 1 : 0; }
 
 // Host mirror of the kernel's index algebra: thread t of pass F3 owns k0 = t >> 5 (sub-transform) and k1 = t & 31
 // (its row), and consumes H in the order its tail groups finish bins: float4 j = 2 i + h of thread t, half e,

@@ -464,6 +464,87 @@ __host__ __device__ __forceinline__ void dit_tail(v2f (&x)[R])
     bfly_dit<(I + Q) * (32 / R), SIGN>(x[I + Q], x[I + 3 * Q]);
 }
 
+// ---- the last two stages of a DIT network as ONE radix-4 group on shared products ------------------------------
+// Tail group I pairs (A, B) and (C, D) with alpha = W^(2k), then (A', C') with beta = W^k and (B', D') with S j beta
+// (W = e^{SIGN j 2 pi / R}, k = I, A ... D = x[I], x[I + R/4], x[I + R/2], x[I + 3R/4]): four butterflies, three packed
+// instructions each where the twiddle is not 1 or +-j -- twelve.  A unit twiddle is w = j^rot m (1 + j tau) with |tau| <= 1
+// (m = cos, tau = tan of its angle; beyond 45 degrees a factor j comes out and m = sin, tau = -cot), and x^ = x + j tau x
+// is one packed FMA on the swizzled operand.  With gamma = alpha beta:
+//     B^ (1);  T1, T2 = A +- m_a j^rot_a B^ (2);  C^, D^ on beta, gamma (2);  S1, S2 = C^ +- (gamma / beta's m and rot) D^ (2);
+//     A'', C'' = T1 +- m_b j^rot_b S1 (2);  B'', D'' = T2 +- S j m_b j^rot_b S2 (2)                        -- eleven,
+// every constant a compile-time literal, every rotation by j an operand swizzle with a sign.  Only the rounding order
+// differs from the four butterflies.  Groups whose alpha is 1 or +-j gain nothing and stay on dit_tail's code.
+constexpr double kCos32d[9] = {1.0, 0.98078528040323044913, 0.92387953251128675613, 0.83146961230254523708,
+                               0.70710678118654752440, 0.55557023301960222474, 0.38268343236508977173,
+                               0.19509032201612826785, 0.0};
+constexpr double cos32d(int k)
+{
+    k &= 31;
+    if (k > 16) k = 32 - k;
+    return k <= 8 ? kCos32d[k] : -kCos32d[16 - k];
+}
+struct TwFactors { int rot; double m, tau; };
+// e^{SIGN j 2 pi K/32} = j^rot m (1 + j tau), |tau| <= 1
+constexpr TwFactors tw_factors(int K, int SIGN)
+{
+    const double c = cos32d(K), s = SIGN * cos32d(K + 24);
+    const double ac = c < 0 ? -c : c, as = s < 0 ? -s : s;
+    if (ac >= as) return TwFactors{0, c, s / c};
+    return TwFactors{1, s, -c / s};                          // c + j s = j s (1 - j c / s)
+}
+// acc + j^ROT m v: one packed FMA (m a compile-time constant at every call)
+template <int ROT>
+__host__ __device__ __forceinline__ v2f fma_jrot(v2f v, float m, v2f acc)
+{
+    constexpr int r = ((ROT % 4) + 4) % 4;
+    if constexpr (r == 0) return __builtin_elementwise_fma(v, v2f{m, m}, acc);
+    else if constexpr (r == 1) return __builtin_elementwise_fma(v.yx, v2f{-m, m}, acc);
+    else if constexpr (r == 2) return __builtin_elementwise_fma(v, v2f{-m, -m}, acc);
+    else return __builtin_elementwise_fma(v.yx, v2f{m, -m}, acc);
+}
+// MIDDLE: only x[I + R/4] and x[I + R/2] are finished (dit_tail_middle's outputs; the other two rows are left as they were)
+template <int I, int R, int SIGN, bool MIDDLE>
+__host__ __device__ __forceinline__ void dit_tail_r4_group(v2f (&x)[R])
+{
+    static_assert(R >= 8 && I < R / 4, "dit_tail_r4");
+    constexpr int Q = R / 4, KA = I * (64 / R), KB = I * (32 / R);
+    if constexpr (KA % 8 == 0) {
+        if constexpr (MIDDLE) dit_tail_middle<I, R, SIGN>(x); else dit_tail<I, R, SIGN>(x);
+    } else {
+        constexpr TwFactors fa = tw_factors(KA, SIGN), fb = tw_factors(KB, SIGN), fg = tw_factors(KA + KB, SIGN);
+        constexpr float ta = (float)fa.tau, ma = (float)fa.m, tb = (float)fb.tau, mb = (float)fb.m, tg = (float)fg.tau;
+        constexpr float r = (float)(fg.m / fb.m);
+        constexpr int RR = fg.rot - fb.rot, SJ = SIGN > 0 ? 1 : 3;
+        const v2f A = x[I], B = x[I + Q], C = x[I + 2 * Q], D = x[I + 3 * Q];
+        const v2f Bh = fma_jrot<1>(B, ta, B);
+        const v2f T1 = fma_jrot<fa.rot>(Bh, ma, A);
+        const v2f T2 = fma_jrot<fa.rot + 2>(Bh, ma, A);
+        const v2f Ch = fma_jrot<1>(C, tb, C);
+        const v2f Dh = fma_jrot<1>(D, tg, D);
+        const v2f S1 = fma_jrot<RR>(Dh, r, Ch);
+        const v2f S2 = fma_jrot<RR + 2>(Dh, r, Ch);
+        if constexpr (!MIDDLE) x[I] = fma_jrot<fb.rot>(S1, mb, T1);
+        x[I + 2 * Q] = fma_jrot<fb.rot + 2>(S1, mb, T1);
+        x[I + Q] = fma_jrot<fb.rot + SJ>(S2, mb, T2);
+        if constexpr (!MIDDLE) x[I + 3 * Q] = fma_jrot<fb.rot + SJ + 2>(S2, mb, T2);
+    }
+}
+template <int I, int R, int SIGN>
+__host__ __device__ __forceinline__ void dit_tail_r4(v2f (&x)[R]) { dit_tail_r4_group<I, R, SIGN, false>(x); }
+template <int I, int R, int SIGN>
+__host__ __device__ __forceinline__ void dit_tail_middle_r4(v2f (&x)[R]) { dit_tail_r4_group<I, R, SIGN, true>(x); }
+// dit_tail / dit_tail_middle, or their radix-4 forms where R4 (the kernel's choice per instantiation)
+template <bool R4, int I, int R, int SIGN>
+__host__ __device__ __forceinline__ void dit_tail_sel(v2f (&x)[R])
+{
+    if constexpr (R4) dit_tail_r4<I, R, SIGN>(x); else dit_tail<I, R, SIGN>(x);
+}
+template <bool R4, int I, int R, int SIGN>
+__host__ __device__ __forceinline__ void dit_tail_middle_sel(v2f (&x)[R])
+{
+    if constexpr (R4) dit_tail_middle_r4<I, R, SIGN>(x); else dit_tail_middle<I, R, SIGN>(x);
+}
+
 // w^k for k = 0..R-1 by a log-depth product tree (pw[0] unused = 1)
 template <int R>
 __host__ __device__ __forceinline__ void twiddle_powers(v2f w, v2f (&pw)[R])
