@@ -252,6 +252,9 @@ def alt_lib(name, extra, units=("fastfir2_kernels",), verbose=False):
 # the build of K1 whose pass twiddles k1 = 1, 2 and 3 stay in registers (fastfir2_kernels.hip: K1_TWREG), kept beside
 # the product's library for tests/test_fastfir_twreg_gpu.py
 TWREG3 = ("twreg3", ["-DK1_TWREG=3"])
+# ... and the build whose real-gain kernel rebuilds the outer-pass twiddle powers in every block (K1_PWRES = 0: the
+# instruction stream before the powers became resident), for the byte-for-byte test tests/test_fastfir_pwres_gpu.py
+PWRES0 = ("pwres0", ["-DK1_PWRES=0"])
 
 
 if __name__ == "__main__":

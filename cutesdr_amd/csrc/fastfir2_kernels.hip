@@ -18,8 +18,8 @@
 //     ds_write2_b64 (half the LDS rate of ds_read_b64) nor reorders them, and still counts them
 //     in its s_waitcnt bookkeeping;
 //   * sched_barrier(0) between groups pins that order against the machine scheduler.
-// The outer-pass twiddle powers are computed once per block (pass I3) and reused by pass F1 of the
-// next block.
+// The outer-pass twiddle powers: in the real-gain kernel computed once, in front of the block loop, and resident for the
+// whole run (K1_PWRES); in every other kernel computed once per block (pass I3) and reused by pass F1 of the next block.
 #define CSDR_FMA_BFLY 1          // FMA-form decimation-in-time butterflies (fft_core.hpp)
 #define CSDR_PLAIN_CONST_FMA 1   // ... written without asm where the twiddle is a compile-time constant
 #include "launch_once.hpp"
@@ -42,7 +42,7 @@ namespace csdr {
 #endif
 #ifndef K1_TWREG
 #define K1_TWREG 16         // real-gain kernel: pass twiddles k1 = 1 ... of F2 / I2 that stay in registers.  All sixteen the
-                            // passes use fit (252 VGPRs, no scratch) and none is read from LDS (HISTORY.md; 3 is the build
+                            // passes use fit (254 VGPRs beside the resident outer powers, no scratch) and none is read from LDS (HISTORY.md; 3 is the build
                             // tests/test_fastfir_twreg_gpu.py runs beside it)
 #endif
 #ifndef K1_HREG4K
@@ -58,6 +58,10 @@ namespace csdr {
 #ifndef K1_RADIX4
 #define K1_RADIX4 1         // real-gain kernel: the last two stages of every register network as radix-4 groups on shared
                             // products (fft_core.hpp: dit_tail_r4), eleven packed instructions a group instead of twelve
+#endif
+#ifndef K1_PWRES
+#define K1_PWRES 1          // real-gain kernel: the outer-pass twiddle powers are built once in front of the block loop and stay
+                            // in registers for the whole run (0: rebuilt at the top of every I3, as in every other kernel)
 #endif
 static_assert(K1_TWREG >= 0 && K1_TWREG <= 16, "K1_TWREG");
 
@@ -194,6 +198,7 @@ struct K1Cfg {
     static constexpr int HREG = RG ? 0 : (LOG2N == 12 ? K1_HREG4K : (LOG2N == 11 ? K1_HREG2K : K1_HREG));   // resident float4 of H
     static constexpr int TWREG = RG ? K1_TWREG : 0;      // pass twiddles k1 = 1 ... TWREG of F2 / I2 that stay in registers
     static constexpr bool R4 = RG && K1_RADIX4 != 0;     // tail groups in the radix-4 form (other rounding order: this kernel only)
+    static constexpr bool PW_RESIDENT = RG && K1_PWRES != 0;   // the outer-pass powers are built once per run, not once per block
 
     // the register arrays a thread carries through the block loop
     using Y = v2f[G][R0];                   // F1 / I3: the R0 points of this thread's G columns
@@ -289,8 +294,10 @@ template <int LOG2N> __device__ __forceinline__ void k1_load_half(rsrc_t r, int 
         }
 }
 
-// outer-pass twiddles W_N^{n2 k0}, n2 = 2t+e, k0 = 1..15: pw[e][k0].  Rebuilt at the top of every
-// I3 and kept for F1 of the next block only: live across the whole loop they would not fit beside H
+// outer-pass twiddles W_N^{n2 k0}, n2 = 2t+e: pw[e][k0], k0 = 1 ... PWN - 1.  On complex H (and at the smaller sizes) rebuilt
+// at the top of every I3 and kept for F1 of the next block only: live across the whole loop they would not fit beside H.
+// The real-gain kernel holds no H and eight powers per column instead of fifteen: there the set fastfir_os2_body builds
+// in front of the block loop stays for the whole run (K1Cfg::PW_RESIDENT) -- the same products on the same inputs, once
 // (N = 2048: sixteen base twiddles and no powers -- they are fetched where the outer passes use them, 8 KB of table
 // that stays in the vector cache, instead of thirty-two registers held for the whole run)
 template <int LOG2N> __device__ __forceinline__ v4f k1_w_pair(const K1Thread &c, int pp)
@@ -723,8 +730,10 @@ __device__ __forceinline__ void k1_pass_i3(const K1Thread &c, int b, typename K1
     });
     if constexpr (R0 > 2) {
         if constexpr (!Cfg::W1_RESIDENT) k1_load_w1<LOG2N>(c, w1);
+        if constexpr (!K1Cfg<LOG2N, RG>::PW_RESIDENT) {
 #pragma unroll
-        for (int e = 0; e < G; e++) twiddle_powers<Cfg::PWN>(opaque(w1[e]), pw[e]);     // while the reads are in flight
+            for (int e = 0; e < G; e++) twiddle_powers<Cfg::PWN>(opaque(w1[e]), pw[e]);     // while the reads are in flight
+        }
         CSDR_SB();
         static_for<0, (R0 >= 8 ? R0 / 4 : 1)>([&](auto Gg) {
             constexpr int g = Gg.value;
@@ -968,6 +977,7 @@ hipError_t fastfir2_launch(int log2n, const FastFirArgs &a, hipStream_t stream, 
 
 int fastfir2_twreg() { return K1_TWREG; }
 int fastfir2_radix4() { return K1Cfg<14, true>::R4 ? 1 : 0; }
+int fastfir2_pwres() { return K1Cfg<14, true>::PW_RESIDENT ? 1 : 0; }
 
 // Host mirror of the kernel's index algebra: thread t of pass F3 owns k0 = t >> 5 (sub-transform) and k1 = t & 31
 // (its row), and consumes H in the order its tail groups finish bins: float4 j = 2 i + h of thread t, half e,

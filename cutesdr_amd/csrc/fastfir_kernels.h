@@ -45,6 +45,8 @@ hipError_t fastfir2_launch(int log2n, const FastFirArgs &a, hipStream_t stream, 
 int fastfir2_twreg();
 // 1 where that unit's real-gain kernel runs its tail groups in the radix-4 form (K1_RADIX4; fft_core.hpp: dit_tail_r4)
 int fastfir2_radix4();
+// 1 where that unit's real-gain kernel keeps the outer-pass twiddle powers in registers for the whole run (K1_PWRES)
+int fastfir2_pwres();
 // natural-order spectrum bin of H slot (float4 index j*(N/32) + t, half e) of that kernel
 int fastfir2_bin_of(int log2n, int t, int j, int e);
 // natural-order spectrum bin of gain slot (float4 index i*(N/32) + t, component c): the same per-thread order, four
