@@ -1,6 +1,5 @@
 // downconv_kernels.hip -- launch side of the NCO + decimator cascade (K2): the LDS layout, the run-time-plan
 // instantiation of the kernel and the table of the precompiled plans (downconv_kernel.hpp holds the device code).
-#include "launch_once.hpp"
 #include "downconv_kernel.hpp"
 
 namespace csdr {
@@ -55,21 +54,7 @@ hipError_t downconv_launch(DcArgs &a, hipStream_t stream)
             for (int s = 0; s < p->ns; s++) same = same && p->kind[s] == a.kind[s];
             if (same) return p->launch(a, stream);
         }
-    // (once per device: launch_once.hpp; never needed in practice -- a cascade is ~10 KB)
-    if (a.nb_mask) {
-        if (lds > 64 * 1024) {
-            hipError_t e = CSDR_MAX_LDS_ONCE((&downconv_kernel<DcPlanDyn, true>), lds);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL((downconv_kernel<DcPlanDyn, true>), dim3(a.nchan * a.nseg), dim3(DC_T), lds, stream, a);
-        return hipGetLastError();
-    }
-    if (lds > 64 * 1024) {
-        hipError_t e = CSDR_MAX_LDS_ONCE((&downconv_kernel<DcPlanDyn>), lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(downconv_kernel<DcPlanDyn>, dim3(a.nchan * a.nseg), dim3(DC_T), lds, stream, a);
-    return hipGetLastError();
+    return dc_launch<DcPlanDyn>(a, lds, stream);
 }
 
 }  // namespace csdr

@@ -21,21 +21,36 @@ struct WireIn {                          // optional packed input of a kernel; p
 typedef float wf2 __attribute__((ext_vector_type(2)));
 typedef float wf4 __attribute__((ext_vector_type(4)));
 
-// sample i of a channel's datagram sequence
-__device__ __forceinline__ wf2 wire_sample(const unsigned char *chan, int pkt_len, long i64)
+// Sample i of a channel's datagram sequence, in two halves for kernels that prefetch: wire_sample_fetch issues the
+// loads and leaves the raw words (three 16-bit halves of a 24-bit sample, or the one word of a 16-bit sample),
+// wire_sample_decode turns them into the complex sample where it is consumed.
+__device__ __forceinline__ void wire_sample_fetch(const unsigned char *chan, int pkt_len, long i64, unsigned w[3])
 {
     const unsigned i = (unsigned)i64;
     if (pkt_len == 1444) {
         const unsigned q = i / 240u, j = i - q * 240u;
         const unsigned short *h = reinterpret_cast<const unsigned short *>(chan + (q * 1444u + 4u + 6u * j));   // 2-byte aligned
-        const unsigned h0 = h[0], h1 = h[1], h2 = h[2];
-        const int vi = (int)((h0 << 8) | ((h1 & 0xffu) << 24));
-        const int vq = (int)(((h1 >> 8) << 8) | (h2 << 16));
+        w[0] = h[0]; w[1] = h[1]; w[2] = h[2];
+    } else {
+        const unsigned q = i >> 8, j = i & 255u;
+        w[0] = *reinterpret_cast<const unsigned *>(chan + (q * 1028u + 4u + 4u * j));
+    }
+}
+__device__ __forceinline__ wf2 wire_sample_decode(const unsigned w[3], int pkt_len)
+{
+    if (pkt_len == 1444) {
+        const int vi = (int)((w[0] << 8) | ((w[1] & 0xffu) << 24));
+        const int vq = (int)(((w[1] >> 8) << 8) | (w[2] << 16));
         return wf2{(float)vi * (1.0f / 65536.0f), (float)vq * (1.0f / 65536.0f)};
     }
-    const unsigned q = i >> 8, j = i & 255u;
-    const unsigned d = *reinterpret_cast<const unsigned *>(chan + (q * 1028u + 4u + 4u * j));
-    return wf2{(float)(short)(d & 0xffffu), (float)(short)(d >> 16)};
+    return wf2{(float)(short)(w[0] & 0xffffu), (float)(short)(w[0] >> 16)};
+}
+__device__ __forceinline__ wf2 wire_sample(const unsigned char *chan, int pkt_len, long i64)
+{
+    unsigned w[3];
+    if (pkt_len == 1444) { wire_sample_fetch(chan, 1444, i64, w); return wire_sample_decode(w, 1444); }   // one format test
+    wire_sample_fetch(chan, 1028, i64, w);
+    return wire_sample_decode(w, 1028);
 }
 
 // Samples i, i+1 (i even: a pair never straddles a datagram, both sample counts are even) with aligned 32-bit

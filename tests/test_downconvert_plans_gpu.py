@@ -224,6 +224,89 @@ def test_maximum_segments_with_ragged_and_short_last_segments(plans):
         b.close()
 
 
+# ------------------------------------------------------------------------------------------------ C: blanker in front
+class _DcBlank(C.Structure):
+    """DcBlank of downconv_kernels.h: what csdr__noiseproc_batch_mask leaves for the down-converter"""
+    _fields_ = [("mask", C.c_void_p), ("mask_stride", C.c_long), ("state", C.c_void_p), ("hist", C.c_void_p)]
+
+
+@pytest.mark.parametrize("dyn", [0, 1], ids=["compiled", "runtime"])
+@pytest.mark.parametrize("fs,width", [(2e6, 20.0), (2000200.0, 21.0)], ids=["odd-delay", "even-delay"])
+@pytest.mark.parametrize("src", ["rows", 1028, 1444])
+def test_blanked_down_converter_matches_fp64(oracle, src, fs, width, dyn):
+    """The down-converter that applies the noise blanker's mask in its own loads (sample i = mask bit ? 0 :
+    raw[i - delay_n - 1]), on its own: one FM channel, float rows and both datagram formats, D1 = delay_n + 1 = 21 and
+    22 (behind an odd delay the datagram form fetches aligned pairs one sample early, rotates them across the wave and
+    decodes one trailing sample), three calls of 64, 4 and 130 datagrams (or 256-sample rows) cut into as many segments
+    as the host rule allows -- the first reaches into the blanker's history, the second is no longer than the warm-up.
+    Expected: the fp64 cascade over the oracle blanker's output on the oracle's unpacked samples (mask + delay give
+    that stream word for word: test_frontend_gpu.py::test_blank_mask_is_bit_exact).  Input: white I/Q of amplitude
+    1500 with +25000 impulses at rate 2e-4, as there; dc_ref.dc_reference_fp32 of the six blanked streams (6 % of the
+    samples zeroed) stays within 0.16 .. 0.22 tol of the fp64 reference, as it does for white input."""
+    import cutesdr_amd as ca
+    from test_frontend_gpu import _pack16, _pack24
+    L = _lib()
+    L.csdr__noiseproc_batch_mask.restype = C.c_int
+    L.csdr__noiseproc_batch_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_longlong, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]
+    L.csdr__downconvert_batch_process_rows.restype = C.c_int
+    L.csdr__downconvert_batch_process_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p,
+                                                       C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(_DcBlank)]
+    per = 240 if src == 1444 else 256
+    counts = [64, 4, 130]
+    tot = sum(counts) * per
+    assert all(npk * per % 32 == 0 for npk in counts) and counts[1] * per <= D.warmup_len(FM) < counts[0] * per
+    rng = np.random.default_rng(17)
+    x = 1500.0 * (rng.standard_normal(tot) + 1j * rng.standard_normal(tot))
+    x[rng.random(tot) < 2e-4] += 25000.0
+    if src == "rows":
+        xs = x.astype(np.complex64)
+    else:
+        raw = (_pack24 if src == 1444 else _pack16)(x)
+        xs = oracle.unpack_packets(raw, src).astype(np.complex64)
+    delay1 = int(width * 1e-6 * fs) // 2 + 1
+    assert delay1 == (21 if width == 20.0 else 22)
+    freq = D.parity_freq(fs)
+    nb, b = ca.NoiseProcBatch(1), ca.DownConvertBatch(1)
+    q = oracle.CNoiseProc(); q.SetupBlanker(True, 25.0, width, fs)
+    bufs, got, blanked = [], [], []
+    try:
+        nb.setup(True, 25.0, width, fs)
+        assert b.set_data_rate(fs, 15000.0) == fs / 32 and tuple(b.stages(0)) == FM
+        b.set_frequency(freq)
+        assert L.csdr__downconvert_batch_set_wgs(b.h, 1 << 20) == 0
+        k0 = 0
+        with kernel_form(dyn):
+            for npk in counts:
+                n, a0 = npk * per, k0 * per
+                words = (n + 31) // 32 + 64
+                part = np.ascontiguousarray(xs[a0:a0 + n] if src == "rows" else raw[k0:k0 + npk])
+                dp, dm, do = ca.DeviceBuffer(part.nbytes), ca.DeviceBuffer(words * 4), ca.DeviceBuffer(8 * (n >> 5))
+                bufs += [dp, dm, do]
+                dp.upload(part)
+                rows, pk, npk_arg, fmt = (C.c_void_p(dp.ptr), None, 0, 0) if src == "rows" else (None, C.c_void_p(dp.ptr), npk, src)
+                st, hi = C.c_void_p(), C.c_void_p()
+                assert L.csdr__noiseproc_batch_mask(nb.h, rows, n, pk, npk_arg, fmt, n, C.c_void_p(dm.ptr), words,
+                                                    C.byref(st), C.byref(hi), None) == 0
+                blank = _DcBlank(dm.ptr, words, st.value, hi.value)
+                assert L.csdr__downconvert_batch_process_rows(b.h, rows, n, None, n, C.c_void_p(do.ptr), n >> 5, None, pk, fmt,
+                                                              C.byref(blank)) == 0
+                ca.sync()
+                got.append(do.download(np.complex64, n >> 5).astype(np.complex128))
+                blanked.append(q.ProcessBlanker(xs[a0:a0 + n].astype(np.complex128)))
+                k0 += npk
+    finally:
+        b.close(); nb.close()
+        for d in bufs:
+            d.free()
+    blanked = np.concatenate(blanked)
+    zeros = int((blanked == 0).sum()) - delay1                # (the delay line starts with delay1 zeros of its own)
+    print("DCBLK %s D1 %d: %d of %d samples blanked" % (src, delay1, zeros, tot))
+    assert 0 < zeros < tot                                    # the case blanks, and not everything
+    assert_parity(np.concatenate(got), D.dc_reference(FM, freq, fs, blanked),
+                  "blanked %s D1 %d %s" % (src, delay1, "run-time" if dyn else "compiled"))
+
+
 # ------------------------------------------------------------------------------------------------ C: NCO edges
 NCO_RATE = 2e6
 NCO_FREQS = [("zero", 0.0), ("+rate/2", NCO_RATE / 2), ("-rate/2", -NCO_RATE / 2), ("rate/2 - 1 Hz", NCO_RATE / 2 - 1.0),
