@@ -74,6 +74,10 @@ struct csdr_demod_batch {
     long raw_cap = 0;
     unsigned *d_mask = nullptr; long mask_cap = 0;    // the blanker's mask of process_packets (fused form): [channels][mask_cap] words
     DcBlank blank{};
+    // the last blanked call, for the display behind it (csdr__demod_batch_last_blank): `blank` still describes what its
+    // mask pass left.  Dropped by every other process call, a commit and a rate change.
+    BlankCall last_blank{BLANK_CALL_NONE, nullptr, 0, 0};
+    bool last_two_pass = false;                       // ... and that call ran the two-pass form (CSDR_BLANK_FUSED=0): no mask
     ~csdr_demod_batch()
     {
         if (d_blank) (void)hipFree(d_blank);
@@ -113,7 +117,20 @@ static int batch_plumbing(csdr_demod_batch *b, bool ranked, PlanGroup *extra = n
     }
     return extra ? extra->plumbing(pr_lo) : CSDR_OK;
 }
-// pipelined mode: `stream` waits for what the previous call left in flight (PlanGroup::late_join), in every group
+// the record of the last blanked call goes with whatever changes what `blank` describes, or runs the chain on other input
+static void batch_forget_blank(csdr_demod_batch *b)
+{
+    b->last_blank = BlankCall{BLANK_CALL_NONE, nullptr, 0, 0};
+    b->last_two_pass = false;
+}
+// pipelined mode: `stream` waits for what the previous call left in flight (PlanGroup::late_join), in every group.
+// (The display behind a blanked call -- csdr_fft_batch_put_display_stream_blanked / _packets_blanked -- needs no join of
+// its own, in either mode: it only READS, on the caller's stream, the mask, the blanker's state and history half and the
+// input that the call's mask pass -- issued on that same stream before it -- wrote or read; the down-converters that
+// read the same buffers on the batch's streams do not write them.  The NEXT blanked call's mask pass, which overwrites
+// mask and history half, is issued on the caller's stream too, hence behind the display's reads -- and, by the join
+// below, behind the down-converters'.  The caller refills the input only behind that next call, as the pipelined
+// contract says.)
 static int batch_late_join(csdr_demod_batch *b, void *stream)
 {
     for (auto &g : b->groups) { const int rc = g->late_join((hipStream_t)stream); if (rc) return rc; }
@@ -244,6 +261,7 @@ int csdr_demod_batch_set_input_rate(csdr_demod_batch *b, double rate)
 {
     if (!b) return fail(CSDR_EINVAL, "bad handle");
     if (!(rate > 0.0) || !std::isfinite(rate)) return fail(CSDR_EINVAL, "input rate %g", rate);     // before anything records it
+    batch_forget_blank(b);
     if (b->groups.empty() || (rate == b->in_rate && !b->rate_change_failed)) { b->in_rate = rate; return CSDR_OK; }
     if (!device_ok(b->device)) return CSDR_EHIP;
     CSDR_HIP(hipDeviceSynchronize());                  // control plane: nothing of this batch in flight from here on
@@ -390,6 +408,7 @@ int csdr_demod_batch_set_input_rows(csdr_demod_batch *b, const int *input_row)
 int csdr_demod_batch_commit(csdr_demod_batch *b)
 {
     if (!b) return fail(CSDR_EINVAL, "bad handle");
+    batch_forget_blank(b);
     if (!device_ok(b->device)) return CSDR_EHIP;
     if (!b->groups.empty()) return fail(CSDR_ESTATE, "already committed");
     std::map<long long, std::vector<int>> by_bw;
@@ -603,6 +622,7 @@ static int demod_batch_run(csdr_demod_batch *b, const float *d_in, long long in_
                            const void *d_packets = nullptr, int pkt_len = 0, const DcBlank *blank = nullptr)
 {
     if (!b || (!d_in && !d_packets) || !d_out) return fail(CSDR_EINVAL, "bad argument");
+    batch_forget_blank(b);                               // (the blanked entry points record their call behind this)
     if (b->groups.empty()) return fail(CSDR_ESTATE, "commit first");
     if (b->rate_change_failed)
         return fail(CSDR_ESTATE, "a csdr_demod_batch_set_input_rate failed half way (rows of one group decimate differently): call it again");
@@ -664,6 +684,7 @@ int csdr_demod_batch_process_packets(csdr_demod_batch *b, const void *d_packets,
     if (!nb)        // the down-converter decodes the datagrams in its own loads: no unpacked copy, no extra pass
         return demod_batch_run(b, nullptr, 0, (int)n, d_out, out_stride, stream, false, d_packets, pkt_len);
     { const int rcs = batch_blanker_fits(b, nb); if (rcs) return rcs; }
+    batch_forget_blank(b);                               // the mask and the blanker's halves are about to change
     // With the blanker.  The internal buffers below (mask / blanked samples) are single-buffered, and the blanker's
     // history halves alternate per call: in pipelined mode the down-converters of the PREVIOUS call (on the batch's own
     // streams) may still be reading them, and the caller's stream -- on which the blanker of this call runs -- has not
@@ -679,7 +700,9 @@ int csdr_demod_batch_process_packets(csdr_demod_batch *b, const void *d_packets,
         int rc = csdr__noiseproc_batch_mask(nb, nullptr, 0, d_packets, npackets, pkt_len, (int)n, b->d_mask, b->mask_cap,
                                             &b->blank.state, &b->blank.hist, stream);
         if (rc < 0) return rc;
-        return demod_batch_run(b, nullptr, 0, (int)n, d_out, out_stride, stream, false, d_packets, pkt_len, &b->blank);
+        rc = demod_batch_run(b, nullptr, 0, (int)n, d_out, out_stride, stream, false, d_packets, pkt_len, &b->blank);
+        if (rc == CSDR_OK) b->last_blank = BlankCall{BLANK_CALL_PACKETS, d_packets, pkt_len, (int)n};
+        return rc;
     }
     // two passes: the blanker decodes the datagrams in ITS loads and leaves blanked fp32 samples for the chain
     if (n > b->raw_cap) {
@@ -691,7 +714,9 @@ int csdr_demod_batch_process_packets(csdr_demod_batch *b, const void *d_packets,
     }
     int rc = csdr__noiseproc_batch_process_packets(nb, d_packets, npackets, pkt_len, b->d_blank, b->raw_cap, stream);
     if (rc < 0) return rc;
-    return demod_batch_run(b, b->d_blank, b->raw_cap, (int)n, d_out, out_stride, stream, false);
+    rc = demod_batch_run(b, b->d_blank, b->raw_cap, (int)n, d_out, out_stride, stream, false);
+    b->last_two_pass = rc == CSDR_OK;
+    return rc;
 }
 /* The strict / pipelined pass on fp32 rows with CNoiseProc's blanker in front (what CSdrInterface::ProcessIQData runs in
  * place before the chain, sdrinterface.cpp:884), FUSED like the datagram form: the blanker kernel leaves one bit per sample,
@@ -710,13 +735,31 @@ int csdr_demod_batch_process_blanked(csdr_demod_batch *b, const float *d_in, lon
                 return fail(CSDR_ESTATE, "process_blanked: every receiver reads its own row (csdr_demod_batch_set_input_rows is off)");
     { const int rcs = batch_blanker_fits(b, nb); if (rcs) return rcs; }
     const long n = n_per_channel;
+    batch_forget_blank(b);
     // (the single-buffered mask, as in process_packets)
     if (b->pipelined) { const int rcj = batch_late_join(b, stream); if (rcj) return rcj; }
     { const int rcm = batch_mask_rows(b, n); if (rcm) return rcm; }
     int rc = csdr__noiseproc_batch_mask(nb, d_in, in_stride, nullptr, 0, 0, (int)n, b->d_mask, b->mask_cap,
                                         &b->blank.state, &b->blank.hist, stream);
     if (rc < 0) return rc;
-    return demod_batch_run(b, d_in, in_stride, (int)n, d_out, out_stride, stream, false, nullptr, 0, &b->blank);
+    rc = demod_batch_run(b, d_in, in_stride, (int)n, d_out, out_stride, stream, false, nullptr, 0, &b->blank);
+    if (rc == CSDR_OK) b->last_blank = BlankCall{BLANK_CALL_ROWS, d_in, in_stride, (int)n};
+    return rc;
+}
+/* internal (capi_fft.hip: the display behind a blanked chain call): what the LAST blanked call's mask pass left -- mask,
+ * blanker state and the history half it read -- with the record of that call's input, the batch's width and device.
+ * CSDR_ESTATE when the last process call was not a fused blanked one. */
+int csdr__demod_batch_last_blank(csdr_demod_batch *b, DcBlank *blank, BlankCall *call, int *channels, int *device)
+{
+    if (!b || !blank || !call) return fail(CSDR_EINVAL, "bad argument");
+    if (b->last_two_pass)
+        return fail(CSDR_ESTATE, "the chain's last call ran the two-pass blanker (CSDR_BLANK_FUSED=0): it left no mask");
+    if (b->last_blank.form == BLANK_CALL_NONE)
+        return fail(CSDR_ESTATE, "the chain's last call was not a blanked one (csdr_demod_batch_process_blanked, or _process_packets with a blanker)");
+    *blank = b->blank; *call = b->last_blank;
+    if (channels) *channels = b->channels;
+    if (device) *device = b->device;
+    return CSDR_OK;
 }
 /* internal (diagnostics: tools/experiments/r6_repro_mode3.py): how fast each plan group's own buffers stream -- a
  * device-to-device copy of the filter-output rows into the spare rows, timed with events, per group in the batch's launch

@@ -3,6 +3,8 @@
 #include "spectrum_kernels.h"
 #include "display_stream_kernels.h"
 #include "display_plan.hpp"
+#include "downconv_kernels.h"
+#include "capi_internal.hpp"
 #include "host_math.hpp"
 #include <cstdint>
 #include <cstring>
@@ -171,11 +173,13 @@ int csdr_fft_batch_reset(csdr_fft_batch *f)
 int csdr_fft_batch_size(csdr_fft_batch *f) { return f ? f->size : fail(CSDR_EINVAL, "bad handle"); }
 
 // where the frames of a display-stream launch come from (spectrum_stream_launch, 2048 ... 8192 points): frame f at
-// sample start + f step of the call, DC subtracted, from fp32 rows or from datagrams (pk)
+// sample start + f step of the call, DC subtracted, from fp32 rows or from datagrams (pk); blank: behind a blanked chain
+// call, through the blanked loaders
 struct FrameSrc {
     long long start, step;
     const double *dc;
     const unsigned char *pk; long pk_stride; int pkt_len;
+    const DcBlank *blank;
 };
 
 // PutInDisplayFFT of nframes frames of `size` samples per channel, back to back in each row (src == nullptr), or as src
@@ -220,6 +224,9 @@ static int fft_put_frames(csdr_fft_batch *f, const float *d_in, long long in_str
     a.frame_start = src ? src->start : 0; a.frame_step = src ? src->step : f->size;
     a.dc = src ? src->dc : nullptr;
     a.pk = src ? src->pk : nullptr; a.pk_stride = src ? src->pk_stride : 0;
+    const DcBlank *blank = src ? src->blank : nullptr;
+    a.nb_mask = blank ? blank->mask : nullptr; a.nb_mask_stride = blank ? blank->mask_stride : 0;
+    a.nb_state = blank ? (const NbChan *)blank->state : nullptr;
     const int l2 = log2_of(f->size);
     if (src) CSDR_HIP(spectrum_stream_launch(l2, a, src->pkt_len, (hipStream_t)stream));
     else if (l2 >= 11 && l2 <= 14) CSDR_HIP(spectrum_launch(l2, a, (hipStream_t)stream));
@@ -242,24 +249,37 @@ int csdr_fft_batch_put_display(csdr_fft_batch *f, const float *d_in, long long i
 // plain launch in place.  The rest is gathered, DC-corrected, into the staging rows first: the frame that begins in the
 // carried partial frame, and at the other sizes (16384, where the stream loaders spill, and the multi-launch sizes) every
 // used frame.  The partial frame at the end stays in d_carry.
+// blank: the call's samples as the blanker of the chain call that consumed them handed them over (StreamSrc in
+// display_stream_kernels.h).  The blanked loaders (2048 and 4096 points; at 8192 they spilled) read no history: the choice
+// here is that a frame whose delayed samples may reach in front of the call -- first sample below the largest
+// delay_n + 1, NB_MAX_WIDTH / 2 + 1 -- is gathered like the frame that begins in the carry (with step >= N >= 2048
+// that is at most the first two used frames of a call), instead of teaching the loaders the history branch.
 static int fft_put_stream(csdr_fft_batch *f, const float *d_in, long long in_stride, const WireIn &wire, long long n,
-                          const double *d_dc, void *stream)
+                          const double *d_dc, void *stream, const DcBlank *blank = nullptr)
 {
     if (n == 0) return 0;
     if (!device_ok(f->device)) return CSDR_EHIP;
     const int N = f->size, l2 = log2_of(N);
-    const bool loaders = l2 >= 11 && l2 <= 13;
+    // (CSDR_DISPLAY_BLANKED_LOADERS=0: every used frame of a blanked call through the gather -- the A/B of
+    // tools/bench_display_blanked.py; the words are the same)
+    static const bool blanked_loaders = !(getenv("CSDR_DISPLAY_BLANKED_LOADERS") && atoi(getenv("CSDR_DISPLAY_BLANKED_LOADERS")) == 0);
+    const bool loaders = blank ? blanked_loaders && spectrum_stream_blanked_ok(l2, wire.pk ? wire.pkt_len : 0) : l2 >= 11 && l2 <= 13;
+    const long long first_loaded = blank ? NB_MAX_WIDTH / 2 + 1 : 0;       // the loaders take frames from here on
     const DisplayPlan p = display_plan(f->ds, n, N);
     hipStream_t st = (hipStream_t)stream;
     StreamSrc a;
     a.in = d_in; a.in_stride = (long)in_stride; a.wire = wire; a.dc = d_dc;
     a.carry = f->d_carry; a.pos = f->ds.pos; a.carry_stride = N; a.channels = f->channels;
+    a.nb_mask = blank ? blank->mask : nullptr; a.nb_mask_stride = blank ? blank->mask_stride : 0;
+    a.nb_state = blank ? (const NbChan *)blank->state : nullptr; a.nb_hist = blank ? blank->hist : nullptr;
     long long start = p.start;
     int left = p.count;
     bool clear_over = true;
-    auto in_place = [&](int k) { return !wire.pk && !d_dc && start >= 0 && (k == 1 || p.step == N); };
-    if (left > 0 && !in_place(left) && (start < 0 || !loaders)) {
-        const int ng = loaders ? 1 : left;
+    auto in_place = [&](int k) { return !blank && !wire.pk && !d_dc && start >= 0 && (k == 1 || p.step == N); };
+    if (left > 0 && !in_place(left) && (start < first_loaded || !loaders)) {
+        int ng = left;
+        if (loaders)                                    // (unblanked: the one frame that begins in the carry)
+            for (ng = 1; ng < left && start + ng * p.step < first_loaded; ) ng++;
         const size_t need = (size_t)f->channels * ng * N * 2;
         if (need > f->stage_cap) {
             CSDR_HIP(hipStreamSynchronize(st));
@@ -277,7 +297,7 @@ static int fft_put_stream(csdr_fft_batch *f, const float *d_in, long long in_str
         int rc;
         if (in_place(left)) rc = fft_put_frames(f, d_in + 2 * start, in_stride, left, stream, nullptr, clear_over);
         else {
-            const FrameSrc src{start, p.step, d_dc, wire.pk, wire.chan_stride, wire.pkt_len};
+            const FrameSrc src{start, p.step, d_dc, wire.pk, wire.chan_stride, wire.pkt_len, blank};
             rc = fft_put_frames(f, d_in, in_stride, left, stream, &src, clear_over);
         }
         if (rc) return rc;
@@ -328,6 +348,47 @@ int csdr_fft_batch_put_display_packets(csdr_fft_batch *f, const void *d_packets,
     const int per = pkt_len == 1444 ? 240 : 256;
     return fft_put_stream(f, nullptr, 0, WireIn{(const unsigned char *)d_packets, (long)npackets * pkt_len, pkt_len, per},
                           (long long)npackets * per, d_dc, stream);
+}
+// the blanked pair: the chain `b` remembers its last blanked call (csdr__demod_batch_last_blank) -- the display reads the
+// same input through the mask, state and history half that call's mask pass left, so it must be THAT call's input
+static int fft_blank_of(csdr_fft_batch *f, csdr_demod_batch *b, int form, const void *src, long long stride, int n,
+                        DcBlank *blank)
+{
+    BlankCall call;
+    int channels = 0, device = -1;
+    const int rc = csdr__demod_batch_last_blank(b, blank, &call, &channels, &device);
+    if (rc) return rc;
+    if (channels != f->channels || device != f->device)
+        return fail(CSDR_EINVAL, "display of %d channels on device %d behind a chain of %d on device %d", f->channels,
+                    f->device, channels, device);
+    if (call.form != form)
+        return fail(CSDR_EINVAL, "the chain's last blanked call took %s", call.form == BLANK_CALL_PACKETS ? "datagrams" : "fp32 rows");
+    if (call.src != src || call.stride != stride || call.n != n)
+        return fail(CSDR_EINVAL, "not the input of the chain's last blanked call (buffer, %s or count differ)",
+                    form == BLANK_CALL_PACKETS ? "packet length" : "stride");
+    return CSDR_OK;
+}
+int csdr_fft_batch_put_display_stream_blanked(csdr_fft_batch *f, csdr_demod_batch *b, const float *d_in,
+                                              long long in_stride, int n, const double *d_dc, void *stream)
+{
+    if (!f || !b || !d_in || n < 0 || in_stride < n) return fail(CSDR_EINVAL, "bad argument");
+    if ((uintptr_t)d_in & 7) return fail(CSDR_EINVAL, "d_in must be 8-byte aligned");
+    DcBlank blank;
+    { const int rc = fft_blank_of(f, b, BLANK_CALL_ROWS, d_in, in_stride, n, &blank); if (rc) return rc; }
+    return fft_put_stream(f, d_in, in_stride, WireIn{nullptr, 0, 0, 0}, n, d_dc, stream, &blank);
+}
+int csdr_fft_batch_put_display_packets_blanked(csdr_fft_batch *f, csdr_demod_batch *b, const void *d_packets,
+                                               int npackets, int pkt_len, const double *d_dc, void *stream)
+{
+    if (!f || !b || !d_packets || npackets < 0) return fail(CSDR_EINVAL, "bad argument");
+    if (pkt_len != 1028 && pkt_len != 1444) return fail(CSDR_EINVAL, "packet length %d", pkt_len);
+    if ((long)npackets * pkt_len >= (1l << 31)) return fail(CSDR_EINVAL, "a channel's datagrams of one call must stay below 2 GiB");
+    if ((uintptr_t)d_packets & 3) return fail(CSDR_EINVAL, "datagram buffer must be 4-byte aligned");
+    const int per = pkt_len == 1444 ? 240 : 256;
+    DcBlank blank;
+    { const int rc = fft_blank_of(f, b, BLANK_CALL_PACKETS, d_packets, pkt_len, npackets * per, &blank); if (rc) return rc; }
+    return fft_put_stream(f, nullptr, 0, WireIn{(const unsigned char *)d_packets, (long)npackets * pkt_len, pkt_len, per},
+                          (long long)npackets * per, d_dc, stream, &blank);
 }
 /* copy of m_pFFTAveBuf of one channel (bels, display order), synchronises */
 int csdr_fft_batch_get_ave(csdr_fft_batch *f, int channel, float *out)

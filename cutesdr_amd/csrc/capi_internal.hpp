@@ -4,7 +4,17 @@
 #pragma once
 #include "../../include/cutesdr_mi.h"
 
-namespace csdr { struct DcBlank; }                      // downconv_kernels.h
+namespace csdr {
+struct DcBlank;                                         // downconv_kernels.h
+// the last blanked call of a chain batch (csdr__demod_batch_last_blank): which input it consumed
+enum { BLANK_CALL_NONE = 0, BLANK_CALL_ROWS = 1, BLANK_CALL_PACKETS = 2 };
+struct BlankCall {
+    int form;                                           // BLANK_CALL_*
+    const void *src;                                    // d_in / d_packets
+    long long stride;                                   // rows: in_stride; datagrams: pkt_len
+    int n;                                              // samples per channel
+};
+}
 
 extern "C" {
 /* capi_downconv.hip */
@@ -24,4 +34,5 @@ int csdr__noiseproc_batch_process_packets(csdr_noiseproc_batch *b, const void *d
                                           float *d_out, long long out_stride, void *stream);
 /* capi_demod_batch.hip */
 int csdr__demod_batch_wait_input_free(csdr_demod_batch *b, void *stream);
+int csdr__demod_batch_last_blank(csdr_demod_batch *b, csdr::DcBlank *blank, csdr::BlankCall *call, int *channels, int *device);
 }

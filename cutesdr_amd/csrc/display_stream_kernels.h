@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "wire_format.hpp"
+#include "frontend_kernels.h"
 
 namespace csdr {
 
@@ -9,6 +10,11 @@ namespace csdr {
 // datagrams of `wire` when wire.pk is set) minus the channel's DC offset (dc: optional [channels][2] doubles, the
 // arithmetic of unpack_kernel: (float)((double)v - dc)); sample s in [-pos, 0) is carry[ch][pos + s], the partial frame
 // the previous calls left (already corrected, as m_DataBuf is).
+// Behind a blanked chain call (nb_mask set: the mask, state and history half that call's mask pass left, DcBlank in
+// downconv_kernels.h) sample s >= 0, before the DC correction, is what the reference's in-place blanker hands over
+// (interface/sdrinterface.cpp:884) -- the down-converter's rule, downconv_kernels.h:44-51, indexed by row = channel:
+//     nb_state[ch].on ? (mask bit s set ? (0, 0) : raw[s - delay_n - 1]) : raw[s]     raw[j < 0] = nb_hist[ch][NB_HIST + j]
+// so a blanked sample becomes -dc (:891-894), and the carry holds blanked, corrected samples.
 struct StreamSrc {
     const float *in; long in_stride;    // [channels][in_stride] complex fp32; unused when wire.pk is set
     WireIn wire;
@@ -16,6 +22,9 @@ struct StreamSrc {
     const float *carry; int pos;        // [channels][carry_stride] complex fp32, the first pos samples valid
     long carry_stride;
     int channels;
+    const unsigned *nb_mask; long nb_mask_stride;   // [channels][stride] words, bit s & 31 of word s >> 5; nullptr: no blanker
+    const NbChan *nb_state;                         // [channels]: on, delay_n
+    const float *nb_hist;                           // [channels][NB_HIST] complex: the inputs before the call
 };
 
 // out[ch][k * N + i] = stream sample start + k * step + i, for k < count, i < N

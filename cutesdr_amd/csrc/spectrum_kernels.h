@@ -1,6 +1,7 @@
 // spectrum_kernels.h -- launch interface of the CFft kernels (internal).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "frontend_kernels.h"
 
 namespace csdr {
 
@@ -22,7 +23,13 @@ struct SpectrumArgs {
     long frame_start, frame_step;
     const double *dc;                   // optional [channels][2] (I, Q), subtracted as unpack_kernel does
     const unsigned char *pk; long pk_stride;   // datagrams [channels][pk_stride] bytes (wire_format.hpp), or nullptr: `in`
+    // behind a blanked chain call (StreamSrc in display_stream_kernels.h): the stream sample is the one delay_n + 1 behind,
+    // zero under the mask.  The blanked loaders read no history: frame_start >= NB_MAX_WIDTH / 2 + 1 with them.
+    const unsigned *nb_mask; long nb_mask_stride;   // [channels][stride] words; nullptr: no blanker
+    const NbChan *nb_state;                         // [channels]: on, delay_n
 };
+// which sizes have a blanked form of the stream loaders (pkt_len 0: fp32 rows); the others gather their frames
+bool spectrum_stream_blanked_ok(int log2n, int pkt_len);
 hipError_t spectrum_launch(int log2n, const SpectrumArgs &a, hipStream_t stream);
 // 2048 ... 8192 points with the frame load of the display stream: fp32 rows (a.pk == nullptr) or datagrams of
 // pkt_len 1028 / 1444 decoded in the load, frames at frame_start + f frame_step, DC subtracted

@@ -78,6 +78,37 @@ struct WireLoad {
         }
     }
 };
+// The stream frame loaders behind a blanked chain call (SpectrumArgs::nb_mask; the rule is StreamSrc's,
+// display_stream_kernels.h): fetch issues the inner loader's load at s - D1 (D1 = delay_n + 1, 0 when the row's blanker is
+// off) plus the mask word of s, decode yields dc.sub(0, 0) under the mask and the inner decode otherwise.  The inner
+// loader's start is moved back by D1 once: its fetch is the unblanked one.  No history branch here -- a frame whose
+// delayed samples reach in front of the call (first sample < NB_MAX_WIDTH / 2 + 1, the largest D1) goes through the
+// gather instead (capi_fft.hip: fft_put_stream), like the frame that begins in the carry.
+// The mask word's shift (s & 31) travels with the word: the wide kernels fetch samples a multiple of 32 apart, so a
+// thread's shifts of one frame fold into one register.  opaque() once more behind the select, so that the transform sees
+// a loaded sample whichever side it came from (the words are those of the fp32-row forms).
+template <class Inner>
+struct BlankedLoad {
+    struct Raw { typename Inner::Raw r; unsigned m, sh; };
+    Inner in; const unsigned *mrow; long start, step; v2f zero;
+    __device__ __forceinline__ BlankedLoad(const SpectrumArgs &a, int ch)
+        : in(a, ch), mrow(a.nb_mask + (long)ch * a.nb_mask_stride), start(a.frame_start), step(a.frame_step),
+          zero(in.dc.sub(0.f, 0.f))
+    {
+        const NbChan *nb = a.nb_state + ch;
+        in.start -= nb->on ? nb->delay_n + 1 : 0;         // (off: the mask pass left the row all zero, as the down-converter relies on)
+    }
+    template <int N> __device__ __forceinline__ Raw fetch(int f, int i) const
+    {
+        const unsigned s = (unsigned)(start + (long)f * step) + (unsigned)i;      // < 2^31, as in WireLoad
+        return Raw{in.template fetch<N>(f, i), mrow[s >> 5], s & 31u};
+    }
+    __device__ __forceinline__ v2f decode(Raw r) const
+    {
+        const v2f v = in.decode(r.r);
+        return opaque(((r.m >> r.sh) & 1u) ? zero : v);
+    }
+};
 
 
 #ifndef CSDR_SPEC_WAVES
@@ -650,15 +681,20 @@ static hipError_t spec_launch_one(const SpectrumArgs &a, hipStream_t s)
         if (e != hipSuccess) return e;
     }
     static const bool wide = !plain || !(getenv("CSDR_SPEC16") && atoi(getenv("CSDR_SPEC16")) == 0);
-    if (LOG2N == 12 && wide)
-        hipLaunchKernelGGL(spectrum16_kernel<Ld>, dim3(a.channels * a.nparts), dim3(256), SPEC16_LDS, s, a);
-    else if (LOG2N == 11 && wide)
-        hipLaunchKernelGGL(spectrum8_kernel<Ld>, dim3(a.channels * a.nparts), dim3(128), SPEC8_LDS, s, a);
-    else if (LOG2N == 13 && wide) {
-        e = CSDR_MAX_LDS_ONCE((&spectrum32_kernel<Ld>), SPEC32_LDS);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(spectrum32_kernel<Ld>, dim3(a.channels * a.nparts), dim3(512), SPEC32_LDS, s, a);
-    } else if constexpr (plain)
+    // (the size tests are compile-time: a loader is instantiated in the kernel of ITS sizes only -- the blanked loaders
+    // have no 8192-point form)
+    if constexpr (LOG2N == 12) {
+        if (wide) hipLaunchKernelGGL(spectrum16_kernel<Ld>, dim3(a.channels * a.nparts), dim3(256), SPEC16_LDS, s, a);
+    } else if constexpr (LOG2N == 11) {
+        if (wide) hipLaunchKernelGGL(spectrum8_kernel<Ld>, dim3(a.channels * a.nparts), dim3(128), SPEC8_LDS, s, a);
+    } else if constexpr (LOG2N == 13) {
+        if (wide) {
+            e = CSDR_MAX_LDS_ONCE((&spectrum32_kernel<Ld>), SPEC32_LDS);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(spectrum32_kernel<Ld>, dim3(a.channels * a.nparts), dim3(512), SPEC32_LDS, s, a);
+        }
+    }
+    if constexpr (plain) if (!wide || LOG2N == 14)
         hipLaunchKernelGGL(spectrum_kernel<LOG2N>, dim3(a.channels * a.nparts), dim3(Cfg::T), Cfg::LDS_BYTES, s, a);
     if (a.nparts > 1) {
         hipLaunchKernelGGL(spectrum_alpha_kernel, dim3(a.channels), dim3(64), 0, s, a);
@@ -697,8 +733,30 @@ static hipError_t spectrum_stream_one(int log2n, const SpectrumArgs &a, hipStrea
     default: return hipErrorInvalidValue;
     }
 }
+// The blanked loaders exist at 2048 and 4096 points.  At 8192 points (spectrum32_kernel, 512 threads: at most 256
+// registers) the mask word per prefetched sample spilled -- 72 bytes of scratch per lane on fp32 rows, 16 on 16-bit and
+// 124 on 24-bit datagrams -- so that size gathers its frames behind a blanked call, as 16384 points does for every stream.
+bool spectrum_stream_blanked_ok(int log2n, int pkt_len)
+{
+    return (log2n == 11 || log2n == 12) && (pkt_len == 0 || pkt_len == 1028 || pkt_len == 1444);
+}
+template <class Ld>
+static hipError_t spectrum_blanked_one(int log2n, const SpectrumArgs &a, hipStream_t stream)
+{
+    switch (log2n) {
+    case 11: return spec_launch_one<11, Ld>(a, stream);
+    case 12: return spec_launch_one<12, Ld>(a, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
 hipError_t spectrum_stream_launch(int log2n, const SpectrumArgs &a, int pkt_len, hipStream_t stream)
 {
+    if (a.nb_mask) {
+        if (!spectrum_stream_blanked_ok(log2n, a.pk ? pkt_len : 0)) return hipErrorInvalidValue;
+        if (!a.pk) return spectrum_blanked_one<BlankedLoad<RowDcLoad>>(log2n, a, stream);
+        if (pkt_len == 1444) return spectrum_blanked_one<BlankedLoad<WireLoad<1444>>>(log2n, a, stream);
+        return spectrum_blanked_one<BlankedLoad<WireLoad<1028>>>(log2n, a, stream);
+    }
     if (!a.pk) return spectrum_stream_one<RowDcLoad>(log2n, a, stream);
     if (pkt_len == 1444) return spectrum_stream_one<WireLoad<1444>>(log2n, a, stream);
     if (pkt_len == 1028) return spectrum_stream_one<WireLoad<1028>>(log2n, a, stream);

@@ -1051,6 +1051,21 @@ class FftBatch(_Obj):
                                                               C.c_void_p(d_dc or 0), C.c_void_p(stream) if stream else None),
                      "csdr_fft_batch_put_display_packets")
 
+    # ---- behind a blanked chain call: the samples as the chain's blanker handed them over (sdrinterface.cpp:884), from
+    # the mask that call left.  The input buffer is the one the chain call consumed and must still be alive: these take
+    # device pointers only (demod: the DemodBatch of that call).
+    def put_display_stream_blanked_ptr(self, demod, d_in, in_stride, n, d_dc=None, stream=None):
+        """after demod.process_blanked-style csdr_demod_batch_process_blanked on (d_in, in_stride, n); returns the frames used"""
+        return check(lib().csdr_fft_batch_put_display_stream_blanked(self.h, demod.h, C.c_void_p(d_in), in_stride, n,
+                                                                     C.c_void_p(d_dc or 0), C.c_void_p(stream) if stream else None),
+                     "csdr_fft_batch_put_display_stream_blanked")
+
+    def put_display_packets_blanked_ptr(self, demod, d_packets, npackets, pkt_len, d_dc=None, stream=None):
+        """after csdr_demod_batch_process_packets with a blanker on (d_packets, npackets, pkt_len); returns the frames used"""
+        return check(lib().csdr_fft_batch_put_display_packets_blanked(self.h, demod.h, C.c_void_p(d_packets), npackets, pkt_len,
+                                                                      C.c_void_p(d_dc or 0), C.c_void_p(stream) if stream else None),
+                     "csdr_fft_batch_put_display_packets_blanked")
+
     def put_display_packets(self, raw, pkt_len, dc=None):
         """raw uint8 [channels, npackets, pkt_len] (host); dc: optional [channels, 2] offsets -> frames used"""
         raw = np.ascontiguousarray(raw, dtype=np.uint8)

@@ -491,8 +491,14 @@ int csdr_fft_batch_get_waterfall_all(csdr_fft_batch *f, int max_w, double max_db
  * whether it reaches PutInDisplayFFT.  The frame position, skip value, skip counter and gate are ONE set per object:
  * every row gets the same sample count per call.  Used frames go through exactly the averaging, log and overload code
  * of csdr_fft_batch_put_display, so get_ave / get_total_count / get_screen_all / get_waterfall_all work unchanged.
- * Out of scope: a blanked display (run csdr_noiseproc_batch_process into fp32 rows, then put_display_stream); the
- * SPUR_CAL_MAXSAMPLES bookkeeping of NcoSpurCalibrate (the host keeps m_NcoSpurCalCount); shard forms. */
+ * With the blanker on, the reference's display sees the blanked, delayed samples (:884 runs in place first):
+ * csdr_fft_batch_put_display_stream_blanked / _packets_blanked below give that picture behind a blanked chain call,
+ * from the mask the call left -- no second blanker pass.
+ * Out of scope: the SPUR_CAL_MAXSAMPLES bookkeeping of NcoSpurCalibrate (the host keeps m_NcoSpurCalCount); shard forms
+ * (of the plain and of the blanked pair); spur calibration on blanked samples -- the reference calibrates behind the
+ * blanker (:886), csdr_ingest_spurcal* see the unblanked input: while NcoSpurCalibrate is active (the first
+ * SPUR_CAL_MAXSAMPLES samples after a start) a host either accepts that estimate -- it differs by the blanked samples'
+ * share of the running mean -- or runs csdr_noiseproc_batch_process into rows of its own and calibrates on those. */
 /* SetMaxDisplayRate (sdrinterface.h:112-114): skip value = (int)(sample_rate / (size * max_display_rate)), counter 0.
  * gated != 0 turns on the m_ScreenUpateFinished handshake: after a used frame, none is used until
  * csdr_fft_batch_screen_update_done.  Until this is called the skip value is 0 (every frame) and the gate is off.
@@ -516,6 +522,32 @@ int csdr_fft_batch_put_display_stream(csdr_fft_batch *f, const float *d_in, long
  * the rules of csdr_demod_batch_process_packets (pkt_len 1028 or 1444, 4-byte aligned, below 2 GiB per channel) */
 int csdr_fft_batch_put_display_packets(csdr_fft_batch *f, const void *d_packets, int npackets, int pkt_len,
                                        const double *d_dc, void *stream);
+/* The display stream of the samples the LAST blanked chain call of `b` consumed, as its blanker handed them over
+ * (:884): stream sample s of row c, before the DC correction, is
+ *     blanker of c on ? (mask bit s of the call set ? (0, 0) : input[s - delay_n - 1]) : input[s]
+ * with input[j < 0] the samples of the calls before -- the rule the blanked down-converter applies in its own loads; a
+ * blanked sample becomes -dc (:891-894) and the carried partial frame holds blanked samples, as m_DataBuf does.  Nothing
+ * is blanked twice: the call reads the mask, the blanker's state and the history the chain call left on the device.
+ * Return value, frame logic, averaging and readers are those of the unblanked pair; a receiver whose blanker is off gets
+ * exactly its samples.  The contract:
+ *  - call it after csdr_demod_batch_process_blanked (-> _put_display_stream_blanked) or csdr_demod_batch_process_packets
+ *    with a blanker (-> _put_display_packets_blanked), with the same `stream`, the same input buffer and the same count
+ *    (and stride / packet length), and BEFORE the next call on `b`: the mask is single-buffered and the blanker's
+ *    history halves alternate;
+ *  - f and b are on the same device and have the same number of channels; every receiver reads its own row (what
+ *    process_blanked demands);
+ *  - the blanker object of that call still exists and has not been set up in between;
+ *  - strict and pipelined mode both work: the display only reads, on the caller's stream, behind the call's mask pass,
+ *    and the next call's mask pass is ordered behind it on that stream.
+ * CSDR_ESTATE when the last process call of `b` was not such a call (none yet, an unblanked one, or a commit or a rate
+ * change since; with CSDR_BLANK_FUSED=0 the chain runs the two-pass blanker and leaves no mask: CSDR_ESTATE too);
+ * CSDR_EINVAL when buffer, form, count, channels or device differ.  A refused call changes nothing.
+ * The frames are read where they lie at 2048 and 4096 points (the first one or two of a call, whose delayed samples
+ * may lie in front of it, and every other size through the gather). */
+int csdr_fft_batch_put_display_stream_blanked(csdr_fft_batch *f, csdr_demod_batch *b, const float *d_in,
+                                              long long in_stride, int n, const double *d_dc, void *stream);
+int csdr_fft_batch_put_display_packets_blanked(csdr_fft_batch *f, csdr_demod_batch *b, const void *d_packets,
+                                               int npackets, int pkt_len, const double *d_dc, void *stream);
 
 /* ----------------------------------------------------------------------------------------
  * CFractResampler (dsp/fractresampler.h:17-33)
