@@ -11,3 +11,4 @@ from .host import SoundSinkBatch  # noqa: F401
 from .host import TestGenBatch  # noqa: F401
 
 from .host import ScopeBatch  # noqa: F401
+from .host import PlotterBatch  # noqa: F401

@@ -514,6 +514,15 @@ int csdr_fft_batch_get_waterfall_all(csdr_fft_batch *f, int max_w, double max_db
     return CSDR_OK;
 }
 
+// what csdr_plotter_batch_draw reads: nothing of the cached translate table, and nothing here is changed
+int csdr__fft_batch_view(csdr_fft_batch *f, FftView *v)
+{
+    if (!f || !v) return fail(CSDR_EINVAL, "bad argument");
+    v->device = f->device; v->channels = f->channels; v->size = f->size; v->invert = f->invert; v->fs = f->fs;
+    v->d_ave = f->d_ave; v->d_over = f->d_over;
+    return CSDR_OK;
+}
+
 }  // extern "C"
 
 /* ---------------- single-channel host form: CFft drop-in ---------------- */

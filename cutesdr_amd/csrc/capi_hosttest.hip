@@ -8,6 +8,7 @@
 #include "display_plan.hpp"
 #include "testgen_host.hpp"
 #include "scope_host.hpp"
+#include "plotter_host.hpp"
 #include "fastfir_kernels.h"
 #include "fft_core.hpp"
 #include <cstring>
@@ -431,5 +432,48 @@ void csdr__host_scope_fft_map(int span, int cpx, double fs, int w, int h, const 
     for (int x = 0; x < w; x++) out[x] = sc::fft_pixel(m, w, x, [&](int i) { return bels[i]; });
     map4[0] = m.bin_min; map4[1] = m.bin_max; map4[2] = m.bins; map4[3] = m.h;
 }
+
+// ---- the batch plotter's host-side pieces (plotter_host.hpp), the same functions the draw kernel evaluates
+// one GetScreenIntegerFFTData of draw() as the kernel computes it: per pixel the largest bel of its run (the smallest
+// when max_db < min_db), then the level.
+// ave [n] bels in display order -> out [w]; map4 = {m_BinMin, m_BinMax, the "more bins than pixels" branch, lanes per pixel}
+void csdr__host_plotter_map(int n, int invert, double fs, int span, int w, int h, int max_db, int min_db, const float *ave,
+                            int *out, int *map4)
+{
+    const pl::Map m = pl::make_map(n, fs, span, w);
+    const double gain = pl::db_gain(max_db, min_db), off = pl::db_off(max_db);
+    for (int x = 0; x < w; x++) {
+        int lo, hi;
+        pl::pixel_bins(m, n, invert, w, x, &lo, &hi);
+        const int smallest = pl::run_keeps_smallest(max_db, min_db);
+        float top = pl::run_start(smallest);
+        for (int i = lo; i <= hi; i++) top = pl::run_keep(top, ave[i], smallest);
+        out[x] = pl::level(h, gain, off, top);
+    }
+    if (map4) { map4[0] = m.bin_min; map4[1] = m.bin_max; map4[2] = m.bins; map4[3] = pl::group_lanes(m, w); }
+}
+// a sequence of slot calls on a new view: calls [ncalls][3] = {what, a, b}, what: 0 resizeEvent(a, b), 1
+// SetPercent2DScreen(a), 2 SetSpanFreq(a), 3 SetMaxdB(a), 4 SetdBStepSize(a), 5 UpdateOverlay, 6 one draw's scroll ->
+// out8 = {w, h2d, wf_h, m_MindB, m_MaxdB, m_Span, ring head, lines drawn}
+void csdr__host_plotter_view(const int *calls, int ncalls, int *out8)
+{
+    pl::View k;
+    for (int c = 0; c < ncalls; c++) {
+        const int a = calls[3 * c + 1], b = calls[3 * c + 2];
+        switch (calls[3 * c]) {
+        case 0: k.resize(a, b); break;
+        case 1: k.set_percent(a); break;
+        case 2: k.span = a; break;
+        case 3: k.max_db = a; break;
+        case 4: k.step = a; break;
+        case 5: k.update_overlay(); break;
+        default: k.scroll(); break;
+        }
+    }
+    out8[0] = k.w; out8[1] = k.h2d; out8[2] = k.wf_h; out8[3] = k.min_db; out8[4] = k.max_db; out8[5] = k.span;
+    out8[6] = k.head; out8[7] = k.filled;
+}
+// the pen of one draw: state2 = {m_ADOverLoad, m_ADOverloadOneShotCounter}, updated; returns 1 for red
+int csdr__host_plotter_pen(int *state2, int fft_overload) { return pl::pen_step(&state2[0], &state2[1], fft_overload); }
 
 }  // extern "C"

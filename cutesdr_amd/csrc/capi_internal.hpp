@@ -14,6 +14,13 @@ struct BlankCall {
     long long stride;                                   // rows: in_stride; datagrams: pkt_len
     int n;                                              // samples per channel
 };
+// what a plotter batch reads of a spectrum batch at a draw (csdr__fft_batch_view)
+struct FftView {
+    int device, channels, size, invert;                 // as they are at the call
+    double fs;
+    const float *d_ave;                                 // [channels][size] bels, display order
+    const int *d_over;                                  // [channels] overload words of the last put
+};
 }
 
 extern "C" {
@@ -32,6 +39,8 @@ int csdr__noiseproc_batch_mask(csdr_noiseproc_batch *b, const float *d_in, long 
 int csdr__noiseproc_batch_shape(csdr_noiseproc_batch *b, int *channels, int *device);
 int csdr__noiseproc_batch_process_packets(csdr_noiseproc_batch *b, const void *d_packets, int npackets, int pkt_len,
                                           float *d_out, long long out_stride, void *stream);
+/* capi_fft.hip */
+int csdr__fft_batch_view(csdr_fft_batch *f, csdr::FftView *v);
 /* capi_demod_batch.hip */
 int csdr__demod_batch_wait_input_free(csdr_demod_batch *b, void *stream);
 int csdr__demod_batch_last_blank(csdr_demod_batch *b, csdr::DcBlank *blank, csdr::BlankCall *call, int *channels, int *device);

@@ -1433,3 +1433,87 @@ class ScopeBatch(_Obj):
         check(lib().csdr_scope_batch_get_fft_screens_all(
             self.h, C.c_void_p(out.data_ptr()), out.stride(1), C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)),
             "csdr_scope_batch_get_fft_screens_all")
+
+
+class PlotterBatch(_Obj):
+    """V CPlotter display states (gui/plotter.cpp:100-114, :374-389, :408-480; gui/plotter.h:32-44) over the rows of an
+    FftBatch: per view its own size, span, dB range and 2D/waterfall split; one launch per draw updates every running
+    view and the waterfall images stay on the device.  Setters as the reference's slots; view < 0: every view."""
+    _destroy = "csdr_plotter_batch_destroy"
+
+    def __init__(self, views, device=0):
+        self.views, self.device = int(views), device
+        self.h = check_ptr(lib().csdr_plotter_batch_create(device, self.views), "csdr_plotter_batch_create")
+
+    def set_source(self, fft_row, view=-1):
+        """the row of the FftBatch a view plots (default: row = view)"""
+        check(lib().csdr_plotter_batch_set_source(self.h, view, fft_row), "csdr_plotter_batch_set_source")
+
+    def resizeEvent(self, w, h, view=-1):
+        check(lib().csdr_plotter_batch_resize(self.h, view, w, h), "csdr_plotter_batch_resize")
+
+    def SetPercent2DScreen(self, percent, view=-1):
+        check(lib().csdr_plotter_batch_set_percent_2d(self.h, view, percent), "csdr_plotter_batch_set_percent_2d")
+
+    def SetSpanFreq(self, span, view=-1):
+        check(lib().csdr_plotter_batch_set_span(self.h, view, span), "csdr_plotter_batch_set_span")
+
+    def SetMaxdB(self, max_db, view=-1):
+        check(lib().csdr_plotter_batch_set_max_db(self.h, view, max_db), "csdr_plotter_batch_set_max_db")
+
+    def SetdBStepSize(self, step, view=-1):
+        check(lib().csdr_plotter_batch_set_db_step(self.h, view, step), "csdr_plotter_batch_set_db_step")
+
+    def UpdateOverlay(self, view=-1):
+        check(lib().csdr_plotter_batch_update_overlay(self.h, view), "csdr_plotter_batch_update_overlay")
+
+    def SetADOverload(self, on, view=-1):
+        check(lib().csdr_plotter_batch_set_ad_overload(self.h, view, 1 if on else 0), "csdr_plotter_batch_set_ad_overload")
+
+    def SetRunningState(self, running, view=-1):
+        check(lib().csdr_plotter_batch_set_running(self.h, view, 1 if running else 0), "csdr_plotter_batch_set_running")
+
+    def draw(self, fft, stream=None):
+        """CPlotter::draw of every running view from `fft` (an FftBatch), asynchronous on stream; returns the number of
+        running views"""
+        return check(lib().csdr_plotter_batch_draw(self.h, fft.h, C.c_void_p(stream) if stream else None),
+                     "csdr_plotter_batch_draw")
+
+    def geometry(self, view):
+        """(w, 2D height, waterfall height, m_MindB)"""
+        g = [C.c_int() for _ in range(4)]
+        check(lib().csdr_plotter_batch_get_geometry(self.h, view, *[C.cast(C.byref(x), C.c_void_p) for x in g]),
+              "csdr_plotter_batch_get_geometry")
+        return tuple(x.value for x in g)
+
+    def trace(self, view):
+        """(the last draw's levels int32 [w], pen red?)"""
+        y, red = np.zeros(max(self.geometry(view)[0], 1), dtype=np.int32), C.c_int()
+        w = check(lib().csdr_plotter_batch_get_trace(self.h, view, _vp(y), C.cast(C.byref(red), C.c_void_p)),
+                  "csdr_plotter_batch_get_trace")
+        return y[:w], bool(red.value)
+
+    def waterfall(self, view):
+        """the image, uint32 0xFFRRGGBB [waterfall height, w], newest line first"""
+        w, _, wf_h, _ = self.geometry(view)
+        out = np.zeros((wf_h, w), dtype=np.uint32)
+        check(lib().csdr_plotter_batch_get_waterfall(self.h, view, _vp(out) if out.size else None),
+              "csdr_plotter_batch_get_waterfall")
+        return out
+
+    def traces_all_ptr(self, d_y, stride, d_pen=None, stream=None):
+        """every view's trace into device int32 [views][stride] and its pen into device int32 [views]; asynchronous"""
+        check(lib().csdr_plotter_batch_get_traces_all(self.h, C.c_void_p(d_y), stride, C.c_void_p(d_pen) if d_pen else None,
+                                                      C.c_void_p(stream) if stream else None),
+              "csdr_plotter_batch_get_traces_all")
+
+    def lines_all_ptr(self, d_rgb, stride, stream=None):
+        """every view's newest waterfall line into device uint32 [views][stride]; asynchronous"""
+        check(lib().csdr_plotter_batch_get_lines_all(self.h, C.c_void_p(d_rgb), stride, C.c_void_p(stream) if stream else None),
+              "csdr_plotter_batch_get_lines_all")
+
+    def waterfall_ptr(self, view, d_rgb, stream=None):
+        """one view's image unrolled into device uint32 [waterfall height][w]; asynchronous; returns the height"""
+        return check(lib().csdr_plotter_batch_get_waterfall_dev(self.h, view, C.c_void_p(d_rgb),
+                                                                C.c_void_p(stream) if stream else None),
+                     "csdr_plotter_batch_get_waterfall_dev")

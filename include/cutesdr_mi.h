@@ -882,6 +882,90 @@ int csdr_scope_batch_get_fft_state(csdr_scope_batch *s, int channel, long long *
  * left untouched.  Asynchronous on `stream`, behind the puts before it. */
 int csdr_scope_batch_get_fft_screens_all(csdr_scope_batch *s, int *d_out, long long out_stride, void *stream);
 
+/* ----------------------------------------------------------------------------------------
+ * Batch plotter: V views, each one CPlotter's display state (reference gui/plotter.cpp, gui/plotter.h), over the rows of
+ * a csdr_fft_batch.  Several views may plot the same row with their own window size, span, dB range and 2D/waterfall
+ * split; one launch per draw updates every running view: the waterfall's scroll and new top line, the 2D trace and the
+ * overload pen.  The waterfall image stays on the device.
+ *
+ * Per view, as the reference:
+ *   Construction (gui/plotter.cpp:100-114): span 50000, m_MaxdB 0, m_MindB -130, m_dBStepSize 10, 50 percent 2D, not
+ * running, size (0, 0), m_ADOverLoad false, one-shot counter 0.  Here also: view v plots row v until set_source.
+ *   resizeEvent (:374-389): 2D height = percent * H / 100, waterfall height = (100 - percent) * H / 100 in integer
+ * arithmetic, both W wide; the waterfall is black after EVERY resize event, one at the same size included; then
+ * DrawOverlay, whose only arithmetic effect is m_MindB = m_MaxdB - VERT_DIVS (14) * m_dBStepSize (:597, plotter.h:16),
+ * and only when the overlay pixmap is not null: W > 0 and 2D height > 0.
+ *   SetPercent2DScreen (plotter.h:35) stores the percentage and resizes at the widget's size (so it blackens too).
+ *   SetSpanFreq, SetMaxdB, SetdBStepSize (plotter.h:41-44) only store; m_MindB follows at the next UpdateOverlay(),
+ * which the reference's host calls after each of them (gui/mainwindow.cpp:914-915, 930-933).  A setter without
+ * update_overlay leaves m_MindB as it was, here too.
+ *   SetADOverload (plotter.h:43) sets the flag and zeroes the one-shot counter; SetRunningState stores the flag, and
+ * draw() does nothing for a view that is not running, not even the scroll.
+ *   draw() (:408-480): scroll the waterfall down one line (:425); GetScreenIntegerFFTData(255, w, m_MaxdB, m_MindB,
+ * -m_Span / 2, m_Span / 2) gives the new top line m_ColorTbl[255 - y] (:429-441) and its return value is the FFT's
+ * overload flag; the same call at the 2D height gives the trace (:451-474); the pen is red if m_ADOverLoad or that
+ * flag, else green, and in the red branch only `if (counter++ > 10) { counter = 0; m_ADOverLoad = false; }` (:458-468;
+ * OVERLOAD_DISPLAY_LIMIT :50) -- a SetADOverload(true) alone shows red for 12 draws.  -m_Span / 2 and m_Span / 2 are
+ * integer divisions of a qint32.
+ *   The mapping is csdr_fft_batch_get_screen's, bit for bit, for finite bels (dsp/fft.cpp:308-410 with that function's
+ * two bound fixes): every pixel of [0, w) is defined by a draw, and a pixel that covers several bins shows the smallest
+ * of their levels -- its strongest bin, or, while a stale m_MindB lies above m_MaxdB (a setter without update_overlay, or
+ * a view without a 2D pixmap, whose m_MindB never follows), its weakest, as that function does.  Where C leaves a
+ * double -> int conversion undefined the value saturates; that includes m_MaxdB == m_MindB, where the gain is infinite.
+ *
+ * Storage and ordering.  The settings live on the host; a setter touches no device memory and waits for nothing, and
+ * what it changed -- a resize's blackening and SetADOverload included -- travels with the next draw in stream order
+ * (a ring of 16 pinned parameter slots; a call waits, on that launch's event only, when the launch 16 before it has
+ * not finished).  Trace, waterfall ring, pen, one-shot counter and m_ADOverLoad live on the device.  The waterfall is a
+ * ring [wf_h][w] of 0xFFRRGGBB with a head row: a draw moves the head and writes one line, a resize resets head and
+ * line count, and the readers show black below the lines drawn since -- no image is ever copied or cleared.  resize
+ * and set_percent_2d allocate when a view grows (every allocation of a call before any view changes: CSDR_ENOMEM
+ * changes nothing); they then wait for the object's launches in flight.  The trace is forgotten (all 0 until the next
+ * draw) when the widget's size changes and on every set_percent_2d, where the reference makes a new m_2DPixmap
+ * (:378-384); a resize event at the same size keeps it.
+ *   view < 0 in a setter: every view.  Refused with CSDR_EINVAL, nothing changed: a view out of range, a negative row,
+ * w or h outside [0, 4096] (MAX_SCREENSIZE :48), percent outside [0, 100], step < 1 (m_MaxdB == m_MindB).
+ *
+ * Out of scope: painting (grid, text, cursors: DrawOverlay's drawing, MakeFrequencyStrs, the mouse), CMeter, a shard
+ * form (one plotter batch per device), image encoding, a per-view FFT size or average (properties of the row).
+ * -------------------------------------------------------------------------------------- */
+typedef struct csdr_plotter_batch csdr_plotter_batch;
+/* NULL without a HIP device (no CPU fallback); views 1..4096 */
+csdr_plotter_batch *csdr_plotter_batch_create(int device, int views);
+void csdr_plotter_batch_destroy(csdr_plotter_batch *p);
+int csdr_plotter_batch_set_source(csdr_plotter_batch *p, int view, int fft_row);      /* the row of the spectrum batch a view plots */
+int csdr_plotter_batch_resize(csdr_plotter_batch *p, int view, int w, int h);         /* resizeEvent :374-389; may allocate and then waits */
+int csdr_plotter_batch_set_percent_2d(csdr_plotter_batch *p, int view, int percent);  /* SetPercent2DScreen; may allocate and then waits */
+int csdr_plotter_batch_set_span(csdr_plotter_batch *p, int view, int span_hz);        /* SetSpanFreq */
+int csdr_plotter_batch_set_max_db(csdr_plotter_batch *p, int view, int max_db);       /* SetMaxdB */
+int csdr_plotter_batch_set_db_step(csdr_plotter_batch *p, int view, int step);        /* SetdBStepSize; step >= 1 */
+int csdr_plotter_batch_update_overlay(csdr_plotter_batch *p, int view);               /* DrawOverlay's m_MindB :597 */
+int csdr_plotter_batch_set_ad_overload(csdr_plotter_batch *p, int view, int on);      /* SetADOverload; applied by the next draw, running or not */
+int csdr_plotter_batch_set_running(csdr_plotter_batch *p, int view, int on);          /* SetRunningState */
+/* CPlotter::draw of every running view, one launch on `stream`: reads f's size, sample rate, invert flag, averaged bels
+ * and overload words as they are at the call, in stream order behind the puts issued on `stream`; neither uses nor
+ * disturbs the translate table csdr_fft_batch_get_screen caches in f.  Returns the number of views drawn: the running
+ * ones with w > 0 (a running view with w == 0 takes the pen step, draws nothing and is not counted; wf_h == 0: a trace
+ * only; 2D height 0: a waterfall only, the trace all 0).  CSDR_EINVAL, nothing changed: f NULL or on another device, a running view whose row is >= f's
+ * channels. */
+int csdr_plotter_batch_draw(csdr_plotter_batch *p, csdr_fft_batch *f, void *stream);
+/* host readers: wait for the object's last call only (its event, on a stream of the object's own).
+ * get_trace: the last draw's w levels into out_y and its pen into pen_red (1 red, 0 green; may be NULL); all 0 before
+ * the first draw since the size changed; returns w.  get_waterfall: the image [wf_h][w], newest line first, black below the lines
+ * drawn since the last resize; returns wf_h. */
+int csdr_plotter_batch_get_trace(csdr_plotter_batch *p, int view, int *out_y, int *pen_red);
+int csdr_plotter_batch_get_waterfall(csdr_plotter_batch *p, int view, unsigned int *out_rgb);
+/* w, 2D height, waterfall height and m_MindB of a view (any pointer may be NULL); host state, waits for nothing */
+int csdr_plotter_batch_get_geometry(csdr_plotter_batch *p, int view, int *w, int *h2d, int *wf_h, int *min_db);
+/* device readers, asynchronous on `stream` behind the object's calls before them; a later draw waits for them.
+ * get_traces_all: view v's trace into d_y[v * stride ...] (the first w entries, the rest untouched) and its pen into
+ * d_pen[v] (may be NULL).  get_lines_all: each view's newest waterfall line into d_rgb[v * stride ...], black before
+ * the first draw since a resize, untouched for a view without a waterfall.  stride >= the widest view.
+ * get_waterfall_dev: one view's image unrolled into d_rgb [wf_h][w], row pitch w, as get_waterfall; returns wf_h. */
+int csdr_plotter_batch_get_traces_all(csdr_plotter_batch *p, int *d_y, long long stride, int *d_pen, void *stream);
+int csdr_plotter_batch_get_lines_all(csdr_plotter_batch *p, unsigned int *d_rgb, long long stride, void *stream);
+int csdr_plotter_batch_get_waterfall_dev(csdr_plotter_batch *p, int view, unsigned int *d_rgb, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
