@@ -9,6 +9,7 @@
 #include "testgen_host.hpp"
 #include "scope_host.hpp"
 #include "plotter_host.hpp"
+#include "seq_host.hpp"
 #include "fastfir_kernels.h"
 #include "fft_core.hpp"
 #include <cstring>
@@ -475,5 +476,15 @@ void csdr__host_plotter_view(const int *calls, int ncalls, int *out8)
 }
 // the pen of one draw: state2 = {m_ADOverLoad, m_ADOverloadOneShotCounter}, updated; returns 1 for red
 int csdr__host_plotter_pen(int *state2, int fft_overload) { return pl::pen_step(&state2[0], &state2[1], fft_overload); }
+
+// ---- the datagram sequence check's sequential form (seq_host.hpp: seq_walk over seq_step, the function K12 evaluates):
+// npackets datagrams of pkt_len bytes in host memory, one receiver; *last, *missed, *events carried in and out,
+// *first_gap this walk's
+void csdr__host_seq_walk(const void *packets, int npackets, int pkt_len, int *last, long long *missed, long long *events, int *first_gap)
+{
+    seq::State s{*missed, *events, *last, -1};
+    seq::seq_walk((const unsigned char *)packets, npackets, pkt_len, &s);
+    *last = s.last; *missed = s.missed; *events = s.events; *first_gap = s.first_gap;
+}
 
 }  // extern "C"

@@ -1517,3 +1517,62 @@ class PlotterBatch(_Obj):
         return check(lib().csdr_plotter_batch_get_waterfall_dev(self.h, view, C.c_void_p(d_rgb),
                                                                 C.c_void_p(stream) if stream else None),
                      "csdr_plotter_batch_get_waterfall_dev")
+
+
+class SeqCheckBatch(_Obj):
+    """C copies of CUdpThread::OnreadyRead's packet bookkeeping (interface/netiobase.cpp:484-496, m_MissedPackets), one per
+    receiver, over the datagram buffer process_packets reads: per receiver the reference's signed missed count, the
+    number of out-of-sequence datagrams and where the last put's first one was."""
+    _destroy = "csdr_seqcheck_batch_destroy"
+
+    def __init__(self, channels, device=0):
+        self.channels, self.device = int(channels), device
+        self.h = check_ptr(lib().csdr_seqcheck_batch_create(device, self.channels), "csdr_seqcheck_batch_create")
+
+    def put(self, packets, npackets=None, pkt_len=None, stream=None):
+        """packets: uint8 [channels, npackets, pkt_len] (uploaded, checked, waited for) or a device pointer to such a
+        buffer with npackets and pkt_len given (asynchronous on stream)"""
+        if isinstance(packets, (int, np.integer)):
+            check(lib().csdr_seqcheck_batch_put(self.h, C.c_void_p(int(packets)), npackets, pkt_len,
+                                                C.c_void_p(stream) if stream else None), "csdr_seqcheck_batch_put")
+            return
+        raw = np.ascontiguousarray(packets, dtype=np.uint8)
+        assert raw.ndim == 3 and raw.shape[0] == self.channels
+        dp = DeviceBuffer(max(raw.nbytes, 4), self.device)
+        dp.upload(raw)
+        try:
+            check(lib().csdr_seqcheck_batch_put(self.h, C.c_void_p(dp.ptr), raw.shape[1], raw.shape[2],
+                                                C.c_void_p(stream) if stream else None), "csdr_seqcheck_batch_put")
+            sync(self.device)
+        finally:
+            dp.free()
+
+    def clear(self, channel=-1):
+        """missed, events <- 0, the expected number kept (the GUI's start, gui/mainwindow.cpp:703); channel < 0: all"""
+        check(lib().csdr_seqcheck_batch_clear(self.h, channel), "csdr_seqcheck_batch_clear")
+
+    def reset(self, channel=-1):
+        """clear, and the expected number <- 0 (a new CUdpThread, netiobase.cpp:433)"""
+        check(lib().csdr_seqcheck_batch_reset(self.h, channel), "csdr_seqcheck_batch_reset")
+
+    def get(self, channel):
+        """(missed, events, first_gap, last) of one receiver; waits for the object's last call only"""
+        m, e, g, l = C.c_longlong(), C.c_longlong(), C.c_int(), C.c_int()
+        check(lib().csdr_seqcheck_batch_get(self.h, channel, *[C.cast(C.byref(x), C.c_void_p) for x in (m, e, g, l)]),
+              "csdr_seqcheck_batch_get")
+        return m.value, e.value, g.value, l.value
+
+    def get_all_ptr(self, d_missed=None, d_events=None, d_first_gap=None, stream=None):
+        """into device arrays int64 / int64 / int32 [channels]; asynchronous on stream"""
+        check(lib().csdr_seqcheck_batch_get_all(self.h, *[C.c_void_p(p) if p else None for p in (d_missed, d_events, d_first_gap)],
+                                                C.c_void_p(stream) if stream else None), "csdr_seqcheck_batch_get_all")
+
+    def get_all(self):
+        """(missed int64 [channels], events int64 [channels], first_gap int32 [channels])"""
+        n = self.channels
+        d = DeviceBuffer(20 * n, self.device)
+        self.get_all_ptr(d.ptr, d.ptr + 8 * n, d.ptr + 16 * n)
+        sync(self.device)
+        v = d.download(np.uint8, 20 * n)
+        d.free()
+        return v[:8 * n].view(np.int64).copy(), v[8 * n:16 * n].view(np.int64).copy(), v[16 * n:].view(np.int32).copy()

@@ -966,6 +966,47 @@ int csdr_plotter_batch_get_traces_all(csdr_plotter_batch *p, int *d_y, long long
 int csdr_plotter_batch_get_lines_all(csdr_plotter_batch *p, unsigned int *d_rgb, long long stride, void *stream);
 int csdr_plotter_batch_get_waterfall_dev(csdr_plotter_batch *p, int view, unsigned int *d_rgb, void *stream);
 
+/* --------------------------------------------------------------------------------------
+ * Datagram sequence check: C independent copies of the packet bookkeeping of CUdpThread::OnreadyRead (reference
+ * interface/netiobase.cpp:484-496 for 24 bit, :509-521 for 16 bit: the same text), one per receiver, advanced over the
+ * datagrams of one call in one launch.  The buffer is the one csdr_demod_batch_process_packets reads -- [channels]
+ * [npackets][pkt_len] bytes as they arrived -- so one upload serves both calls on one stream; bytes 2-3 of each
+ * datagram, little endian, are its sequence number, and nothing else of the datagram is read.
+ *
+ * The rule, per receiver: `last` is m_LastSeqNum, a quint16 that starts at 0 (:433); `missed` is
+ * CNetIOBase::m_MissedPackets (the GUI's status line, gui/mainwindow.cpp:760), held in 64 bits.  For each datagram in
+ * order:
+ *     if (seq == 0) last = 0;
+ *     if (seq != last) { missed += (int)(qint16)seq - (int)(qint16)last; last = seq; }
+ *     last = (last + 1) & 0xffff; if (last == 0) last = 1;
+ * with the qint16 casts kept: one datagram lost across 0x7fff/0x8000 moves the count by -65535, a duplicate or a late
+ * datagram moves it down.  Two more results of the same test seq != last, which the signed sum hides: `events`, the
+ * number of datagrams that failed it (accumulates like missed; a swap adds +k and -k to missed and 2 or 3 here), and
+ * `first_gap`, the index within the LAST put of its first such datagram, or -1 (also before the first put).
+ *
+ * Ordering.  put is asynchronous on `stream`; the state lives on the device.  clear and reset take effect between the
+ * puts issued before and after them: a small launch on a stream of the object's own, ordered behind the last call by its
+ * event, and the next put waits for that event on its stream -- no host wait, no device-wide one.  get waits for the
+ * object's last call only; get_all is asynchronous on `stream` behind it, and a later put waits for it.
+ *   Refused with CSDR_EINVAL before any state changes: pkt_len other than 1028 or 1444, d_packets NULL or not 4-byte
+ * aligned, npackets < 0, a receiver's npackets * pkt_len at or above 2 GiB (offsets are 32 bit), a channel out of range.
+ * npackets == 0 returns 0 and changes nothing, first_gap included.
+ *
+ * Out of scope: repairing, reordering or dropping anything (the reference only counts); header bytes 0-1 (the
+ * reference tells the formats apart by the datagram's size alone); a shard form (one object per device).
+ * -------------------------------------------------------------------------------------- */
+typedef struct csdr_seqcheck_batch csdr_seqcheck_batch;
+/* NULL without a HIP device (no CPU fallback); channels >= 1 */
+csdr_seqcheck_batch *csdr_seqcheck_batch_create(int device, int channels);
+void csdr_seqcheck_batch_destroy(csdr_seqcheck_batch *s);
+int csdr_seqcheck_batch_put(csdr_seqcheck_batch *s, const void *d_packets, int npackets, int pkt_len, void *stream);
+int csdr_seqcheck_batch_clear(csdr_seqcheck_batch *s, int channel);   /* missed, events <- 0; last kept (mainwindow.cpp:703); channel < 0: all */
+int csdr_seqcheck_batch_reset(csdr_seqcheck_batch *s, int channel);   /* and last <- 0 (netiobase.cpp:433) */
+/* one receiver's record to the host (any pointer may be NULL) */
+int csdr_seqcheck_batch_get(csdr_seqcheck_batch *s, int channel, long long *missed, long long *events, int *first_gap, int *last);
+/* every receiver's into device arrays [channels] of the caller's (any may be NULL) */
+int csdr_seqcheck_batch_get_all(csdr_seqcheck_batch *s, long long *d_missed, long long *d_events, int *d_first_gap, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
