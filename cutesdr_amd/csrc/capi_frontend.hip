@@ -3,21 +3,13 @@
 // NCO-spur DC estimate (interface/sdrinterface.cpp:829-848).
 #include "capi_common.hpp"
 #include "capi_internal.hpp"
-#include "frontend_kernels.h"
+#include "nb_host.hpp"
 #include "ref_constants.hpp"
 #include <cmath>
 #include <cstdint>
 #include <vector>
 
 using namespace csdr;
-
-struct NbHost {                          // the SetupBlanker comparands (noiseproc.cpp:80-86)
-    bool configured = false, on = false;
-    double thresh = 0, width = 0, fs = 0;
-    int mag_n = 0;                       // as on the device (a rate-only change does not reconfigure: not derivable from fs)
-    bool integral = true;                // every sample since the last set-up (which clears sum and buffers) came from datagrams:
-                                         // the moving sum and the history are whole multiples of 2^-8 (frontend_kernels.hip)
-};
 
 struct csdr_noiseproc_batch {
     int device, channels;
@@ -33,9 +25,19 @@ struct csdr_noiseproc_batch {
 };
 
 // tests (A/B of the two mask kernels in one process): 0 = always the general kernel
-static int &nb_int_switch() { static int on = !(getenv("CSDR_NB_INT") && atoi(getenv("CSDR_NB_INT")) == 0); return on; }
-static bool nb_int_enabled() { return nb_int_switch() != 0; }
-extern "C" int csdr__noiseproc_set_int(int on) { if (on >= 0) nb_int_switch() = on; return nb_int_switch(); }
+static int nb_int_switch = 1;
+extern "C" int csdr__noiseproc_set_int(int on) { if (on >= 0) nb_int_switch = on; return nb_int_switch; }
+
+// A datagram argument of an entry point ([channels][npackets][pkt_len] bytes) as a WireIn.  Returns the rules it breaks,
+// for the entry point's own error text: the two datagram lengths; 32-bit offsets and 32-bit loads in the kernels
+// (wire_format.hpp) -- a channel's datagrams of one call below 2 GiB, the buffer 4-byte aligned
+enum { WIRE_LEN = 1, WIRE_2GIB = 2, WIRE_ALIGN = 4 };
+static int wire_in(const void *d_packets, int npackets, int pkt_len, WireIn &w)
+{
+    if (pkt_len != 1028 && pkt_len != 1444) return WIRE_LEN;
+    w = WireIn{(const unsigned char *)d_packets, (long)npackets * pkt_len, pkt_len, pkt_len == 1444 ? 240 : 256};
+    return (w.chan_stride >= (1l << 31) ? WIRE_2GIB : 0) | (((uintptr_t)d_packets & 3) ? WIRE_ALIGN : 0);
+}
 
 static int nb_setup_one(csdr_noiseproc_batch *b, int c, int on, double thresh, double width, double fs)
 {
@@ -111,13 +113,12 @@ int csdr__noiseproc_batch_process_packets(csdr_noiseproc_batch *b, const void *d
                                           float *d_out, long long out_stride, void *stream)
 {
     if (!b || !d_packets || !d_out || npackets < 0) return fail(CSDR_EINVAL, "bad argument");
-    if (pkt_len != 1028 && pkt_len != 1444) return fail(CSDR_EINVAL, "packet length %d", pkt_len);
-    const int per = pkt_len == 1444 ? 240 : 256;
-    if ((long)npackets * pkt_len >= (1l << 31)) return fail(CSDR_EINVAL, "a channel's datagrams of one call must stay below 2 GiB");
-    // the kernel fetches the 16-bit samples with 32-bit loads (wire_format.hpp): same rule as the down-converter
-    if ((uintptr_t)d_packets & 3) return fail(CSDR_EINVAL, "datagram buffer must be 4-byte aligned");
-    return nb_run(b, nullptr, 0, WireIn{(const unsigned char *)d_packets, (long)npackets * pkt_len, pkt_len, per},
-                  npackets * per, d_out, out_stride, stream);
+    WireIn wire;
+    const int bad = wire_in(d_packets, npackets, pkt_len, wire);
+    if (bad & WIRE_LEN) return fail(CSDR_EINVAL, "packet length %d", pkt_len);
+    if (bad & WIRE_2GIB) return fail(CSDR_EINVAL, "a channel's datagrams of one call must stay below 2 GiB");
+    if (bad & WIRE_ALIGN) return fail(CSDR_EINVAL, "datagram buffer must be 4-byte aligned");
+    return nb_run(b, nullptr, 0, wire, npackets * wire.per, d_out, out_stride, stream);
 }
 /* internal: the shape of a blanker object (csdr_demod_batch_process_packets / _process_blanked check that it is theirs:
  * the mask rows, and the state / history the down-converter indexes by input row, are sized by the CHAIN's width) */
@@ -142,11 +143,10 @@ int csdr__noiseproc_batch_mask(csdr_noiseproc_batch *b, const float *d_in, long 
     if (mask_stride * 32 < n_per_channel) return fail(CSDR_EINVAL, "mask rows too short");
     WireIn wire{nullptr, 0, 0, 0};
     if (d_packets) {
-        if (pkt_len != 1028 && pkt_len != 1444) return fail(CSDR_EINVAL, "packet length %d", pkt_len);
-        const int per = pkt_len == 1444 ? 240 : 256;
-        if ((long)npackets * pkt_len >= (1l << 31) || ((uintptr_t)d_packets & 3) || npackets * per != n_per_channel)
+        const int bad = wire_in(d_packets, npackets, pkt_len, wire);
+        if (bad & WIRE_LEN) return fail(CSDR_EINVAL, "packet length %d", pkt_len);
+        if (bad || npackets * wire.per != n_per_channel)
             return fail(CSDR_EINVAL, "datagram buffer: 4-byte aligned, below 2 GiB per channel, npackets x samples = n");
-        wire = WireIn{(const unsigned char *)d_packets, (long)npackets * pkt_len, pkt_len, per};
     }
     const size_t half = (size_t)b->channels * NB_HIST * 2;
     *d_state = b->d_chan + (size_t)b->cur * b->channels;
@@ -165,32 +165,13 @@ static int nb_run(csdr_noiseproc_batch *b, const float *d_in, long long in_strid
     a.hist = b->d_hist + b->cur * half; a.hist_next = b->d_hist + (b->cur ^ 1) * half;
     a.mask = d_mask; a.mask_stride = mask_stride;
     a.channels = b->channels; a.n = n_per_channel;
-    static const bool ring_env = !(getenv("CSDR_NB_RING") && atoi(getenv("CSDR_NB_RING")) == 0);
-    a.ring = ring_env;
     // float rows: from here on the sums may carry roundings -- the integer form is off until the next set-up clears them
     if (!wire.pk) for (auto &h : b->h) h.integral = false;
-    a.int_ok = nb_int_enabled() && wire.pk != nullptr;
-    for (int c = 0; c < b->channels && a.int_ok; c++) if (b->h[c].on && !b->h[c].integral) a.int_ok = 0;
-    for (int c = 0; c < b->channels && a.ring; c++)
-        if (b->h[c].on && (b->h[c].mag_n + 1 < noiseblank_ring_min(d_mask != nullptr) ||
-                           b->h[c].mag_n + 1 > noiseblank_ring_max(d_mask != nullptr))) a.ring = 0;
-    // segments: enough workgroups to fill the chip, each at least 32 tiles long (the longest blank
-    // width is 4 tiles, the moving-sum reduction at a segment start another ~10-32 tiles' worth of reads)
-    // (mask mode: 74 registers, three 512-thread workgroups per CU: 3072 workgroups = four rounds measured best,
-    // 3.28 ms for the C4 share's datagram-fed chain against 3.36 with 2048 and 3.49 with 4096)
-    // (with the ring: two workgroups per CU -- 64 KB of ring each -- and ONE round of them: mask form 1.07 ms against
-    // 1.11 with two rounds, 1.18 with six; sample form 2.20 against 2.24 and 2.29 with four)
-    static const long want_env = getenv("CSDR_NB_WGS") ? atol(getenv("CSDR_NB_WGS")) : 0;
-    const long want_wgs = want_env > 0 ? want_env : (a.ring ? 512 : (d_mask ? 3072 : 2048));
-    long nseg = (want_wgs + b->channels - 1) / b->channels;
-    const long tile = noiseblank_tile(d_mask != nullptr);
-    const long min_seg = 32 * tile;
-    if (nseg > n_per_channel / min_seg) nseg = n_per_channel / min_seg;
-    if (nseg < 1) nseg = 1;
-    long seg_len = (n_per_channel + nseg - 1) / nseg;
-    seg_len = (seg_len + tile - 1) / tile * tile;
-    a.seg_len = (int)seg_len;
-    a.nseg = (int)((n_per_channel + seg_len - 1) / seg_len);
+    static const bool ring_env = !(getenv("CSDR_NB_RING") && atoi(getenv("CSDR_NB_RING")) == 0);
+    const bool mask = d_mask != nullptr;
+    const NbForm form = nb_choose_form(mask, wire.pk ? wire.pkt_len : 0, b->h.data(), b->channels, ring_env, nb_int_switch != 0);
+    const NbSegments segs = nb_segments(n_per_channel, b->channels, mask, nb_form_ring(form));
+    a.form = form; a.nseg = segs.nseg; a.seg_len = segs.seg_len;
     CSDR_HIP(noiseblank_launch(a, (hipStream_t)stream));
     b->cur ^= 1;
     return CSDR_OK;
@@ -254,17 +235,17 @@ int csdr_ingest_unpack(int device, const void *d_packets, int channels, int npac
                        long long out_stride, const double *d_dc, void *stream)
 {
     if (!d_packets || !d_out || channels < 1 || npackets < 0) return fail(CSDR_EINVAL, "bad argument");
-    if (pkt_len != 1028 && pkt_len != 1444)
+    WireIn wire;
+    const int bad = wire_in(d_packets, npackets, pkt_len, wire);        // (this kernel's offsets are 64-bit: no 2 GiB rule)
+    if (bad & WIRE_LEN)
         return fail(CSDR_EINVAL, "packet length %d: the wire format has 1028-byte (16 bit) and 1444-byte (24 bit) "
                     "datagrams", pkt_len);
-    const int per = pkt_len == 1444 ? 240 : 256;
-    if ((long long)npackets * per > out_stride) return fail(CSDR_EINVAL, "out_stride too small");
-    if ((out_stride & 1) || ((uintptr_t)d_out & 15) || ((uintptr_t)d_packets & 3))
+    if ((long long)npackets * wire.per > out_stride) return fail(CSDR_EINVAL, "out_stride too small");
+    if ((out_stride & 1) || ((uintptr_t)d_out & 15) || (bad & WIRE_ALIGN))
         return fail(CSDR_EINVAL, "unpack: d_packets must be 4-byte aligned, d_out 16-byte aligned, out_stride even");
     if (!device_ok(device)) return CSDR_EHIP;
-    CSDR_HIP(unpack_launch((const unsigned char *)d_packets, (long)npackets * pkt_len, channels, npackets, pkt_len,
-                           d_out, out_stride, d_dc, (hipStream_t)stream));
-    return npackets * per;
+    CSDR_HIP(unpack_launch(wire.pk, wire.chan_stride, channels, npackets, pkt_len, d_out, out_stride, d_dc, (hipStream_t)stream));
+    return npackets * wire.per;
 }
 int csdr_ingest_unpack_host(int device, const void *packets, int npackets, int pkt_len, double *out_iq)
 {
@@ -300,11 +281,13 @@ int csdr_ingest_spurcal_packets(int device, const void *d_packets, int channels,
                                 void *stream)
 {
     if (!d_packets || !d_dc || channels < 1 || npackets < 0) return fail(CSDR_EINVAL, "bad argument");
-    if (pkt_len != 1028 && pkt_len != 1444) return fail(CSDR_EINVAL, "packet length %d", pkt_len);
-    if ((long)npackets * pkt_len >= (1l << 31)) return fail(CSDR_EINVAL, "a channel's datagrams of one call must stay below 2 GiB");
-    if ((uintptr_t)d_packets & 3) return fail(CSDR_EINVAL, "datagram buffer must be 4-byte aligned");
+    WireIn wire;
+    const int bad = wire_in(d_packets, npackets, pkt_len, wire);
+    if (bad & WIRE_LEN) return fail(CSDR_EINVAL, "packet length %d", pkt_len);
+    if (bad & WIRE_2GIB) return fail(CSDR_EINVAL, "a channel's datagrams of one call must stay below 2 GiB");
+    if (bad & WIRE_ALIGN) return fail(CSDR_EINVAL, "datagram buffer must be 4-byte aligned");
     if (!device_ok(device)) return CSDR_EHIP;
-    CSDR_HIP(spurcal_packets_launch((const unsigned char *)d_packets, channels, npackets, pkt_len, d_dc, (hipStream_t)stream));
+    CSDR_HIP(spurcal_packets_launch(wire.pk, channels, npackets, wire.pkt_len, d_dc, (hipStream_t)stream));
     return CSDR_OK;
 }
 int csdr_ingest_spurcal_host(int device, int n, const double *in_iq, double *dc_iq)

@@ -10,6 +10,7 @@
 #include "scope_host.hpp"
 #include "plotter_host.hpp"
 #include "seq_host.hpp"
+#include "nb_host.hpp"
 #include "fastfir_kernels.h"
 #include "fft_core.hpp"
 #include <cstring>
@@ -485,6 +486,26 @@ void csdr__host_seq_walk(const void *packets, int npackets, int pkt_len, int *la
     seq::State s{*missed, *events, *last, -1};
     seq::seq_walk((const unsigned char *)packets, npackets, pkt_len, &s);
     *last = s.last; *missed = s.missed; *events = s.events; *first_gap = s.first_gap;
+}
+
+// ---- the noise blanker's host logic (nb_host.hpp)
+// samples per tile the segments of a call are cut by (mask form or sample form), and the ring's window limits
+void csdr__host_nb_geometry(int mask, int *seg_tile, int *ring_min, int *ring_max)
+{
+    *seg_tile = nb_seg_tile(mask != 0); *ring_min = nb_ring_min(mask != 0); *ring_max = nb_ring_max(mask != 0);
+}
+void csdr__host_nb_segments(long long n, int channels, int mask, int ring, int *nseg, int *seg_len)
+{
+    const NbSegments s = nb_segments((long)n, channels, mask != 0, ring != 0);
+    *nseg = s.nseg; *seg_len = s.seg_len;
+}
+// the kernel form (NbForm) of a call: mask or samples out, pkt_len 0 for float rows; per channel on, mag_n, integral
+int csdr__host_nb_form(int mask, int pkt_len, int channels, const int *on, const int *mag_n, const int *integral,
+                       int ring_switch, int int_switch)
+{
+    std::vector<NbHost> h(channels);
+    for (int c = 0; c < channels; c++) { h[c].on = on[c] != 0; h[c].mag_n = mag_n[c]; h[c].integral = integral[c] != 0; }
+    return (int)nb_choose_form(mask != 0, pkt_len, h.data(), channels, ring_switch != 0, int_switch != 0);
 }
 
 }  // extern "C"

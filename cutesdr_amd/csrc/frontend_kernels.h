@@ -29,19 +29,13 @@ struct NbArgs {
                                         // no 8-byte write and re-read per sample, no third input stream here
     const float *hist; float *hist_next;    // [channels][NB_HIST] complex: the last NB_HIST inputs, ping-pong
     int channels, n;
-    int ring;                           // the window's magnitudes stay in an LDS ring (frontend_kernels.hip) -- only when
-                                        // EVERY channel with the blanker on has noiseblank_ring_min(mask form?) <=
-                                        // mag_n + 1 <= noiseblank_ring_max(mask form?)
-    int int_ok;                         // mask form on datagrams: every sample the blanker has seen since its set-up came from
-                                        // datagrams -- sum and history are integral in units of 2^-8 and the integer kernel
-                                        // (noiseblank_mask_int_kernel) decides exactly what the general one does
-    int nseg, seg_len;                  // each channel's call is cut into nseg segments of seg_len samples (a
-                                        // multiple of 1024, >= 4 blank widths), one workgroup each
+    int form;                           // NbForm (nb_host.hpp: nb_choose_form): samples or mask out, the window's magnitudes
+                                        // in an LDS ring or fetched again, the general kernel or the integer one
+    int nseg, seg_len;                  // each channel's call is cut into nseg segments of seg_len samples, one workgroup
+                                        // each (nb_host.hpp: nb_segments -- whole tiles of the form that runs; a segment
+                                        // that is not the whole call is >= 32 tiles, four times the longest warm-up)
 };
-hipError_t noiseblank_launch(const NbArgs &a, hipStream_t stream);
-int noiseblank_ring_min(bool mask);
-int noiseblank_ring_max(bool mask);
-int noiseblank_tile(bool mask);        // samples per tile of the kernel (its mask form: a.out == nullptr): segment lengths are multiples of it
+hipError_t noiseblank_launch(const NbArgs &a, hipStream_t stream);     // noiseblank_kernels.hip
 
 // packets: [channels][npackets][pkt_len] bytes, pkt_len 1028 (16 bit, 256 samples) or 1444 (24 bit, 240);
 // out complex fp32 [channels][out_stride]; dc: optional [channels][2] doubles subtracted (I, Q)

@@ -9,28 +9,22 @@
 //   put(x) / get(x)   N doubles of a row of the workgroup's exchange area
 #pragma once
 #include <hip/hip_runtime.h>
+#include "wave_dpp.hpp"
 
 namespace csdr {
 
 constexpr int PT = 1024;                 // K4's tile length (samples); here because a thread's share of a scan, Wg<NW>::LC, is cut from it
 constexpr int PC_MAX_WAVES = 4;          // waves of the largest workgroup that scans
 
-// A wave's scan steps on the DPP network instead of __shfl_up (two ds_bpermute per double and step: an LDS-pipe
-// round trip each, and a tile runs some ninety such steps one after the other on a single wave per SIMD).
-// pc_dpp<CTRL, ROW_MASK>(v, ident): v of the source lane, `ident` where the step has none.  The six steps
-// row_shr 1, 2, 4, 8, row_bcast 15 (rows 1, 3), row_bcast 31 (rows 2, 3) leave in every lane the combination of
-// lanes 0 .. lane, like the six __shfl_up steps (associativity is all they need; identities make the lane guards
-// unnecessary); wave_shr 1 then gives the exclusive value.
+// A wave's scan steps run on the DPP network (wave_dpp.hpp) instead of __shfl_up: a tile runs some ninety such steps
+// one after the other on a single wave per SIMD.  pc_dpp<CTRL, ROW_MASK>(v, ident): v of the source lane, `ident` where
+// the step has none.
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ double pc_dpp(double v, double ident)
 {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v), o = (unsigned long long)__double_as_longlong(ident);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)o, (int)(unsigned)u, CTRL, ROW_MASK, 0xf, false);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)(o >> 32), (int)(unsigned)(u >> 32), CTRL, ROW_MASK, 0xf, false);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+    return __longlong_as_double((long long)wave_dpp64<CTRL, ROW_MASK>((unsigned long long)__double_as_longlong(v),
+                                                                       (unsigned long long)__double_as_longlong(ident)));
 }
-#define PC_SCAN_STEPS(STEP) STEP(0x111, 0xf) STEP(0x112, 0xf) STEP(0x114, 0xf) STEP(0x118, 0xf) STEP(0x142, 0xa) STEP(0x143, 0xc)
-constexpr int PC_WAVE_SHR1 = 0x138;
 
 // s -> a s + b
 struct Aff1 {
@@ -167,9 +161,9 @@ struct Wg {
     {
         static_assert(M::N <= 8, "a row of PcSync::xch holds eight doubles");
 #define PC_STEP(C_, R_) m = m.after(m.template dpp<C_, R_>());
-        PC_SCAN_STEPS(PC_STEP)
+        WAVE_SCAN_STEPS(PC_STEP)
 #undef PC_STEP
-        M ex = m.template dpp<PC_WAVE_SHR1, 0xf>();
+        M ex = m.template dpp<WAVE_SHR1, 0xf>();
         if constexpr (NW == 1) {
             total = m.lane63();
         } else {
@@ -193,7 +187,7 @@ struct Wg {
     {
         double incl = x;
 #define PC_STEP(C_, R_) incl += pc_dpp<C_, R_>(incl, 0.0);
-        PC_SCAN_STEPS(PC_STEP)
+        WAVE_SCAN_STEPS(PC_STEP)
 #undef PC_STEP
         double ex = incl - x;
         if constexpr (NW > 1) {
@@ -208,7 +202,7 @@ struct Wg {
     // value of thread t-1 (thread 0 gets `first`)
     __device__ __forceinline__ float prev_thread(float v, float first) const
     {
-        float p = __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), PC_WAVE_SHR1, 0xf, 0xf, false));
+        float p = __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), WAVE_SHR1, 0xf, 0xf, false));
         if constexpr (NW > 1) {
             double (*xc)[8] = xbank();
             if (lane == 63) xc[w][6] = (double)v;

@@ -21,6 +21,22 @@ struct WireIn {                          // optional packed input of a kernel; p
 typedef float wf2 __attribute__((ext_vector_type(2)));
 typedef float wf4 __attribute__((ext_vector_type(4)));
 
+// Where sample i of a channel's datagram sequence starts.  With i even that is a 4-byte aligned address, and the words
+// from there hold the samples up to the end of i's datagram back to back: 3 words per sample pair (24 bit), 1 word
+// per sample (16 bit).
+__device__ __forceinline__ const unsigned char *wire_at24(const unsigned char *chan, unsigned i)
+{
+    const unsigned q = i / 240u, j = i - q * 240u;
+    return chan + (q * 1444u + 4u + 6u * j);
+}
+__device__ __forceinline__ const unsigned char *wire_at16(const unsigned char *chan, unsigned i)
+{
+    return chan + ((i >> 8) * 1028u + 4u + 4u * (i & 255u));
+}
+// ... as the pointer to the first 32-bit word of sample i, i even
+__device__ __forceinline__ const unsigned *wire_words24(const unsigned char *chan, unsigned i) { return reinterpret_cast<const unsigned *>(wire_at24(chan, i)); }
+__device__ __forceinline__ const unsigned *wire_words16(const unsigned char *chan, unsigned i) { return reinterpret_cast<const unsigned *>(wire_at16(chan, i)); }
+
 // Sample i of a channel's datagram sequence, in two halves for kernels that prefetch: wire_sample_fetch issues the
 // loads and leaves the raw words (three 16-bit halves of a 24-bit sample, or the one word of a 16-bit sample),
 // wire_sample_decode turns them into the complex sample where it is consumed.
@@ -28,12 +44,10 @@ __device__ __forceinline__ void wire_sample_fetch(const unsigned char *chan, int
 {
     const unsigned i = (unsigned)i64;
     if (pkt_len == 1444) {
-        const unsigned q = i / 240u, j = i - q * 240u;
-        const unsigned short *h = reinterpret_cast<const unsigned short *>(chan + (q * 1444u + 4u + 6u * j));   // 2-byte aligned
+        const unsigned short *h = reinterpret_cast<const unsigned short *>(wire_at24(chan, i));   // 2-byte aligned
         w[0] = h[0]; w[1] = h[1]; w[2] = h[2];
     } else {
-        const unsigned q = i >> 8, j = i & 255u;
-        w[0] = *reinterpret_cast<const unsigned *>(chan + (q * 1028u + 4u + 4u * j));
+        w[0] = *wire_words16(chan, i);
     }
 }
 __device__ __forceinline__ wf2 wire_sample_decode(const unsigned w[3], int pkt_len)
@@ -61,12 +75,10 @@ __device__ __forceinline__ wf4 wire_pair_fetch(const unsigned char *chan, int pk
 {
     const unsigned i = (unsigned)i64;
     if (pkt_len == 1444) {
-        const unsigned q = i / 240u, j = (i - q * 240u) >> 1;
-        const unsigned *w = reinterpret_cast<const unsigned *>(chan + (q * 1444u + 4u + 12u * j));
+        const unsigned *w = wire_words24(chan, i);
         return wf4{__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2]), 0.f};
     }
-    const unsigned q = i >> 8, j = (i & 255u) >> 1;
-    const unsigned *w = reinterpret_cast<const unsigned *>(chan + (q * 1028u + 4u + 8u * j));
+    const unsigned *w = wire_words16(chan, i);
     return wf4{__uint_as_float(w[0]), __uint_as_float(w[1]), 0.f, 0.f};
 }
 __device__ __forceinline__ wf4 wire_pair_decode(wf4 r, int pkt_len)

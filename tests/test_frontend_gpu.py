@@ -608,3 +608,75 @@ def test_integer_mask_kernel_decides_what_the_general_one_does(oracle, src):
     delayed = np.where(idx >= 0, xs[0][np.maximum(idx, 0)], 0).astype(np.complex64)
     want = q.ProcessBlanker(xs[0][:n0].astype(np.complex128)).astype(np.complex64)
     assert np.array_equal(np.where(bits, np.complex64(0), delayed), want)
+
+
+@pytest.mark.parametrize("src", ["rows", 1028, 1444])
+def test_blank_mask_with_a_channel_off_and_then_on(oracle, src):
+    """The mask form's finish with a channel whose blanker is OFF: three channels at 2 MS/s (the ring form; on datagrams
+    the integer kernel), channel 1 off.  Its mask words must be all zero in every call -- the second one is long
+    enough for two segments per channel, so a segment that is not the last writes zeros too -- while channels 0 and 2
+    give the oracle's words through their masks.  Then channel 1 is switched on (on the oracle object that saw the
+    earlier calls pass through as well) and one more long call must match on all three: the off path left the state
+    and the history the next call needs."""
+    import ctypes as C_
+    import cutesdr_amd as ca
+    L = ca.lib()
+    L.csdr__noiseproc_batch_mask.restype = C_.c_int
+    L.csdr__noiseproc_batch_mask.argtypes = [C_.c_void_p, C_.c_void_p, C_.c_longlong, C_.c_void_p, C_.c_int, C_.c_int, C_.c_int,
+                                             C_.c_void_p, C_.c_longlong, C_.POINTER(C_.c_void_p), C_.POINTER(C_.c_void_p),
+                                             C_.c_void_p]
+    Cn, fs, thresh, width = 3, 2e6, 25.0, 20.0
+    per = 240 if src == 1444 else 256
+    counts = [1, 1100, 3, 1100]                                # datagrams (or 256-sample rows) per call; 1100: > 64 tiles of 4096
+    tot = sum(counts) * per
+    rng = np.random.default_rng(31)
+    x = [1500.0 * (rng.standard_normal(tot) + 1j * rng.standard_normal(tot)) for _ in range(Cn)]
+    for xc in x:
+        xc[rng.random(tot) < 2e-4] += 25000.0
+    if src == "rows":
+        xs = [xc.astype(np.complex64) for xc in x]
+    else:
+        raw = np.stack([(_pack24 if src == 1444 else _pack16)(xc) for xc in x])
+        xs = [oracle.unpack_packets(raw[c], src).astype(np.complex64) for c in range(Cn)]
+    nb = ca.NoiseProcBatch(Cn); nb.setup(True, thresh, width, fs); nb.setup(False, thresh, width, fs, channel=1)
+    refs = []
+    for c in range(Cn):
+        q = oracle.CNoiseProc(); q.SetupBlanker(c != 1, thresh, width, fs); refs.append(q)
+    delay1 = int(width * 1e-6 * fs) // 2 + 1                   # delay_n + 1 (noiseproc.cpp:92-99)
+    since = [0] * Cn                                           # the stream index each channel's delay line starts at (a set-up clears it)
+    k0, blanked, seen = 0, 0, 0
+    for call, npk in enumerate(counts):
+        n, a0 = npk * per, k0 * per
+        if call == len(counts) - 1:
+            nb.setup(True, thresh, width, fs, channel=1); refs[1].SetupBlanker(True, thresh, width, fs)
+            since[1] = a0
+        words = (n + 31) // 32 + 64
+        dm = ca.DeviceBuffer(Cn * words * 4)
+        st, hi = C_.c_void_p(), C_.c_void_p()
+        if src == "rows":
+            part = np.ascontiguousarray(np.stack([xc[a0:a0 + n] for xc in xs]))
+            dp = ca.DeviceBuffer(part.nbytes); dp.upload(part)
+            rc = L.csdr__noiseproc_batch_mask(nb.h, C_.c_void_p(dp.ptr), n, None, 0, 0, n, C_.c_void_p(dm.ptr), words,
+                                              C_.byref(st), C_.byref(hi), None)
+        else:
+            part = np.ascontiguousarray(raw[:, k0:k0 + npk])
+            dp = ca.DeviceBuffer(part.nbytes); dp.upload(part)
+            rc = L.csdr__noiseproc_batch_mask(nb.h, None, 0, C_.c_void_p(dp.ptr), npk, src, n, C_.c_void_p(dm.ptr), words,
+                                              C_.byref(st), C_.byref(hi), None)
+        assert rc == 0
+        ca.sync()
+        m = dm.download(np.uint32, Cn * words).reshape(Cn, words)
+        for c in range(Cn):
+            want = refs[c].ProcessBlanker(xs[c][a0:a0 + n].astype(np.complex128)).astype(np.complex64)
+            if c == 1 and call < len(counts) - 1:              # off: nothing blanked, and the data passes (no delay)
+                assert not m[c, :(n + 31) // 32].any(), (call, np.nonzero(m[c, :(n + 31) // 32])[0][:5])
+                assert np.array_equal(want, xs[c][a0:a0 + n])
+                continue
+            bits = ((m[c, :, None] >> np.arange(32, dtype=np.uint32)) & 1).reshape(-1)[:n].astype(bool)
+            idx = np.arange(a0, a0 + n) - delay1
+            delayed = np.where(idx >= since[c], xs[c][np.maximum(idx, 0)], 0).astype(np.complex64)
+            got = np.where(bits, np.complex64(0), delayed)
+            assert np.array_equal(got, want), (call, c, np.nonzero(got != want)[0][:5])
+            blanked += int(bits.sum()); seen += n
+        k0 += npk
+    assert 0 < blanked < seen                                  # the case blanks, and not everything
