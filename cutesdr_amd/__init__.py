@@ -13,3 +13,4 @@ from .host import TestGenBatch  # noqa: F401
 from .host import ScopeBatch  # noqa: F401
 from .host import PlotterBatch  # noqa: F401
 from .host import SeqCheckBatch  # noqa: F401
+from .host import SpurCalBatch  # noqa: F401

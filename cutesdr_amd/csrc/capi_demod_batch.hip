@@ -761,6 +761,26 @@ int csdr__demod_batch_last_blank(csdr_demod_batch *b, DcBlank *blank, BlankCall 
     if (device) *device = b->device;
     return CSDR_OK;
 }
+/* internal (capi_fft.hip, capi_spurcal.hip): the same for a reader `what` of `channels` receivers on `device` that is
+ * handed the input (form, src, stride, n) -- it must be THAT call's input, and the reader the chain's width on its
+ * device.  CSDR_ESTATE as above, CSDR_EINVAL when anything differs; nothing changed either way. */
+int csdr__demod_batch_blank_for(csdr_demod_batch *b, const char *what, int channels, int device, int form, const void *src,
+                                long long stride, int n, DcBlank *blank)
+{
+    BlankCall call;
+    int b_channels = 0, b_device = -1;
+    const int rc = csdr__demod_batch_last_blank(b, blank, &call, &b_channels, &b_device);
+    if (rc) return rc;
+    if (b_channels != channels || b_device != device)
+        return fail(CSDR_EINVAL, "%s of %d channels on device %d behind a chain of %d on device %d", what, channels, device,
+                    b_channels, b_device);
+    if (call.form != form)
+        return fail(CSDR_EINVAL, "the chain's last blanked call took %s", call.form == BLANK_CALL_PACKETS ? "datagrams" : "fp32 rows");
+    if (call.src != src || call.stride != stride || call.n != n)
+        return fail(CSDR_EINVAL, "not the input of the chain's last blanked call (buffer, %s or count differ)",
+                    form == BLANK_CALL_PACKETS ? "packet length" : "stride");
+    return CSDR_OK;
+}
 /* internal (diagnostics: tools/experiments/r6_repro_mode3.py): how fast each plan group's own buffers stream -- a
  * device-to-device copy of the filter-output rows into the spare rows, timed with events, per group in the batch's launch
  * order; us_out[k] = microseconds of the k-th group's copy, bytes_out[k] its size.  Synchronises. */

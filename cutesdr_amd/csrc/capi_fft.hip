@@ -354,19 +354,7 @@ int csdr_fft_batch_put_display_packets(csdr_fft_batch *f, const void *d_packets,
 static int fft_blank_of(csdr_fft_batch *f, csdr_demod_batch *b, int form, const void *src, long long stride, int n,
                         DcBlank *blank)
 {
-    BlankCall call;
-    int channels = 0, device = -1;
-    const int rc = csdr__demod_batch_last_blank(b, blank, &call, &channels, &device);
-    if (rc) return rc;
-    if (channels != f->channels || device != f->device)
-        return fail(CSDR_EINVAL, "display of %d channels on device %d behind a chain of %d on device %d", f->channels,
-                    f->device, channels, device);
-    if (call.form != form)
-        return fail(CSDR_EINVAL, "the chain's last blanked call took %s", call.form == BLANK_CALL_PACKETS ? "datagrams" : "fp32 rows");
-    if (call.src != src || call.stride != stride || call.n != n)
-        return fail(CSDR_EINVAL, "not the input of the chain's last blanked call (buffer, %s or count differ)",
-                    form == BLANK_CALL_PACKETS ? "packet length" : "stride");
-    return CSDR_OK;
+    return csdr__demod_batch_blank_for(b, "display", f->channels, f->device, form, src, stride, n, blank);
 }
 int csdr_fft_batch_put_display_stream_blanked(csdr_fft_batch *f, csdr_demod_batch *b, const float *d_in,
                                               long long in_stride, int n, const double *d_dc, void *stream)

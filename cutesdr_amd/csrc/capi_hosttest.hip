@@ -10,6 +10,7 @@
 #include "scope_host.hpp"
 #include "plotter_host.hpp"
 #include "seq_host.hpp"
+#include "spurcal_host.hpp"
 #include "nb_host.hpp"
 #include "fastfir_kernels.h"
 #include "fft_core.hpp"
@@ -486,6 +487,22 @@ void csdr__host_seq_walk(const void *packets, int npackets, int pkt_len, int *la
     seq::State s{*missed, *events, *last, -1};
     seq::seq_walk((const unsigned char *)packets, npackets, pkt_len, &s);
     *last = s.last; *missed = s.missed; *events = s.events; *first_gap = s.first_gap;
+}
+
+// ---- the NCO-spur bookkeeping (spurcal_host.hpp: the functions K13 evaluates)
+// a put of n samples in calls of call_len on a receiver with (count, active): out4 = {calls that run the recurrence,
+// samples they cover, count after, active after}
+void csdr__host_spurcal_put(int count, int active, int n, int call_len, int *out4)
+{
+    const spur::Put p = spur::spurcal_put(count, active, n, call_len);
+    out4[0] = p.calls; out4[1] = p.samples; out4[2] = p.count; out4[3] = p.active;
+}
+// ManageNCOSpurOffsets on one receiver: cmd 0 SET(vi, vq), 1 STARTCAL, 2 READ; off2, *count, *active updated
+void csdr__host_spurcal_command(int cmd, double vi, double vq, double *off2, int *count, int *active)
+{
+    spur::Rec r{*count, *active};
+    spur::spurcal_command(cmd, vi, vq, off2, &r);
+    *count = r.count; *active = r.active;
 }
 
 // ---- the noise blanker's host logic (nb_host.hpp)

@@ -44,4 +44,6 @@ int csdr__fft_batch_view(csdr_fft_batch *f, csdr::FftView *v);
 /* capi_demod_batch.hip */
 int csdr__demod_batch_wait_input_free(csdr_demod_batch *b, void *stream);
 int csdr__demod_batch_last_blank(csdr_demod_batch *b, csdr::DcBlank *blank, csdr::BlankCall *call, int *channels, int *device);
+int csdr__demod_batch_blank_for(csdr_demod_batch *b, const char *what, int channels, int device, int form, const void *src,
+                                long long stride, int n, csdr::DcBlank *blank);
 }

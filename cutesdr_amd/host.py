@@ -1576,3 +1576,88 @@ class SeqCheckBatch(_Obj):
         v = d.download(np.uint8, 20 * n)
         d.free()
         return v[:8 * n].view(np.int64).copy(), v[8 * n:16 * n].view(np.int64).copy(), v[16 * n:].view(np.int32).copy()
+
+
+class SpurCalBatch(_Obj):
+    """C copies of CSdrInterface's NCO-spur state (interface/sdrinterface.cpp:791-848: ManageNCOSpurOffsets,
+    NcoSpurCalibrate), one per receiver on the device: offsets, count and the active flag, commanded like the reference
+    and advanced over the datagrams or rows of a put while a receiver calibrates.  dc_ptr is a d_dc for unpack and
+    display calls."""
+    _destroy = "csdr_spurcal_batch_destroy"
+
+    def __init__(self, channels, device=0):
+        self.channels, self.device = int(channels), device
+        self.h = check_ptr(lib().csdr_spurcal_batch_create(device, self.channels), "csdr_spurcal_batch_create")
+
+    @property
+    def dc_ptr(self):
+        """device pointer to the offsets, float64 [channels, 2]"""
+        return int(check_ptr(lib().csdr_spurcal_batch_dc(self.h), "csdr_spurcal_batch_dc"))
+
+    def set(self, offset_i, offset_q, channel=-1):
+        """NCOSPUR_CMD_SET; channel < 0: every receiver"""
+        check(lib().csdr_spurcal_batch_set(self.h, channel, float(offset_i), float(offset_q)), "csdr_spurcal_batch_set")
+
+    def start_cal(self, channel=-1):
+        """NCOSPUR_CMD_STARTCAL; channel < 0: every receiver"""
+        check(lib().csdr_spurcal_batch_start_cal(self.h, channel), "csdr_spurcal_batch_start_cal")
+
+    def read(self, channel):
+        """NCOSPUR_CMD_READ: (offset_i, offset_q); stops a running calibration, as the reference does"""
+        i, q = C.c_double(), C.c_double()
+        check(lib().csdr_spurcal_batch_read(self.h, channel, *[C.cast(C.byref(x), C.c_void_p) for x in (i, q)]),
+              "csdr_spurcal_batch_read")
+        return i.value, q.value
+
+    def get_state(self, channel):
+        """(offset_i, offset_q, count, active) of one receiver, nothing touched; waits for the object's last call only"""
+        i, q, n, a = C.c_double(), C.c_double(), C.c_int(), C.c_int()
+        check(lib().csdr_spurcal_batch_get_state(self.h, channel, *[C.cast(C.byref(x), C.c_void_p) for x in (i, q, n, a)]),
+              "csdr_spurcal_batch_get_state")
+        return i.value, q.value, n.value, bool(a.value)
+
+    def put_packets_ptr(self, d_packets, npackets, pkt_len, stream=None):
+        """the datagrams [channels][npackets][pkt_len] on the device; asynchronous on stream"""
+        check(lib().csdr_spurcal_batch_put_packets(self.h, C.c_void_p(d_packets), npackets, pkt_len,
+                                                   C.c_void_p(stream) if stream else None), "csdr_spurcal_batch_put_packets")
+
+    def put_stream_ptr(self, d_in, in_stride, n, call_len, stream=None):
+        """n samples of every row of complex fp32 [channels][in_stride], arriving as reference calls of call_len samples"""
+        check(lib().csdr_spurcal_batch_put_stream(self.h, C.c_void_p(d_in), in_stride, n, call_len,
+                                                  C.c_void_p(stream) if stream else None), "csdr_spurcal_batch_put_stream")
+
+    def put_packets_blanked_ptr(self, demod, d_packets, npackets, pkt_len, stream=None):
+        """behind csdr_demod_batch_process_packets with a blanker on (d_packets, npackets, pkt_len): what it handed over"""
+        check(lib().csdr_spurcal_batch_put_packets_blanked(self.h, demod.h, C.c_void_p(d_packets), npackets, pkt_len,
+                                                           C.c_void_p(stream) if stream else None),
+              "csdr_spurcal_batch_put_packets_blanked")
+
+    def put_stream_blanked_ptr(self, demod, d_in, in_stride, n, call_len, stream=None):
+        """behind csdr_demod_batch_process_blanked on (d_in, in_stride, n)"""
+        check(lib().csdr_spurcal_batch_put_stream_blanked(self.h, demod.h, C.c_void_p(d_in), in_stride, n, call_len,
+                                                          C.c_void_p(stream) if stream else None),
+              "csdr_spurcal_batch_put_stream_blanked")
+
+    def put_packets(self, raw, pkt_len=None):
+        """raw uint8 [channels, npackets, pkt_len] (host): uploaded, put, waited for"""
+        raw = np.ascontiguousarray(raw, dtype=np.uint8)
+        assert raw.ndim == 3 and raw.shape[0] == self.channels
+        dp = DeviceBuffer(max(raw.nbytes, 4), self.device)
+        dp.upload(raw)
+        try:
+            self.put_packets_ptr(dp.ptr, raw.shape[1], pkt_len or raw.shape[2])
+            sync(self.device)
+        finally:
+            dp.free()
+
+    def put_stream(self, x, call_len):
+        """x complex [channels, n] (host): uploaded, put, waited for"""
+        x = np.ascontiguousarray(x, dtype=np.complex64)
+        assert x.ndim == 2 and x.shape[0] == self.channels
+        din = DeviceBuffer(max(x.nbytes, 8), self.device)
+        din.upload(x)
+        try:
+            self.put_stream_ptr(din.ptr, x.shape[1], x.shape[1], call_len)
+            sync(self.device)
+        finally:
+            din.free()

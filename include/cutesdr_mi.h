@@ -494,11 +494,11 @@ int csdr_fft_batch_get_waterfall_all(csdr_fft_batch *f, int max_w, double max_db
  * With the blanker on, the reference's display sees the blanked, delayed samples (:884 runs in place first):
  * csdr_fft_batch_put_display_stream_blanked / _packets_blanked below give that picture behind a blanked chain call,
  * from the mask the call left -- no second blanker pass.
- * Out of scope: the SPUR_CAL_MAXSAMPLES bookkeeping of NcoSpurCalibrate (the host keeps m_NcoSpurCalCount); shard forms
- * (of the plain and of the blanked pair); spur calibration on blanked samples -- the reference calibrates behind the
- * blanker (:886), csdr_ingest_spurcal* see the unblanked input: while NcoSpurCalibrate is active (the first
- * SPUR_CAL_MAXSAMPLES samples after a start) a host either accepts that estimate -- it differs by the blanked samples'
- * share of the running mean -- or runs csdr_noiseproc_batch_process into rows of its own and calibrates on those. */
+ * The SPUR_CAL_MAXSAMPLES bookkeeping of NcoSpurCalibrate and its commands, per receiver on the device, are
+ * csdr_spurcal_batch_* below: its csdr_spurcal_batch_dc() is a d_dc for these calls.  The reference calibrates behind
+ * the blanker (:886); csdr_spurcal_batch_put_*_blanked see those samples from the mask of the chain call, as the blanked
+ * display pair does, while the stateless csdr_ingest_spurcal* see the input they are handed.
+ * Out of scope: shard forms (of the plain and of the blanked pair). */
 /* SetMaxDisplayRate (sdrinterface.h:112-114): skip value = (int)(sample_rate / (size * max_display_rate)), counter 0.
  * gated != 0 turns on the m_ScreenUpateFinished handshake: after a used frame, none is used until
  * csdr_fft_batch_screen_update_done.  Until this is called the skip value is 0 (every frame) and the gate is off.
@@ -1006,6 +1006,70 @@ int csdr_seqcheck_batch_reset(csdr_seqcheck_batch *s, int channel);   /* and las
 int csdr_seqcheck_batch_get(csdr_seqcheck_batch *s, int channel, long long *missed, long long *events, int *first_gap, int *last);
 /* every receiver's into device arrays [channels] of the caller's (any may be NULL) */
 int csdr_seqcheck_batch_get_all(csdr_seqcheck_batch *s, long long *d_missed, long long *d_events, int *d_first_gap, void *stream);
+
+/* --------------------------------------------------------------------------------------
+ * Batch NCO-spur calibration: C independent copies of CSdrInterface's NCO-spur state (reference
+ * interface/sdrinterface.cpp:791-824 ManageNCOSpurOffsets, :829-848 NcoSpurCalibrate, :886-887 its call behind the
+ * in-place blanker of :884), one per receiver, held on the device.  Per receiver: m_NCOSpurOffsetI / Q (doubles, 0
+ * at create), m_NcoSpurCalCount and m_NcoSpurCalActive (0, false).  The offsets lie in a [channels][2] array of doubles,
+ * csdr_spurcal_batch_dc(): the d_dc of csdr_ingest_unpack and of the four csdr_fft_batch_put_display_* calls.
+ *
+ * Commands (:791-824).  Every one first clears `active` (:793) -- a read too, which so stops a running calibration, as in
+ * the reference.  channel -1 addresses every receiver (set, start_cal).
+ *   set(i, q)   NCOSPUR_CMD_SET (:796-803).  StartSdr's NetSDR branch (:566-568) is set(0, 0).
+ *   start_cal   NCOSPUR_CMD_STARTCAL (:804-812): an offset > 10.0 or < -10.0 becomes 0, each on its own; count = 0;
+ *               active = true.  StartSdr's SDR-14 / SDR-IQ branch (:587) is start_cal.
+ *   read        NCOSPUR_CMD_READ (:813-820): the offsets.
+ *   get_state   no command of the reference's: offsets, count and active as they are, nothing touched (status lines, tests).
+ *
+ * Puts.  One reference call is one datagram (interface/netiobase.cpp:583, :593: 480 or 512 doubles).  On an active
+ * receiver with count < SPUR_CAL_MAXSAMPLES (300000) the recurrence offset = (1 - 1/100000) offset + (1/100000) x runs
+ * over the whole datagram (:833-840) and count += Length / 4 (:841: 120 or 128); on an active one with count >= 300000
+ * the datagram clears `active` and nothing else (:843-847); an inactive receiver's offsets do not change by a bit.  So a
+ * put of npackets datagrams on a receiver that arrives active with count c0 < 300000 runs the recurrence over the first
+ * u = min(npackets, ceil((300000 - c0) / q)) datagrams, q = samples per datagram / 2; count = c0 + u q; active ends
+ * false exactly when u < npackets (a put that ends on the limit leaves it true until the next datagram arrives).
+ * 24 bit from 0: u = 2500, count 300000.  16 bit: u = 2344, count 300032.
+ *   put_packets          the datagrams, decoded in the load
+ *   put_stream           fp32 rows; call_len is the reference call's length in complex samples (call k covers samples
+ *                        [k call_len, ...); a short last call of r samples adds (2 r) / 4 to count)
+ *   put_packets_blanked  what the blanker of b's last blanked chain call handed over (:884), from that call's mask
+ *   put_stream_blanked   the same on rows
+ * The blanked pair has the sample rule, the contract and the refusals of csdr_fft_batch_put_display_*_blanked: right
+ * behind that chain call, same stream, same buffer / count / packet length or stride, before the next call on b, same
+ * width and device, strict or pipelined; CSDR_ESTATE / CSDR_EINVAL otherwise, nothing changed.  Datagram forms: pkt_len
+ * 1028 or 1444, 4-byte aligned, below 2 GiB per channel; rows 8-byte aligned, in_stride >= n, call_len >= 1.  A put with
+ * a count of 0 is legal.  The same samples give the same doubles whichever of the four forms delivered them.
+ *
+ * Ordering.  Puts are asynchronous on `stream`; commands are small launches on a stream of the object's own.  Each is
+ * ordered behind the object's call before it by an event, so commands and puts take effect in the order they were issued
+ * whatever their streams, and commands issued between two puts apply, in order, before the later put's first datagram
+ * (set(50, -3) then start_cal leaves I = 0, Q = -3, active).  The host waits in read and get_state only.  A display or
+ * unpack call that must see a command's offsets goes behind a put on its stream -- an empty one (count 0) will do: it
+ * only puts what was commanded in front of that stream.
+ *
+ * Out of scope: per-datagram offsets in the display -- a display call subtracts the offsets as they stand after the put
+ * from all of the put's samples, where the reference subtracts them as they stand at each datagram (the display stream
+ * with csdr_ingest_spurcal* works the same way); m_Running; shard forms; the limit as a parameter.
+ * -------------------------------------------------------------------------------------- */
+typedef struct csdr_spurcal_batch csdr_spurcal_batch;
+/* NULL without a HIP device (no CPU fallback); channels >= 1 */
+csdr_spurcal_batch *csdr_spurcal_batch_create(int device, int channels);
+void csdr_spurcal_batch_destroy(csdr_spurcal_batch *s);
+int csdr_spurcal_batch_set(csdr_spurcal_batch *s, int channel, double offset_i, double offset_q);   /* :796-803 */
+int csdr_spurcal_batch_start_cal(csdr_spurcal_batch *s, int channel);                                /* :804-812 */
+int csdr_spurcal_batch_read(csdr_spurcal_batch *s, int channel, double *offset_i, double *offset_q); /* :813-820, :793 */
+int csdr_spurcal_batch_get_state(csdr_spurcal_batch *s, int channel, double *offset_i, double *offset_q, int *count, int *active);
+/* the offsets on the device, [channels][2] doubles (I, Q); valid until destroy; NULL for a NULL handle */
+const double *csdr_spurcal_batch_dc(csdr_spurcal_batch *s);
+/* :886-887 with :829-848 over the datagrams / rows of one call, every receiver */
+int csdr_spurcal_batch_put_packets(csdr_spurcal_batch *s, const void *d_packets, int npackets, int pkt_len, void *stream);
+int csdr_spurcal_batch_put_stream(csdr_spurcal_batch *s, const float *d_in, long long in_stride, int n, int call_len, void *stream);
+/* ... behind :884 */
+int csdr_spurcal_batch_put_packets_blanked(csdr_spurcal_batch *s, csdr_demod_batch *b, const void *d_packets, int npackets,
+                                           int pkt_len, void *stream);
+int csdr_spurcal_batch_put_stream_blanked(csdr_spurcal_batch *s, csdr_demod_batch *b, const float *d_in, long long in_stride,
+                                          int n, int call_len, void *stream);
 
 #ifdef __cplusplus
 }
