@@ -53,6 +53,20 @@ static int fft_read(csdr_fft_batch *f, void *dst, const void *src, size_t bytes)
     return CSDR_OK;
 }
 
+// a device buffer that only grows, to at least `need` elements: the stream's work on the old one ends before it goes
+template <class E>
+static hipError_t fft_grow(E *&buf, size_t &cap, size_t need, hipStream_t st)
+{
+    if (need <= cap) return hipSuccess;
+    hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return e;
+    if (buf) (void)hipFree(buf);
+    buf = nullptr; cap = 0;
+    e = hipMalloc((void **)&buf, need * sizeof(E));
+    if (e == hipSuccess) cap = need;
+    return e;
+}
+
 static void fft_free_dev(csdr_fft_batch *f)
 {
     float **ps[] = {&f->d_win, &f->d_tw1, &f->d_tw2, &f->d_sum, &f->d_pwr, &f->d_ave, &f->d_work, &f->d_carry};
@@ -201,21 +215,15 @@ static int fft_put_frames(csdr_fft_batch *f, const float *d_in, long long in_str
     // rounds, and a workgroup's start -- tables, window, sums, the first frame's latency -- costs five frames' time:
     // 0.39 ms for 256 channels x 32 frames against 0.33; 8192 points -2 %.)
     a.nparts = 1; a.part = nullptr; a.alpha = nullptr;
+    const int l2 = log2_of(f->size);
     {
-        const int l2n = log2_of(f->size);
-        const long per_cu = l2n <= 12 ? 4 : (l2n == 13 ? 2 : 1);
-        const long slots = (l2n >= 11 && l2n <= 14) ? 256 * per_cu : 1024;
+        const long per_cu = l2 <= 12 ? 4 : (l2 == 13 ? 2 : 1);
+        const long slots = (l2 >= 11 && l2 <= 14) ? 256 * per_cu : 1024;
         long np = (slots + f->channels - 1) / f->channels;
         if (np > nframes / 8) np = nframes / 8;
         if (np > 1) {
             const size_t need = (size_t)f->channels * np * f->size + (size_t)f->channels * (np + 1);   // + the group weights
-            if (need > f->part_cap) {
-                CSDR_HIP(hipStreamSynchronize((hipStream_t)stream));
-                if (f->d_part) (void)hipFree(f->d_part);
-                f->d_part = nullptr; f->part_cap = 0;
-                CSDR_HIP(hipMalloc((void **)&f->d_part, need * 4));
-                f->part_cap = need;
-            }
+            CSDR_HIP(fft_grow(f->d_part, f->part_cap, need, (hipStream_t)stream));
             a.nparts = (int)np; a.part = f->d_part;
             a.alpha = f->d_part + (size_t)f->channels * np * f->size;
         }
@@ -227,7 +235,6 @@ static int fft_put_frames(csdr_fft_batch *f, const float *d_in, long long in_str
     const DcBlank *blank = src ? src->blank : nullptr;
     a.nb_mask = blank ? blank->mask : nullptr; a.nb_mask_stride = blank ? blank->mask_stride : 0;
     a.nb_state = blank ? (const NbChan *)blank->state : nullptr;
-    const int l2 = log2_of(f->size);
     if (src) CSDR_HIP(spectrum_stream_launch(l2, a, src->pkt_len, (hipStream_t)stream));
     else if (l2 >= 11 && l2 <= 14) CSDR_HIP(spectrum_launch(l2, a, (hipStream_t)stream));
     else CSDR_HIP(spectrum_generic_launch(l2, a, f->d_work, (hipStream_t)stream));
@@ -280,14 +287,7 @@ static int fft_put_stream(csdr_fft_batch *f, const float *d_in, long long in_str
         int ng = left;
         if (loaders)                                    // (unblanked: the one frame that begins in the carry)
             for (ng = 1; ng < left && start + ng * p.step < first_loaded; ) ng++;
-        const size_t need = (size_t)f->channels * ng * N * 2;
-        if (need > f->stage_cap) {
-            CSDR_HIP(hipStreamSynchronize(st));
-            if (f->d_stage) (void)hipFree(f->d_stage);
-            f->d_stage = nullptr; f->stage_cap = 0;
-            CSDR_HIP(hipMalloc((void **)&f->d_stage, need * 4));
-            f->stage_cap = need;
-        }
+        CSDR_HIP(fft_grow(f->d_stage, f->stage_cap, (size_t)f->channels * ng * N * 2, st));
         CSDR_HIP(display_gather_launch(a, start, p.step, ng, N, f->d_stage, st));
         const int rc = fft_put_frames(f, f->d_stage, (long long)ng * N, ng, stream);
         if (rc) return rc;
@@ -338,14 +338,20 @@ int csdr_fft_batch_put_display_stream(csdr_fft_batch *f, const float *d_in, long
     if ((uintptr_t)d_in & 7) return fail(CSDR_EINVAL, "d_in must be 8-byte aligned");
     return fft_put_stream(f, d_in, in_stride, WireIn{nullptr, 0, 0, 0}, n, d_dc, stream);
 }
-int csdr_fft_batch_put_display_packets(csdr_fft_batch *f, const void *d_packets, int npackets, int pkt_len,
-                                       const double *d_dc, void *stream)
-{   // the datagram rules of csdr_demod_batch_process_packets
-    if (!f || !d_packets || npackets < 0) return fail(CSDR_EINVAL, "bad argument");
+// the datagram rules of csdr_demod_batch_process_packets: the samples per datagram, or the error
+static int fft_datagram_samples(bool handles, const void *d_packets, int npackets, int pkt_len)
+{
+    if (!handles || !d_packets || npackets < 0) return fail(CSDR_EINVAL, "bad argument");
     if (pkt_len != 1028 && pkt_len != 1444) return fail(CSDR_EINVAL, "packet length %d", pkt_len);
     if ((long)npackets * pkt_len >= (1l << 31)) return fail(CSDR_EINVAL, "a channel's datagrams of one call must stay below 2 GiB");
     if ((uintptr_t)d_packets & 3) return fail(CSDR_EINVAL, "datagram buffer must be 4-byte aligned");
-    const int per = pkt_len == 1444 ? 240 : 256;
+    return pkt_len == 1444 ? 240 : 256;
+}
+int csdr_fft_batch_put_display_packets(csdr_fft_batch *f, const void *d_packets, int npackets, int pkt_len,
+                                       const double *d_dc, void *stream)
+{
+    const int per = fft_datagram_samples(f != nullptr, d_packets, npackets, pkt_len);
+    if (per < 0) return per;
     return fft_put_stream(f, nullptr, 0, WireIn{(const unsigned char *)d_packets, (long)npackets * pkt_len, pkt_len, per},
                           (long long)npackets * per, d_dc, stream);
 }
@@ -368,11 +374,8 @@ int csdr_fft_batch_put_display_stream_blanked(csdr_fft_batch *f, csdr_demod_batc
 int csdr_fft_batch_put_display_packets_blanked(csdr_fft_batch *f, csdr_demod_batch *b, const void *d_packets,
                                                int npackets, int pkt_len, const double *d_dc, void *stream)
 {
-    if (!f || !b || !d_packets || npackets < 0) return fail(CSDR_EINVAL, "bad argument");
-    if (pkt_len != 1028 && pkt_len != 1444) return fail(CSDR_EINVAL, "packet length %d", pkt_len);
-    if ((long)npackets * pkt_len >= (1l << 31)) return fail(CSDR_EINVAL, "a channel's datagrams of one call must stay below 2 GiB");
-    if ((uintptr_t)d_packets & 3) return fail(CSDR_EINVAL, "datagram buffer must be 4-byte aligned");
-    const int per = pkt_len == 1444 ? 240 : 256;
+    const int per = fft_datagram_samples(f && b, d_packets, npackets, pkt_len);
+    if (per < 0) return per;
     DcBlank blank;
     { const int rc = fft_blank_of(f, b, BLANK_CALL_PACKETS, d_packets, pkt_len, npackets * per, &blank); if (rc) return rc; }
     return fft_put_stream(f, nullptr, 0, WireIn{(const unsigned char *)d_packets, (long)npackets * pkt_len, pkt_len, per},
@@ -488,13 +491,7 @@ int csdr_fft_batch_get_waterfall_all(csdr_fft_batch *f, int max_w, double max_db
     if (!device_ok(f->device)) return CSDR_EHIP;
     if (max_w == 0) return CSDR_OK;
     const size_t need = (size_t)f->channels * max_w;
-    if (need > f->scr_cap) {                             // the levels of the line, [channels][max_w]
-        CSDR_HIP(hipStreamSynchronize((hipStream_t)stream));
-        if (f->d_scr) (void)hipFree(f->d_scr);
-        f->d_scr = nullptr; f->scr_cap = 0;
-        CSDR_HIP(hipMalloc((void **)&f->d_scr, need * sizeof(int)));
-        f->scr_cap = need;
-    }
+    CSDR_HIP(fft_grow(f->d_scr, f->scr_cap, need, (hipStream_t)stream));   // the levels of the line, [channels][max_w]
     CSDR_HIP(hipMemsetAsync(f->d_scr, 0xff, need * sizeof(int), (hipStream_t)stream));     // -1: not touched
     int rc = csdr_fft_batch_get_screen_all(f, 255, max_w, max_db, min_db, start_hz, stop_hz, f->d_scr, max_w, d_overload, stream);
     if (rc < 0) return rc;

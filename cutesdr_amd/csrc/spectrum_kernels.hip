@@ -3,10 +3,17 @@
 // Replaces CFft::PutInDisplayFFT (reference dsp/fft.cpp:267-288: Hann*2 window, I/Q swap, forward
 // transform) together with the tail of CFft::CpxFFT (:562-589: |X|^2, running mean over AveSize
 // frames, log10, fft-shifted into display order), and CFft::FwdFFT / RevFFT (:416-426).
-// One workgroup of N/32 threads per channel walks that channel's frames in order (the running
-// mean makes frames sequential); the transform is a three-pass decimation-in-time FFT with the FMA
-// butterflies of the overlap-save kernel (fft_core.hpp), its output is scattered straight
-// into display order.  8 B in + 4 B out per bin.
+// One workgroup per channel (or frame group) walks its frames in order (the running mean makes frames sequential);
+// the transform is a three-pass decimation-in-time FFT with the FMA butterflies of the overlap-save kernel
+// (fft_core.hpp), its output is scattered straight into display order.  8 B in + 4 B out per bin.
+// The file in the order it reads:
+//   frame loaders      where sample i of frame f comes from: rows, rows + DC, datagrams, each behind a blanker's mask
+//   transforms         Passes32 (16384 points, 32 per thread) and Wide16<PassB...> (2048 / 4096 / 8192, 16 per thread:
+//                      passes A and C and the fence between B and C once, pass B per size)
+//   spectrum_frames    THE frame loop: prologue, frame load with window and overload test, counters, running sum,
+//                      epilogue with the display-order scatter -- each rule once, for every transform and loader
+//   the kernels        spectrum_kernel<14>, spectrum8 / 16 / 32_kernel: launch bounds around spectrum_frames
+//   fft_plain_kernel, the frame-group combine, and the launchers (one size switch, bounded by the loader's largest size)
 #define CSDR_FMA_BFLY 1          // FMA-form decimation-in-time butterflies (fft_core.hpp)
 #define CSDR_PLAIN_CONST_FMA 1
 #include "launch_once.hpp"
@@ -111,364 +118,123 @@ struct BlankedLoad {
 };
 
 
-#ifndef CSDR_SPEC_WAVES
-#define CSDR_SPEC_WAVES 1
-#endif
-template <int LOG2N, class Ld = RowLoad>
-__global__ __launch_bounds__(SpecCfg<LOG2N>::T) __attribute__((amdgpu_waves_per_eu(CSDR_SPEC_WAVES)))
-void spectrum_kernel(SpectrumArgs a)
-{
+// ---- the transforms.  What the frame loop (spectrum_frames, below) asks of a transform type X:
+//   N, T, P, LDS_BYTES    points, threads, points per thread (N = T P) and the workgroup's LDS image
+//   PREFETCH              whether the samples of frame f+1 are fetched while frame f goes through its transform
+//   X(a, lds), settle()   loads its resident twiddles; what it computes from them, once the prologue's loads are issued
+//                         (in front of them it would wait for its own load first: a memory latency per workgroup)
+//   sample(q), slot(q)    which sample of a frame the thread's q-th point is, and the place in x[] it goes to
+//   keep_window, window   the window value of point q: kept from the start, or read when it is used
+//   run(x, lds)           the transform (its first barrier keeps it behind the previous frame's last pass)
+//   bin0(t)               the bin that x[0] of thread t holds afterwards; x[r] holds bin0 + T r
+
+// 16384 points as 512 threads x 32 points: the three passes of spectrum_passes.hpp, their inner twiddles in LDS behind
+// the data.  (2048 ... 8192 points ran here too until the sixteen-point kernels below took them over: round 4.)
+template <int LOG2N>
+struct Passes32 {
+    static_assert(LOG2N == 14, "what follows is settled for 16384 points: a smaller size would want the prefetch back");
     using Cfg = SpecCfg<LOG2N>;
-    constexpr int N = Cfg::N, T = Cfg::T, R0 = Cfg::R0, G = Cfg::G;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    v2f *lds = reinterpret_cast<v2f *>(smem_raw);
-    v2f *tw2 = lds + Cfg::LDS_DATA;
-    // With nparts > 1 the frames of a channel are cut into nparts groups, one workgroup each: the
-    // running sum is the linear map sum <- alpha_f sum + p_f, so a group accumulates its frames from
-    // zero into `part` and spectrum_combine_kernel folds the groups in order.
-    const int t = threadIdx.x, ch = blockIdx.x / a.nparts, part = blockIdx.x % a.nparts;
-    const int f0 = (int)((long)a.nframes * part / a.nparts), f1 = (int)((long)a.nframes * (part + 1) / a.nparts);
-    for (int i = t; i < 1024; i += T) tw2[i] = reinterpret_cast<const v2f *>(a.tw2)[i];
-    v2f w1[G];
+    static constexpr int N = Cfg::N, T = Cfg::T, P = 32, LDS_BYTES = Cfg::LDS_BYTES;
+    // No prefetch: a workgroup is 512 threads here, two waves per SIMD and so at most 256 registers per wave; with the
+    // prefetched frame on top of the points and the running sums the kernel spilled 80 of them -- 324 bytes of scratch
+    // per lane -- and ran at 1.5 TB/s; the second wave of the SIMD hides the loads instead (round 4).  The window is
+    // read per frame for the same reason.
+    static constexpr bool PREFETCH = false;
+    const int t;
+    v2f *tw2;
+    v2f w1[Cfg::G];
+    __device__ __forceinline__ Passes32(const SpectrumArgs &a, v2f *lds) : t(threadIdx.x), tw2(lds + Cfg::LDS_DATA)
+    {
+        for (int i = t; i < 1024; i += T) tw2[i] = reinterpret_cast<const v2f *>(a.tw2)[i];
 #pragma unroll
-    for (int e = 0; e < G; e++) w1[e] = reinterpret_cast<const v2f *>(a.tw1)[Cfg::col(t, e)];
-    const Ld ld(a, ch);
-    float *sum = a.sum + (long)ch * N, *pwr = a.pwr + (long)ch * N, *ave = a.ave + (long)ch * N;
-    int ave_count = a.counters[2 * ch], total = a.counters[2 * ch + 1];
-    total += f0;                                              // counters at this group's first frame
-    ave_count = ave_count + f0 < a.ave_size ? ave_count + f0 : (ave_count > a.ave_size ? ave_count : a.ave_size);
-    int over = 0;
-    // every thread owns the same 32 bins in every frame: the running sum and mean stay in registers
-    // for the whole call, only the last frame's bels are written
-    int tt = t;
-    asm volatile("" : "+v"(tt));              // keep the scattered addresses out of LICM's hands
-    const int k0 = tt >> 5, k1 = tt & 31;
-    float sm[32];                             // the mean is sum / count: recomputed, not carried
-    static_for<0, 32>([&](auto Rr) {
-        constexpr int r = Rr.value, k2 = r;
-        const int j = ((k0 + R0 * (k1 + 32 * k2)) + N / 2) & (N - 1);     // display order, fft.cpp:564-589
-        sm[r] = a.nparts == 1 ? sum[j] : 0.f;
-    });
-    // the samples of frame f+1 are fetched while frame f goes through its transform (one workgroup has only two
-    // waves and three share a CU: nothing else would hide the HBM latency of a frame's 32 loads per thread)
-    // (not at N = 16384: a workgroup is 512 threads there, two waves per SIMD and so at most 256 registers per wave;
-    // with the prefetched frame on top of the points and the running sums the kernel spilled 80 of them -- 324 bytes
-    // of scratch per lane -- and ran at 1.5 TB/s; the second wave of the SIMD hides the loads instead: round 4)
-    constexpr bool PREFETCH = LOG2N < 14;
-    typename Ld::Raw nxt[PREFETCH ? 32 : 1];
-    auto fetch = [&](int f) {
-        if constexpr (PREFETCH) {
-#pragma unroll
-            for (int e = 0; e < G; e++)
-#pragma unroll
-                for (int n1 = 0; n1 < R0; n1++) nxt[e * R0 + n1] = ld.template fetch<N>(f, 1024 * n1 + Cfg::col(t, e));
-        }
-    };
-    if (f0 < f1) fetch(f0);
-    for (int f = f0; f < f1; f++) {
-        v2f x[32];
-#pragma unroll
-        for (int e = 0; e < G; e++)
-#pragma unroll
-            for (int n1 = 0; n1 < R0; n1++) {
-                const int i = 1024 * n1 + Cfg::col(t, e);
-                v2f s;
-                if constexpr (PREFETCH) s = ld.decode(nxt[e * R0 + n1]); else s = ld.decode(ld.template fetch<N>(f, i));
-                const float w = a.win[i];
-                if (s.x > refc::FFT_OVER_LIMIT_F) over = 1;                     // OVER_LIMIT, fft.cpp:30,275
-                x[e * R0 + n1] = v2f{w * s.y, w * s.x};           // I/Q swapped, fft.cpp:280-281
-            }
-        if (f + 1 < f1) fetch(f + 1);
-        const float prev_count = (float)ave_count;
-        total++;                                                  // CpxFFT counters, fft.cpp:515-517
-        if (ave_count < a.ave_size) ave_count++;
-        fft_fwd_passes<LOG2N>(x, lds, tw2, w1);        // (its own barrier keeps it behind the previous frame's pass C)
-        const float inv_prev = 1.0f / prev_count;      // (one division per frame instead of one per bin, as in spectrum16_kernel)
-        static_for<0, 32>([&](auto Rr) {
-            constexpr int r = Rr.value;
-            const float p = x[r].x * x[r].x + x[r].y * x[r].y;
-            if (total <= a.ave_size) sm[r] = sm[r] + p;
-            else sm[r] = sm[r] - sm[r] * inv_prev + p;            // minus the previous mean (fft.cpp:570-574)
-        });
+        for (int e = 0; e < Cfg::G; e++) w1[e] = reinterpret_cast<const v2f *>(a.tw1)[Cfg::col(t, e)];
     }
-    if (a.nparts > 1) {
-        float *dst = a.part + ((long)ch * a.nparts + part) * N;
-        static_for<0, 32>([&](auto Rr) {
-            constexpr int r = Rr.value, k2 = r;
-            dst[((k0 + R0 * (k1 + 32 * k2)) + N / 2) & (N - 1)] = sm[r];
-        });
-    } else if (a.nframes > 0) {
-        static_for<0, 32>([&](auto Rr) {
-            constexpr int r = Rr.value, k2 = r;
-            const int j = ((k0 + R0 * (k1 + 32 * k2)) + N / 2) & (N - 1);
-            const float m = sm[r] / (float)ave_count;
-            sum[j] = sm[r]; pwr[j] = m;
-            ave[j] = (float)((double)log10f(m + a.kc) + a.kb);
-            if constexpr ((r & 7) == 7) __builtin_amdgcn_sched_barrier(0);
-        });
-    }
-    if (t == 0 && a.nparts == 1) { a.counters[2 * ch] = ave_count; a.counters[2 * ch + 1] = total; }
-    if (over) a.overload[ch] = 1;
-}
+    __device__ __forceinline__ void settle() {}
+    __device__ __forceinline__ int sample(int q) const { return 1024 * (q % Cfg::R0) + Cfg::col(t, q / Cfg::R0); }
+    static __device__ constexpr int slot(int q) { return q; }
+    __device__ __forceinline__ void keep_window(const float *, int) {}
+    __device__ __forceinline__ float window(const float *win, int q) const { return win[sample(q)]; }
+    __device__ __forceinline__ void run(v2f (&x)[32], v2f *lds) const { fft_fwd_passes<LOG2N>(x, lds, tw2, w1); }
+    static __device__ __forceinline__ int bin0(int t) { return (t >> 5) + Cfg::R0 * (t & 31); }   // (32 R0 = T)
+};
 
-// ---- the 4096-point display spectrum (BASELINE config C1) as 256 threads x 16 points -----------------------------
-// spectrum_kernel<12> holds 32 points, the prefetched next frame and 32 running sums per thread: 300 registers, ONE
-// wave per SIMD, its vector unit 42 % busy with nothing to overlap a wave's own LDS and memory waits.  Sixteen points
-// per thread fit two waves per SIMD.  N = 16 x 16 x 16, three radix-16 DIT passes in registers:
-//   A  thread t: samples 256 a + t (one coalesced 8-byte load per point), DFT over a, twiddle W_N^{t ka}   -> (ka, t)
-//   B  thread (ka, c): points (ka, 16 b + c), DFT over b, twiddle W_256^{c kb}, back to the same 16 places
-//   C  thread (ka, kb): its 16 consecutive points, DFT over c                    -> bin ka + 16 kb + 256 kc
-// B -> C stays inside the quarter-wave that owns ka: no workgroup barrier.  Rows of 16 points are 18 apart in LDS
-// (pass C reads them as 16-byte pieces without bank conflicts).
+// ---- 2048 / 4096 / 8192 points as T = N / 16 threads x 16 points, N = 16 x T/16 x 16 --------------------------------
+// Thirty-two points per thread with the prefetched next frame and 32 running sums are 300 registers: ONE wave per
+// SIMD, its vector unit 42 % busy with nothing to overlap a wave's own LDS and memory waits.  Sixteen points per thread
+// fit two waves per SIMD.  Three DIT passes in registers, n = T a + 16 b + c, B = T/16:
+//   A  thread t: samples T a + t (one coalesced 8-byte load per point), DFT over a, twiddle W_N^{t ka}   -> (ka, t)
+//   B  the B points b of column (ka, c): DFT over b, twiddle W_{16 B}^{c kb}, back to the same places -- what a thread
+//      takes of it is the size's own (PassB2048 / 4096 / 8192)
+//   C  thread t = B ka + kb: its 16 consecutive points, DFT over c                   -> bin ka + 16 kb + T kc
+// B -> C stays inside the B threads that own ka: no workgroup barrier.  Rows of 16 points are 18 apart in LDS (pass C
+// reads them as 16-byte pieces without bank conflicts).
 __device__ __forceinline__ int pad16(int pos) { return pos + ((pos >> 4) << 1); }
-constexpr int SPEC16_LDS = (4096 + 2 * 256) * 8;
-#ifndef CSDR_SPEC16_WAVES
-#define CSDR_SPEC16_WAVES 1
-#endif
-template <class Ld = RowLoad>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CSDR_SPEC16_WAVES)))
-void spectrum16_kernel(SpectrumArgs a)
-{
-    constexpr int N = 4096, T = 256;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    v2f *lds = reinterpret_cast<v2f *>(smem_raw);
-    const int t = threadIdx.x, ch = blockIdx.x / a.nparts, part = blockIdx.x % a.nparts;
-    const int f0 = (int)((long)a.nframes * part / a.nparts), f1 = (int)((long)a.nframes * (part + 1) / a.nparts);
-    const v2f *tw1 = reinterpret_cast<const v2f *>(a.tw1);           // W_N^n, n < 1024
-    const v2f wA = tw1[t], wB = tw1[16 * (t & 15)];                  // W_N^t and W_256^c
-    const Ld ld(a, ch);
-    float *sum = a.sum + (long)ch * N, *pwr = a.pwr + (long)ch * N, *ave = a.ave + (long)ch * N;
-    int ave_count = a.counters[2 * ch], total = a.counters[2 * ch + 1];
-    total += f0;                                              // counters at this group's first frame
-    ave_count = ave_count + f0 < a.ave_size ? ave_count + f0 : (ave_count > a.ave_size ? ave_count : a.ave_size);
-    int over = 0;
-    int tt = t;
-    asm volatile("" : "+v"(tt));              // keep the scattered addresses out of LICM's hands
-    const int kbin = (tt >> 4) + 16 * (tt & 15);              // this thread's bins: kbin + 256 kc
-    float sm[16], wn[16];
-    static_for<0, 16>([&](auto Rr) {
-        constexpr int r = Rr.value;
-        sm[r] = a.nparts == 1 ? sum[((kbin + 256 * r) + N / 2) & (N - 1)] : 0.f;   // display order, fft.cpp:564-589
-        wn[r] = a.win[256 * r + t];
-    });
-    v2f pwA[16];                              // W_N^{t ka}: resident (30 registers; pass B's are recomputed per frame)
-    twiddle_powers<16>(wA, pwA);
-    typename Ld::Raw nxt[16];
-    auto fetch = [&](int f) {
-#pragma unroll
-        for (int q = 0; q < 16; q++) nxt[q] = ld.template fetch<N>(f, t + 256 * q);
-    };
-    if (f0 < f1) fetch(f0);
-    for (int f = f0; f < f1; f++) {
-        v2f x[16];
-        static_for<0, 16>([&](auto Q) {
-            constexpr int q = Q.value;
-            const v2f s_ = ld.decode(nxt[q]);
-            if (s_.x > refc::FFT_OVER_LIMIT_F) over = 1;                        // OVER_LIMIT, fft.cpp:30,275
-            x[bitrev<16>(q)] = v2f{wn[q] * s_.y, wn[q] * s_.x};    // I/Q swapped, fft.cpp:280-281
-        });
-        if (f + 1 < f1) fetch(f + 1);
-        const float prev_count = (float)ave_count;
-        total++;                                                  // CpxFFT counters, fft.cpp:515-517
-        if (ave_count < a.ave_size) ave_count++;
-        // ---- pass A
-        dft_dit<16, +1>(x);
-        static_for<1, 16>([&](auto K) { x[K.value] = cmul(x[K.value], pwA[K.value]); });
-        __syncthreads();                       // the previous frame's pass C has read its rows
-        static_for<0, 16>([&](auto K) { lds[pad16(256 * K.value + t)] = x[K.value]; });
-        __syncthreads();
-        // ---- pass B: (ka, c) = (t >> 4, t & 15)
-        {
-            v2f *col = lds + pad16(256 * (t >> 4)) + (t & 15);                   // point b at col[18 b]
-            static_for<0, 16>([&](auto B) { x[bitrev<16>(B.value)] = lds_ld8(col + 18 * B.value); });
-            dft_dit<16, +1>(x);
-            v2f pw[16];
-            twiddle_powers<16>(opaque(wB), pw);
-            static_for<1, 16>([&](auto K) { x[K.value] = cmul(x[K.value], pw[K.value]); });
-            static_for<0, 16>([&](auto K) { lds_st8(col + 18 * K.value, x[K.value]); });
-        }
-        // B -> C stays inside the sixteen threads that own ka
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // ---- pass C: the 16 consecutive points of row t
-        {
-            const v2f *row = lds + 18 * t;
-            static_for<0, 8>([&](auto J) {
-                const v4f v = *reinterpret_cast<const v4f *>(row + 2 * J.value);
-                x[bitrev<16>(2 * J.value)] = v2f{v.x, v.y};
-                x[bitrev<16>(2 * J.value + 1)] = v2f{v.z, v.w};
-            });
-            dft_dit<16, +1>(x);
-        }
-        const float inv_prev = 1.0f / prev_count;                 // (one division per frame instead of one per bin: -10 %)
-        static_for<0, 16>([&](auto Rr) {
-            constexpr int r = Rr.value;
-            const float p = x[r].x * x[r].x + x[r].y * x[r].y;
-            if (total <= a.ave_size) sm[r] = sm[r] + p;
-            else sm[r] = sm[r] - sm[r] * inv_prev + p;            // minus the previous mean (fft.cpp:570-574)
-        });
-    }
-    if (a.nparts > 1) {
-        float *dst = a.part + ((long)ch * a.nparts + part) * N;
-        static_for<0, 16>([&](auto Rr) { dst[((kbin + 256 * Rr.value) + N / 2) & (N - 1)] = sm[Rr.value]; });
-    } else if (a.nframes > 0) {
-        static_for<0, 16>([&](auto Rr) {
-            constexpr int r = Rr.value;
-            const int j = ((kbin + 256 * r) + N / 2) & (N - 1);
-            const float m = sm[r] / (float)ave_count;
-            sum[j] = sm[r]; pwr[j] = m;
-            ave[j] = (float)((double)log10f(m + a.kc) + a.kb);
-        });
-    }
-    if (t == 0 && a.nparts == 1) { a.counters[2 * ch] = ave_count; a.counters[2 * ch + 1] = total; }
-    if (over) a.overload[ch] = 1;
-}
 
-// ---- the 2048-point display spectrum the same way (round 4): 128 threads x 16 points, N = 16 x 8 x 16 ----------------
-// spectrum_kernel<11> is ONE wave of 32 points per thread.  Here: pass A as above (samples 128 a + t), pass B over the
-// eight points b of a COLUMN PAIR per thread (thread (ka, c pair): 2 x 8 points, twiddle W_128^{c kb}), pass C the 16
-// consecutive points of row t = 8 ka + kb -> bin ka + 16 kb + 128 kc.  B -> C inside the eight threads that own ka.
-constexpr int SPEC8_LDS = (2048 + 2 * 128) * 8;
-template <class Ld = RowLoad>
-__global__ __launch_bounds__(128)
-void spectrum8_kernel(SpectrumArgs a)
-{
-    constexpr int N = 2048, T = 128;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    v2f *lds = reinterpret_cast<v2f *>(smem_raw);
-    const int t = threadIdx.x, ch = blockIdx.x / a.nparts, part = blockIdx.x % a.nparts;
-    const int f0 = (int)((long)a.nframes * part / a.nparts), f1 = (int)((long)a.nframes * (part + 1) / a.nparts);
-    const v2f *tw1 = reinterpret_cast<const v2f *>(a.tw1);           // W_N^n, n < 1024
-    const int cp = t & 7;                                             // pass B: columns 2 cp, 2 cp + 1 of ka = t >> 3
-    const v2f wA = tw1[t], wB0 = tw1[16 * (2 * cp)], wB1 = tw1[16 * (2 * cp + 1)];   // W_N^t; W_128^c = W_N^{16 c}
-    const Ld ld(a, ch);
-    float *sum = a.sum + (long)ch * N, *pwr = a.pwr + (long)ch * N, *ave = a.ave + (long)ch * N;
-    int ave_count = a.counters[2 * ch], total = a.counters[2 * ch + 1];
-    total += f0;                                              // counters at this group's first frame
-    ave_count = ave_count + f0 < a.ave_size ? ave_count + f0 : (ave_count > a.ave_size ? ave_count : a.ave_size);
-    int over = 0;
-    int tt = t;
-    asm volatile("" : "+v"(tt));
-    const int kbin = (tt >> 3) + 16 * (tt & 7);               // this thread's bins: kbin + 128 kc
-    float sm[16], wn[16];
-    static_for<0, 16>([&](auto Rr) {
-        constexpr int r = Rr.value;
-        sm[r] = a.nparts == 1 ? sum[((kbin + 128 * r) + N / 2) & (N - 1)] : 0.f;   // display order, fft.cpp:564-589
-        wn[r] = a.win[128 * r + t];
-    });
-    v2f pwA[16];
-    twiddle_powers<16>(wA, pwA);
-    typename Ld::Raw nxt[16];
-    auto fetch = [&](int f) {
-#pragma unroll
-        for (int q = 0; q < 16; q++) nxt[q] = ld.template fetch<N>(f, t + 128 * q);
-    };
-    if (f0 < f1) fetch(f0);
-    for (int f = f0; f < f1; f++) {
-        v2f x[16];
-        static_for<0, 16>([&](auto Q) {
-            constexpr int q = Q.value;
-            const v2f s_ = ld.decode(nxt[q]);
-            if (s_.x > refc::FFT_OVER_LIMIT_F) over = 1;                        // OVER_LIMIT, fft.cpp:30,275
-            x[bitrev<16>(q)] = v2f{wn[q] * s_.y, wn[q] * s_.x};    // I/Q swapped, fft.cpp:280-281
-        });
-        if (f + 1 < f1) fetch(f + 1);
-        const float prev_count = (float)ave_count;
-        total++;                                                  // CpxFFT counters, fft.cpp:515-517
-        if (ave_count < a.ave_size) ave_count++;
-        // ---- pass A
+// 4096: B = 16, thread (ka, c) = (t >> 4, t & 15) takes the whole column, twiddle W_256^{c kb}
+struct PassB4096 {
+    static constexpr int LOG2B = 4, T = 16 << LOG2B;
+    v2f wB;                                                           // W_256^c = W_N^{16 c}
+    __device__ __forceinline__ PassB4096(const v2f *tw1, int t) : wB(tw1[16 * (t & 15)]) {}
+    __device__ __forceinline__ void operator()(v2f (&x)[16], v2f *lds, int t) const
+    {
+        v2f *col = lds + pad16(256 * (t >> 4)) + (t & 15);                   // point b at col[18 b]
+        static_for<0, 16>([&](auto B) { x[bitrev<16>(B.value)] = lds_ld8(col + 18 * B.value); });
         dft_dit<16, +1>(x);
-        static_for<1, 16>([&](auto K) { x[K.value] = cmul(x[K.value], pwA[K.value]); });
-        __syncthreads();                       // the previous frame's pass C has read its rows
-        static_for<0, 16>([&](auto K) { lds[pad16(128 * K.value + t)] = x[K.value]; });
-        __syncthreads();
-        // ---- pass B: (ka, column pair) = (t >> 3, t & 7): point (b, c) at lds[18 (8 ka + b) + c]
-        {
-            v2f *cell = lds + 18 * (8 * (t >> 3)) + 2 * cp;
-            v2f y0[8], y1[8];
-            static_for<0, 8>([&](auto B) {
-                const v4f v = *reinterpret_cast<const v4f *>(cell + 18 * B.value);
-                y0[bitrev<8>(B.value)] = v2f{v.x, v.y}; y1[bitrev<8>(B.value)] = v2f{v.z, v.w};
-            });
-            dft_dit<8, +1>(y0);
-            dft_dit<8, +1>(y1);
-            v2f p0[8], p1[8];
-            twiddle_powers<8>(opaque(wB0), p0);
-            twiddle_powers<8>(opaque(wB1), p1);
-            static_for<0, 8>([&](auto K) {
-                constexpr int k = K.value;
-                if constexpr (k != 0) { y0[k] = cmul(y0[k], p0[k]); y1[k] = cmul(y1[k], p1[k]); }
-                *reinterpret_cast<v4f *>(cell + 18 * k) = v4f{y0[k].x, y0[k].y, y1[k].x, y1[k].y};
-            });
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // ---- pass C: the 16 consecutive points of row t
-        {
-            const v2f *row = lds + 18 * t;
-            static_for<0, 8>([&](auto J) {
-                const v4f v = *reinterpret_cast<const v4f *>(row + 2 * J.value);
-                x[bitrev<16>(2 * J.value)] = v2f{v.x, v.y};
-                x[bitrev<16>(2 * J.value + 1)] = v2f{v.z, v.w};
-            });
-            dft_dit<16, +1>(x);
-        }
-        const float inv_prev = 1.0f / prev_count;
-        static_for<0, 16>([&](auto Rr) {
-            constexpr int r = Rr.value;
-            const float p = x[r].x * x[r].x + x[r].y * x[r].y;
-            if (total <= a.ave_size) sm[r] = sm[r] + p;
-            else sm[r] = sm[r] - sm[r] * inv_prev + p;            // minus the previous mean (fft.cpp:570-574)
-        });
+        v2f pw[16];
+        twiddle_powers<16>(opaque(wB), pw);
+        static_for<1, 16>([&](auto K) { x[K.value] = cmul(x[K.value], pw[K.value]); });
+        static_for<0, 16>([&](auto K) { lds_st8(col + 18 * K.value, x[K.value]); });
     }
-    if (a.nparts > 1) {
-        float *dst = a.part + ((long)ch * a.nparts + part) * N;
-        static_for<0, 16>([&](auto Rr) { dst[((kbin + 128 * Rr.value) + N / 2) & (N - 1)] = sm[Rr.value]; });
-    } else if (a.nframes > 0) {
-        static_for<0, 16>([&](auto Rr) {
-            constexpr int r = Rr.value;
-            const int j = ((kbin + 128 * r) + N / 2) & (N - 1);
-            const float m = sm[r] / (float)ave_count;
-            sum[j] = sm[r]; pwr[j] = m;
-            ave[j] = (float)((double)log10f(m + a.kc) + a.kb);
-        });
-    }
-    if (t == 0 && a.nparts == 1) { a.counters[2 * ch] = ave_count; a.counters[2 * ch + 1] = total; }
-    if (over) a.overload[ch] = 1;
-}
+};
 
-// ---- the 8192-point display spectrum with sixteen points per thread (round 4): 512 threads, N = 16 x 32 x 16 -------------
-// spectrum_kernel<13> is 256 threads x 32 points at 300 registers (2.7 TB/s).  The middle pass has 32 points per column,
-// two threads' worth: the column (ka, c) is split by the PARITY of b over a pair of neighbouring lanes (h = t & 1) --
+// 2048 (round 4): B = 8, the eight points b of a COLUMN PAIR per thread -- thread (ka, c pair) = (t >> 3, t & 7):
+// 2 x 8 points, twiddle W_128^{c kb}; point (b, c) at lds[18 (8 ka + b) + c].  B -> C inside the eight threads that own ka.
+struct PassB2048 {
+    static constexpr int LOG2B = 3, T = 16 << LOG2B;
+    int cp;                                                           // columns 2 cp, 2 cp + 1 of ka = t >> 3
+    v2f wB0, wB1;                                                     // W_128^c = W_N^{16 c}
+    __device__ __forceinline__ PassB2048(const v2f *tw1, int t)
+        : cp(t & 7), wB0(tw1[16 * (2 * cp)]), wB1(tw1[16 * (2 * cp + 1)]) {}
+    __device__ __forceinline__ void operator()(v2f (&)[16], v2f *lds, int t) const
+    {
+        v2f *cell = lds + 18 * (8 * (t >> 3)) + 2 * cp;
+        v2f y0[8], y1[8];
+        static_for<0, 8>([&](auto B) {
+            const v4f v = *reinterpret_cast<const v4f *>(cell + 18 * B.value);
+            y0[bitrev<8>(B.value)] = v2f{v.x, v.y}; y1[bitrev<8>(B.value)] = v2f{v.z, v.w};
+        });
+        dft_dit<8, +1>(y0);
+        dft_dit<8, +1>(y1);
+        v2f p0[8], p1[8];
+        twiddle_powers<8>(opaque(wB0), p0);
+        twiddle_powers<8>(opaque(wB1), p1);
+        static_for<0, 8>([&](auto K) {
+            constexpr int k = K.value;
+            if constexpr (k != 0) { y0[k] = cmul(y0[k], p0[k]); y1[k] = cmul(y1[k], p1[k]); }
+            *reinterpret_cast<v4f *>(cell + 18 * k) = v4f{y0[k].x, y0[k].y, y1[k].x, y1[k].y};
+        });
+    }
+};
+
+// 8192 (round 4): B = 32, two threads' worth.  Thirty-two points per thread would be 256 threads at 300 registers
+// (2.7 TB/s); instead the column (ka, c) is split by the PARITY of b over a pair of neighbouring lanes (h = t & 1) --
 // each does a 16-point DIT over its b = 2 j + h, the odd one applies W_32^{kj}, and the radix-2 butterfly that joins the
 // halves takes the partner's sixteen values over the DPP quad permute (1,0,3,2): no LDS, no barrier.
 //   n = 512 a + 16 b + c     k = ka + 16 kb + 512 kc     kb = kj + 16 h        LDS cell of (ka, x, c): 18 (32 ka + x) + c
-//   A  thread t           : samples 512 a + t, DFT over a, twiddle W_N^{t ka}
 //   B  thread (ka, c, h)  : DFT over b as above, twiddle W_512^{c kb}, back to rows kb of the same columns
-//   C  thread t = 32 ka + kb : its 16 consecutive points, DFT over c                   -> bin ka + 16 kb + 512 kc
 // B -> C inside the half-wave that owns ka.  One workgroup per CU would fit twice (74 KB of LDS); registers allow one.
-constexpr int SPEC32_LDS = (8192 + 2 * 512) * 8;
 __device__ __forceinline__ v2f pair_swap(v2f v)           // the value of lane t ^ 1
 {
     return v2f{__int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v.x), 0xB1, 0xf, 0xf, false)),
                __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v.y), 0xB1, 0xf, 0xf, false))};
 }
-template <class Ld = RowLoad>
-__global__ __launch_bounds__(512)
-void spectrum32_kernel(SpectrumArgs a)
-{
-    constexpr int N = 8192, T = 512;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    v2f *lds = reinterpret_cast<v2f *>(smem_raw);
-    const int t = threadIdx.x, ch = blockIdx.x / a.nparts, part = blockIdx.x % a.nparts;
-    const int f0 = (int)((long)a.nframes * part / a.nparts), f1 = (int)((long)a.nframes * (part + 1) / a.nparts);
-    const v2f *tw1 = reinterpret_cast<const v2f *>(a.tw1);           // W_N^n, n < 1024
-    const int hB = t & 1, cB = (t >> 1) & 15, kaB = t >> 5;          // pass B: (ka, c, h)
-    const v2f wA = tw1[t];                                            // W_N^t
-    const v2f wB = tw1[16 * cB];                                      // W_512^c = W_N^{16 c}
+struct PassB8192 {
+    static constexpr int LOG2B = 5, T = 16 << LOG2B;
+    int hB, cB, kaB;                                                  // (ka, c, h)
+    v2f wB;                                                           // W_512^c = W_N^{16 c}
     v2f wH;                                                           // W_512^{16 c h} = W_32^{c h} = W_N^{256 c h}, c h < 16:
+    __device__ __forceinline__ PassB8192(const v2f *tw1, int t)
+        : hB(t & 1), cB((t >> 1) & 15), kaB(t >> 5), wB(tw1[16 * cB])
     {                                                                 // the table holds an OCTANT of W_N at N = 8192 (W_N^1024 = e^{j pi/4})
         const int m = 256 * cB * hB;                                  // < 4096: up to three eighth turns beyond the table entry
         const v2f v = tw1[m & 1023];
@@ -479,89 +245,143 @@ void spectrum32_kernel(SpectrumArgs a)
         else if (o == 2) wH = v2f{-v.y, v.x};
         else wH = v2f{-r * (v.x + v.y), r * (v.x - v.y)};
     }
+    __device__ __forceinline__ void operator()(v2f (&x)[16], v2f *lds, int) const
+    {
+        v2f *col = lds + 18 * (32 * kaB + hB) + cB;                          // point b = 2 j + h at col[36 j]
+        static_for<0, 16>([&](auto J) { x[bitrev<16>(J.value)] = lds_ld8(col + 36 * J.value); });
+        dft_dit<16, +1>(x);                                                   // Y_h[kj]
+        // the odd half times W_32^{kj} (constants), then the butterfly with the partner lane's half
+        static_for<0, 16>([&](auto K) {
+            constexpr int k = K.value;
+            const v2f w32 = v2f{(float)__builtin_cos(6.283185307179586476925286766559 * k / 32.0),
+                                (float)__builtin_sin(6.283185307179586476925286766559 * k / 32.0)};
+            const v2f mine = hB ? cmul(x[k], w32) : x[k];
+            const v2f other = pair_swap(mine);
+            x[k] = hB ? other - mine : mine + other;          // h = 0: Y0 + w Y1 -> kb = kj;  h = 1: Y0 - w Y1 -> kb = kj + 16
+        });
+        v2f pw[16];
+        twiddle_powers<16>(opaque(wB), pw);                   // W_512^{c kj}
+        static_for<0, 16>([&](auto K) {
+            constexpr int k = K.value;
+            v2f v = x[k];
+            if constexpr (k != 0) v = cmul(v, pw[k]);
+            v = hB ? cmul(v, wH) : v;                         // times W_512^{16 c h}
+            lds_st8(lds + 18 * (32 * kaB + k + 16 * hB) + cB, v);
+        });
+    }
+};
+
+template <class PassB>
+struct Wide16 {
+    static constexpr int T = PassB::T, N = 16 * T, P = 16, LDS_BYTES = (N + 2 * T) * 8;
+    static constexpr bool PREFETCH = true;
+    // W_N^{t ka} stay resident (30 registers) where a thread has them: the 512 threads of 8192 points, at most 256
+    // registers each, recompute them per frame as every size does pass B's
+    static constexpr bool PWA_RESIDENT = T < 512;
+    const int t;
+    const v2f wA;                                                     // W_N^t (tw1: W_N^n, n < 1024)
+    const PassB pass_b;
+    v2f pwA[PWA_RESIDENT ? 16 : 1];
+    float wn[16];
+    __device__ __forceinline__ Wide16(const SpectrumArgs &a, v2f *)
+        : t(threadIdx.x), wA(reinterpret_cast<const v2f *>(a.tw1)[t]), pass_b(reinterpret_cast<const v2f *>(a.tw1), t) {}
+    __device__ __forceinline__ void settle() { if constexpr (PWA_RESIDENT) twiddle_powers<16>(wA, pwA); }
+    __device__ __forceinline__ int sample(int q) const { return t + T * q; }
+    static __device__ constexpr int slot(int q) { return bitrev<16>(q); }
+    __device__ __forceinline__ void keep_window(const float *win, int q) { wn[q] = win[sample(q)]; }
+    __device__ __forceinline__ float window(const float *, int q) const { return wn[q]; }
+    __device__ __forceinline__ void run(v2f (&x)[16], v2f *lds) const
+    {
+        // ---- pass A
+        dft_dit<16, +1>(x);
+        if constexpr (PWA_RESIDENT) {
+            static_for<1, 16>([&](auto K) { x[K.value] = cmul(x[K.value], pwA[K.value]); });
+        } else {
+            v2f pw[16];
+            twiddle_powers<16>(opaque(wA), pw);
+            static_for<1, 16>([&](auto K) { x[K.value] = cmul(x[K.value], pw[K.value]); });
+        }
+        __syncthreads();                       // the previous frame's pass C has read its rows
+        static_for<0, 16>([&](auto K) { lds[pad16(T * K.value + t)] = x[K.value]; });
+        __syncthreads();
+        // ---- pass B
+        pass_b(x, lds, t);
+        // B -> C stays inside the T/16 threads that own ka
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        // ---- pass C: the 16 consecutive points of row t
+        const v2f *row = lds + 18 * t;
+        static_for<0, 8>([&](auto J) {
+            const v4f v = *reinterpret_cast<const v4f *>(row + 2 * J.value);
+            x[bitrev<16>(2 * J.value)] = v2f{v.x, v.y};
+            x[bitrev<16>(2 * J.value + 1)] = v2f{v.z, v.w};
+        });
+        dft_dit<16, +1>(x);
+    }
+    // pass C row t = B ka + kb: bins ka + 16 kb + T kc
+    static __device__ __forceinline__ int bin0(int t) { return (t >> PassB::LOG2B) + 16 * (t & (T / 16 - 1)); }
+};
+
+// ---- the frame loop: one workgroup walks the frames f0 ... f1 of its channel through transform X, loaded by Ld -------
+template <class X, class Ld>
+__device__ __forceinline__ void spectrum_frames(const SpectrumArgs &a)
+{
+    constexpr int N = X::N, P = X::P;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    v2f *lds = reinterpret_cast<v2f *>(smem_raw);
+    // With nparts > 1 the frames of a channel are cut into nparts groups, one workgroup each: the
+    // running sum is the linear map sum <- alpha_f sum + p_f, so a group accumulates its frames from
+    // zero into `part` and spectrum_combine_kernel folds the groups in order.
+    const int t = threadIdx.x, ch = blockIdx.x / a.nparts, part = blockIdx.x % a.nparts;
+    const int f0 = (int)((long)a.nframes * part / a.nparts), f1 = (int)((long)a.nframes * (part + 1) / a.nparts);
+    X xf(a, lds);
     const Ld ld(a, ch);
     float *sum = a.sum + (long)ch * N, *pwr = a.pwr + (long)ch * N, *ave = a.ave + (long)ch * N;
     int ave_count = a.counters[2 * ch], total = a.counters[2 * ch + 1];
     total += f0;                                              // counters at this group's first frame
     ave_count = ave_count + f0 < a.ave_size ? ave_count + f0 : (ave_count > a.ave_size ? ave_count : a.ave_size);
     int over = 0;
+    // every thread owns the same P bins in every frame: the running sum and mean stay in registers
+    // for the whole call, only the last frame's bels are written
     int tt = t;
-    asm volatile("" : "+v"(tt));
-    const int kbin = (tt >> 5) + 16 * (tt & 31);              // pass C row t = 32 ka + kb: bins kbin + 512 kc
-    float sm[16], wn[16];
-    static_for<0, 16>([&](auto Rr) {
+    asm volatile("" : "+v"(tt));              // keep the scattered addresses out of LICM's hands
+    const int bin0 = X::bin0(tt);
+    auto shown = [&](int r) { return (bin0 + (X::T * r + N / 2)) & (N - 1); };     // display order, fft.cpp:564-589
+    float sm[P];                              // the mean is sum / count: recomputed, not carried
+    static_for<0, P>([&](auto Rr) {
         constexpr int r = Rr.value;
-        sm[r] = a.nparts == 1 ? sum[((kbin + 512 * r) + N / 2) & (N - 1)] : 0.f;   // display order, fft.cpp:564-589
-        wn[r] = a.win[512 * r + t];
+        sm[r] = a.nparts == 1 ? sum[shown(r)] : 0.f;
+        xf.keep_window(a.win, r);
     });
-    typename Ld::Raw nxt[16];
+    xf.settle();
+    // the samples of frame f+1 are fetched while frame f goes through its transform (one workgroup has only a few
+    // waves and several share a CU: nothing else would hide the HBM latency of a frame's loads), as raw words
+    typename Ld::Raw nxt[X::PREFETCH ? P : 1];
     auto fetch = [&](int f) {
+        if constexpr (X::PREFETCH) {
 #pragma unroll
-        for (int q = 0; q < 16; q++) nxt[q] = ld.template fetch<N>(f, t + 512 * q);
+            for (int q = 0; q < P; q++) nxt[q] = ld.template fetch<N>(f, xf.sample(q));
+        }
     };
     if (f0 < f1) fetch(f0);
     for (int f = f0; f < f1; f++) {
-        v2f x[16];
-        static_for<0, 16>([&](auto Q) {
+        v2f x[P];
+        static_for<0, P>([&](auto Q) {
             constexpr int q = Q.value;
-            const v2f s_ = ld.decode(nxt[q]);
-            if (s_.x > refc::FFT_OVER_LIMIT_F) over = 1;                        // OVER_LIMIT, fft.cpp:30,275
-            x[bitrev<16>(q)] = v2f{wn[q] * s_.y, wn[q] * s_.x};    // I/Q swapped, fft.cpp:280-281
+            v2f s;
+            if constexpr (X::PREFETCH) s = ld.decode(nxt[q]); else s = ld.decode(ld.template fetch<N>(f, xf.sample(q)));
+            const float w = xf.window(a.win, q);
+            if (s.x > refc::FFT_OVER_LIMIT_F) over = 1;                     // OVER_LIMIT, fft.cpp:30,275
+            x[X::slot(q)] = v2f{w * s.y, w * s.x};                // Hann*2, I/Q swapped, fft.cpp:280-281
         });
         if (f + 1 < f1) fetch(f + 1);
         const float prev_count = (float)ave_count;
         total++;                                                  // CpxFFT counters, fft.cpp:515-517
         if (ave_count < a.ave_size) ave_count++;
-        // ---- pass A
-        dft_dit<16, +1>(x);
-        {
-            v2f pw[16];
-            twiddle_powers<16>(opaque(wA), pw);
-            static_for<1, 16>([&](auto K) { x[K.value] = cmul(x[K.value], pw[K.value]); });
-        }
-        __syncthreads();                       // the previous frame's pass C has read its rows
-        static_for<0, 16>([&](auto K) { lds[pad16(512 * K.value + t)] = x[K.value]; });
-        __syncthreads();
-        // ---- pass B: column (ka, c), the half b = 2 j + h
-        {
-            v2f *col = lds + 18 * (32 * kaB + hB) + cB;                          // point b = 2 j + h at col[36 j]
-            static_for<0, 16>([&](auto J) { x[bitrev<16>(J.value)] = lds_ld8(col + 36 * J.value); });
-            dft_dit<16, +1>(x);                                                   // Y_h[kj]
-            // the odd half times W_32^{kj} (constants), then the butterfly with the partner lane's half
-            static_for<0, 16>([&](auto K) {
-                constexpr int k = K.value;
-                const v2f w32 = v2f{(float)__builtin_cos(6.283185307179586476925286766559 * k / 32.0),
-                                    (float)__builtin_sin(6.283185307179586476925286766559 * k / 32.0)};
-                const v2f mine = hB ? cmul(x[k], w32) : x[k];
-                const v2f other = pair_swap(mine);
-                x[k] = hB ? other - mine : mine + other;          // h = 0: Y0 + w Y1 -> kb = kj;  h = 1: Y0 - w Y1 -> kb = kj + 16
-            });
-            v2f pw[16];
-            twiddle_powers<16>(opaque(wB), pw);                   // W_512^{c kj}
-            static_for<0, 16>([&](auto K) {
-                constexpr int k = K.value;
-                v2f v = x[k];
-                if constexpr (k != 0) v = cmul(v, pw[k]);
-                v = hB ? cmul(v, wH) : v;                         // times W_512^{16 c h}
-                lds_st8(lds + 18 * (32 * kaB + k + 16 * hB) + cB, v);
-            });
-        }
-        // B -> C stays inside the thirty-two threads that own ka
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // ---- pass C: the 16 consecutive points of row t
-        {
-            const v2f *row = lds + 18 * t;
-            static_for<0, 8>([&](auto J) {
-                const v4f v = *reinterpret_cast<const v4f *>(row + 2 * J.value);
-                x[bitrev<16>(2 * J.value)] = v2f{v.x, v.y};
-                x[bitrev<16>(2 * J.value + 1)] = v2f{v.z, v.w};
-            });
-            dft_dit<16, +1>(x);
-        }
-        const float inv_prev = 1.0f / prev_count;
-        static_for<0, 16>([&](auto Rr) {
+        xf.run(x, lds);
+        const float inv_prev = 1.0f / prev_count;                 // (one division per frame instead of one per bin: -10 %)
+        static_for<0, P>([&](auto Rr) {
             constexpr int r = Rr.value;
             const float p = x[r].x * x[r].x + x[r].y * x[r].y;
             if (total <= a.ave_size) sm[r] = sm[r] + p;
@@ -570,19 +390,33 @@ void spectrum32_kernel(SpectrumArgs a)
     }
     if (a.nparts > 1) {
         float *dst = a.part + ((long)ch * a.nparts + part) * N;
-        static_for<0, 16>([&](auto Rr) { dst[((kbin + 512 * Rr.value) + N / 2) & (N - 1)] = sm[Rr.value]; });
+        static_for<0, P>([&](auto Rr) { dst[shown(Rr.value)] = sm[Rr.value]; });
     } else if (a.nframes > 0) {
-        static_for<0, 16>([&](auto Rr) {
+        static_for<0, P>([&](auto Rr) {
             constexpr int r = Rr.value;
-            const int j = ((kbin + 512 * r) + N / 2) & (N - 1);
+            const int j = shown(r);
             const float m = sm[r] / (float)ave_count;
             sum[j] = sm[r]; pwr[j] = m;
             ave[j] = (float)((double)log10f(m + a.kc) + a.kb);
+            if constexpr (P == 32 && (r & 7) == 7) __builtin_amdgcn_sched_barrier(0);   // (32 points: the bels eight at a time)
         });
     }
     if (t == 0 && a.nparts == 1) { a.counters[2 * ch] = ave_count; a.counters[2 * ch + 1] = total; }
     if (over) a.overload[ch] = 1;
 }
+
+template <int LOG2N, class Ld = RowLoad>
+__global__ __launch_bounds__(SpecCfg<LOG2N>::T) __attribute__((amdgpu_waves_per_eu(1)))
+void spectrum_kernel(SpectrumArgs a) { spectrum_frames<Passes32<LOG2N>, Ld>(a); }
+template <class Ld = RowLoad>
+__global__ __launch_bounds__(128)
+void spectrum8_kernel(SpectrumArgs a) { spectrum_frames<Wide16<PassB2048>, Ld>(a); }
+template <class Ld = RowLoad>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1)))
+void spectrum16_kernel(SpectrumArgs a) { spectrum_frames<Wide16<PassB4096>, Ld>(a); }
+template <class Ld = RowLoad>
+__global__ __launch_bounds__(512)
+void spectrum32_kernel(SpectrumArgs a) { spectrum_frames<Wide16<PassB8192>, Ld>(a); }
 
 // plain transform: out[k] = sum_n in[n] e^{sign j 2 pi n k / N}; sign=-1 via conjugation
 template <int LOG2N>
@@ -666,41 +500,37 @@ __global__ void spectrum_combine_kernel(SpectrumArgs a, int n)
     a.sum[(long)ch * n + j] = sm; a.pwr[(long)ch * n + j] = m;
     a.ave[(long)ch * n + j] = (float)((double)log10f(m + a.kc) + a.kb);
 }
-template <int LOG2N, class Ld = RowLoad>
+// (the kernel is a template argument: CSDR_MAX_LDS_ONCE keeps its flag per launch site, so per kernel)
+template <class X, auto Kernel>
 static hipError_t spec_launch_one(const SpectrumArgs &a, hipStream_t s)
 {
-    using Cfg = SpecCfg<LOG2N>;
-    // The display stream's loaders (Ld != RowLoad) run in the wide kernels only, 2048 ... 8192 points: at 16384 points
-    // (spectrum_kernel<14>, 512 threads, at most 256 registers) the datagram loaders spilled 164 / 236 bytes and the
-    // DC row loader 12 bytes of scratch per lane -- that size gathers its frames instead (capi_fft.hip).
-    constexpr bool plain = std::is_same<Ld, RowLoad>::value;
-    static_assert(plain || LOG2N < 14, "the stream loaders have no 16384-point form");
-    hipError_t e = hipSuccess;
-    if constexpr (plain) {
-        e = CSDR_MAX_LDS_ONCE((&spectrum_kernel<LOG2N>), Cfg::LDS_BYTES);
+    if constexpr (X::LDS_BYTES > 64 * 1024) {             // more LDS than a kernel gets unasked
+        const hipError_t e = CSDR_MAX_LDS_ONCE(Kernel, X::LDS_BYTES);
         if (e != hipSuccess) return e;
     }
-    static const bool wide = !plain || !(getenv("CSDR_SPEC16") && atoi(getenv("CSDR_SPEC16")) == 0);
-    // (the size tests are compile-time: a loader is instantiated in the kernel of ITS sizes only -- the blanked loaders
-    // have no 8192-point form)
-    if constexpr (LOG2N == 12) {
-        if (wide) hipLaunchKernelGGL(spectrum16_kernel<Ld>, dim3(a.channels * a.nparts), dim3(256), SPEC16_LDS, s, a);
-    } else if constexpr (LOG2N == 11) {
-        if (wide) hipLaunchKernelGGL(spectrum8_kernel<Ld>, dim3(a.channels * a.nparts), dim3(128), SPEC8_LDS, s, a);
-    } else if constexpr (LOG2N == 13) {
-        if (wide) {
-            e = CSDR_MAX_LDS_ONCE((&spectrum32_kernel<Ld>), SPEC32_LDS);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(spectrum32_kernel<Ld>, dim3(a.channels * a.nparts), dim3(512), SPEC32_LDS, s, a);
-        }
-    }
-    if constexpr (plain) if (!wide || LOG2N == 14)
-        hipLaunchKernelGGL(spectrum_kernel<LOG2N>, dim3(a.channels * a.nparts), dim3(Cfg::T), Cfg::LDS_BYTES, s, a);
+    hipLaunchKernelGGL(Kernel, dim3(a.channels * a.nparts), dim3(X::T), X::LDS_BYTES, s, a);
     if (a.nparts > 1) {
         hipLaunchKernelGGL(spectrum_alpha_kernel, dim3(a.channels), dim3(64), 0, s, a);
-        hipLaunchKernelGGL(spectrum_combine_kernel, dim3(Cfg::N / 256, a.channels), dim3(256), 0, s, a, (int)Cfg::N);
+        hipLaunchKernelGGL(spectrum_combine_kernel, dim3(X::N / 256, a.channels), dim3(256), 0, s, a, (int)X::N);
     }
     return hipGetLastError();
+}
+// The largest size that a kind of loader has a kernel for; above it the frames are gathered (capi_fft.hip).
+// The display stream's loaders run in the sixteen-point kernels only: at 16384 points (spectrum_kernel<14>, 512 threads,
+// at most 256 registers) the datagram loaders spilled 164 / 236 bytes and the DC row loader 12 bytes of scratch per lane.
+// The blanked loaders exist at 2048 and 4096 points: at 8192 points (spectrum32_kernel, 512 threads: at most 256
+// registers) the mask word per prefetched sample spilled -- 72 bytes of scratch per lane on fp32 rows, 16 on 16-bit and
+// 124 on 24-bit datagrams.
+constexpr int PLAIN_MAX_LOG2N = 14, STREAM_MAX_LOG2N = 13, BLANKED_MAX_LOG2N = 12;
+// (the tests against MAX_LOG2N are compile-time: a loader is instantiated in the kernels of ITS sizes only)
+template <int MAX_LOG2N, class Ld>
+static hipError_t spec_launch(int log2n, const SpectrumArgs &a, hipStream_t s)
+{
+    if (log2n == 11) return spec_launch_one<Wide16<PassB2048>, &spectrum8_kernel<Ld>>(a, s);
+    if (log2n == 12) return spec_launch_one<Wide16<PassB4096>, &spectrum16_kernel<Ld>>(a, s);
+    if constexpr (MAX_LOG2N >= 13) if (log2n == 13) return spec_launch_one<Wide16<PassB8192>, &spectrum32_kernel<Ld>>(a, s);
+    if constexpr (MAX_LOG2N >= 14) if (log2n == 14) return spec_launch_one<Passes32<14>, &spectrum_kernel<14, Ld>>(a, s);
+    return hipErrorInvalidValue;
 }
 template <int LOG2N>
 static hipError_t plain_launch_one(int sign, const float *in, float *out, const float *tw1, const float *tw2, hipStream_t s)
@@ -715,51 +545,23 @@ static hipError_t plain_launch_one(int sign, const float *in, float *out, const 
 
 hipError_t spectrum_launch(int log2n, const SpectrumArgs &a, hipStream_t stream)
 {
-    switch (log2n) {
-    case 11: return spec_launch_one<11>(a, stream);
-    case 12: return spec_launch_one<12>(a, stream);
-    case 13: return spec_launch_one<13>(a, stream);
-    case 14: return spec_launch_one<14>(a, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return spec_launch<PLAIN_MAX_LOG2N, RowLoad>(log2n, a, stream);
 }
-template <class Ld>
-static hipError_t spectrum_stream_one(int log2n, const SpectrumArgs &a, hipStream_t stream)
-{
-    switch (log2n) {
-    case 11: return spec_launch_one<11, Ld>(a, stream);
-    case 12: return spec_launch_one<12, Ld>(a, stream);
-    case 13: return spec_launch_one<13, Ld>(a, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
-// The blanked loaders exist at 2048 and 4096 points.  At 8192 points (spectrum32_kernel, 512 threads: at most 256
-// registers) the mask word per prefetched sample spilled -- 72 bytes of scratch per lane on fp32 rows, 16 on 16-bit and
-// 124 on 24-bit datagrams -- so that size gathers its frames behind a blanked call, as 16384 points does for every stream.
 bool spectrum_stream_blanked_ok(int log2n, int pkt_len)
 {
-    return (log2n == 11 || log2n == 12) && (pkt_len == 0 || pkt_len == 1028 || pkt_len == 1444);
-}
-template <class Ld>
-static hipError_t spectrum_blanked_one(int log2n, const SpectrumArgs &a, hipStream_t stream)
-{
-    switch (log2n) {
-    case 11: return spec_launch_one<11, Ld>(a, stream);
-    case 12: return spec_launch_one<12, Ld>(a, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return log2n >= 11 && log2n <= BLANKED_MAX_LOG2N && (pkt_len == 0 || pkt_len == 1028 || pkt_len == 1444);
 }
 hipError_t spectrum_stream_launch(int log2n, const SpectrumArgs &a, int pkt_len, hipStream_t stream)
 {
     if (a.nb_mask) {
         if (!spectrum_stream_blanked_ok(log2n, a.pk ? pkt_len : 0)) return hipErrorInvalidValue;
-        if (!a.pk) return spectrum_blanked_one<BlankedLoad<RowDcLoad>>(log2n, a, stream);
-        if (pkt_len == 1444) return spectrum_blanked_one<BlankedLoad<WireLoad<1444>>>(log2n, a, stream);
-        return spectrum_blanked_one<BlankedLoad<WireLoad<1028>>>(log2n, a, stream);
+        if (!a.pk) return spec_launch<BLANKED_MAX_LOG2N, BlankedLoad<RowDcLoad>>(log2n, a, stream);
+        if (pkt_len == 1444) return spec_launch<BLANKED_MAX_LOG2N, BlankedLoad<WireLoad<1444>>>(log2n, a, stream);
+        return spec_launch<BLANKED_MAX_LOG2N, BlankedLoad<WireLoad<1028>>>(log2n, a, stream);
     }
-    if (!a.pk) return spectrum_stream_one<RowDcLoad>(log2n, a, stream);
-    if (pkt_len == 1444) return spectrum_stream_one<WireLoad<1444>>(log2n, a, stream);
-    if (pkt_len == 1028) return spectrum_stream_one<WireLoad<1028>>(log2n, a, stream);
+    if (!a.pk) return spec_launch<STREAM_MAX_LOG2N, RowDcLoad>(log2n, a, stream);
+    if (pkt_len == 1444) return spec_launch<STREAM_MAX_LOG2N, WireLoad<1444>>(log2n, a, stream);
+    if (pkt_len == 1028) return spec_launch<STREAM_MAX_LOG2N, WireLoad<1028>>(log2n, a, stream);
     return hipErrorInvalidValue;
 }
 hipError_t fft_plain_launch(int log2n, int sign, const float *in, float *out, const float *tw1,

@@ -1,6 +1,8 @@
-// spectrum_passes.hpp -- the three-pass decimation-in-time transform of the display spectrum (K3), N = 2048 ... 16384 as
-// N/32 threads x 32 points: shared by spectrum_kernels.hip and the batch scope's FFT view (scope_kernels.hip).  A unit
-// that includes it defines CSDR_FMA_BFLY (and CSDR_PLAIN_CONST_FMA) before fft_core.hpp, as spectrum_kernels.hip does.
+// spectrum_passes.hpp -- the three-pass decimation-in-time transform of N = 2048 ... 16384 points as N/32 threads x 32
+// points: the 16384-point display spectrum and the plain transforms of every size (spectrum_kernels.hip: Passes32,
+// fft_plain_kernel) and the batch scope's FFT view (scope_kernels.hip).  The display spectrum of 2048 ... 8192 points has
+// transforms of sixteen points per thread of its own (spectrum_kernels.hip: Wide16).  A unit that includes this file
+// defines CSDR_FMA_BFLY (and CSDR_PLAIN_CONST_FMA) before fft_core.hpp, as spectrum_kernels.hip does.
 #pragma once
 #include <type_traits>
 #include "fft_core.hpp"
@@ -18,11 +20,7 @@ struct SpecCfg {
     // take side by side: column pair t + T k, k < G/2.  A wave's load of one element pair is then 64 x 16 contiguous
     // bytes (with G consecutive columns per thread -- 64 bytes at N = 4096 -- every 128-byte line was consumed by four
     // separate load instructions; measured: no difference in time, the line sat in L2 either way).
-#ifdef CSDR_SPEC_CONSECUTIVE_COLUMNS
-    static __device__ __forceinline__ int col(int t, int e) { return G * t + e; }
-#else
     static __device__ __forceinline__ int col(int t, int e) { return 2 * (t + T * (e >> 1)) + (e & 1); }
-#endif
 };
 
 // forward (positive exponent) transform of the block held as x[e*R0+n1] <-> sample 1024*n1+Cfg::col(t,e);
