@@ -17,6 +17,9 @@ struct csdr_noiseproc_batch {
     float *d_hist = nullptr;             // [2][channels][NB_HIST] complex
     int cur = 0;
     std::vector<NbHost> h;
+    // what the last call read (trace_last re-reads it from the halves cur ^ 1, which that call began with and nothing
+    // touches until the next call); a set-up in between forgets it
+    struct Last { bool valid = false; const void *src = nullptr; long long stride = 0; int pkt_len = 0, n = 0; } last;
     ~csdr_noiseproc_batch()
     {
         if (d_chan) (void)hipFree(d_chan);
@@ -24,6 +27,11 @@ struct csdr_noiseproc_batch {
     }
 };
 
+static bool nb_ring_env()
+{
+    static const bool on = !(getenv("CSDR_NB_RING") && atoi(getenv("CSDR_NB_RING")) == 0);
+    return on;
+}
 // tests (A/B of the two mask kernels in one process): 0 = always the general kernel
 static int nb_int_switch = 1;
 extern "C" int csdr__noiseproc_set_int(int on) { if (on >= 0) nb_int_switch = on; return nb_int_switch; }
@@ -91,6 +99,7 @@ int csdr_noiseproc_batch_setup(csdr_noiseproc_batch *b, int channel, int on, dou
 {
     if (!b || channel >= b->channels) return fail(CSDR_EINVAL, "bad argument");
     if (!device_ok(b->device)) return CSDR_EHIP;
+    b->last.valid = false;
     for (int c = (channel < 0 ? 0 : channel); c < (channel < 0 ? b->channels : channel + 1); c++) {
         const int rc = nb_setup_one(b, c, on, threshold, width_us, sample_rate);
         if (rc) return rc;
@@ -167,13 +176,53 @@ static int nb_run(csdr_noiseproc_batch *b, const float *d_in, long long in_strid
     a.channels = b->channels; a.n = n_per_channel;
     // float rows: from here on the sums may carry roundings -- the integer form is off until the next set-up clears them
     if (!wire.pk) for (auto &h : b->h) h.integral = false;
-    static const bool ring_env = !(getenv("CSDR_NB_RING") && atoi(getenv("CSDR_NB_RING")) == 0);
     const bool mask = d_mask != nullptr;
-    const NbForm form = nb_choose_form(mask, wire.pk ? wire.pkt_len : 0, b->h.data(), b->channels, ring_env, nb_int_switch != 0);
+    const NbForm form = nb_choose_form(mask, wire.pk ? wire.pkt_len : 0, b->h.data(), b->channels, nb_ring_env(), nb_int_switch != 0);
     const NbSegments segs = nb_segments(n_per_channel, b->channels, mask, nb_form_ring(form));
     a.form = form; a.nseg = segs.nseg; a.seg_len = segs.seg_len;
     CSDR_HIP(noiseblank_launch(a, (hipStream_t)stream));
     b->cur ^= 1;
+    b->last.valid = true; b->last.n = n_per_channel;
+    b->last.src = wire.pk ? (const void *)wire.pk : (const void *)d_in;
+    b->last.stride = wire.pk ? (long long)wire.chan_stride : in_stride; b->last.pkt_len = wire.pk ? wire.pkt_len : 0;
+    return CSDR_OK;
+}
+/* PROFILE_7 (noiseproc.cpp:127, :159-175): the trace of the object's last call, whichever form it was, from the state
+ * and history that call began with.  Writes d_trace only; `cur` does not flip. */
+int csdr_noiseproc_batch_trace_last(csdr_noiseproc_batch *b, const float *d_in, long long in_stride, const void *d_packets,
+                                    int npackets, int pkt_len, int n_per_channel, float *d_trace, long long trace_stride,
+                                    void *stream)
+{
+    if (!b || (!d_in && !d_packets) || !d_trace || n_per_channel < 0) return fail(CSDR_EINVAL, "bad argument");
+    if (trace_stride < n_per_channel || (trace_stride & 1) || ((uintptr_t)d_trace & 15))
+        return fail(CSDR_EINVAL, "trace rows: 16-byte aligned, trace_stride even and >= n_per_channel");
+    WireIn wire{nullptr, 0, 0, 0};
+    if (d_packets) {
+        const int bad = wire_in(d_packets, npackets, pkt_len, wire);
+        if (bad & WIRE_LEN) return fail(CSDR_EINVAL, "packet length %d", pkt_len);
+        if (bad || npackets < 0 || (long long)npackets * wire.per != n_per_channel)
+            return fail(CSDR_EINVAL, "datagram buffer: 4-byte aligned, below 2 GiB per channel, npackets x samples = n");
+    }
+    const csdr_noiseproc_batch::Last &l = b->last;
+    const void *src = d_packets ? d_packets : (const void *)d_in;
+    if (!l.valid) return fail(CSDR_ESTATE, "trace_last: no call on this blanker since its creation or last set-up");
+    if (l.src != src || l.n != n_per_channel || l.pkt_len != (d_packets ? pkt_len : 0) ||
+        l.stride != (d_packets ? (long long)wire.chan_stride : in_stride))
+        return fail(CSDR_ESTATE, "trace_last: buffer, stride, count and packet length must be those of the last call");
+    if (!device_ok(b->device)) return CSDR_EHIP;
+    const size_t half = (size_t)b->channels * NB_HIST * 2;
+    NbArgs a;
+    a.wire = wire;
+    a.chan = b->d_chan + (size_t)(b->cur ^ 1) * b->channels; a.chan_next = nullptr;
+    a.in = d_in; a.in_stride = in_stride; a.out = d_trace; a.out_stride = trace_stride;
+    a.hist = b->d_hist + (b->cur ^ 1) * half; a.hist_next = nullptr;
+    a.mask = nullptr; a.mask_stride = 0;
+    a.channels = b->channels; a.n = n_per_channel;
+    // the sample form's ring choice and cut, whatever the call was: behind _process the sums are that call's bit for bit
+    const NbForm form = nb_choose_form(false, wire.pk ? wire.pkt_len : 0, b->h.data(), b->channels, nb_ring_env(), false);
+    const NbSegments segs = nb_segments(n_per_channel, b->channels, false, nb_form_ring(form));
+    a.form = form; a.nseg = segs.nseg; a.seg_len = segs.seg_len;
+    CSDR_HIP(noiseblank_trace_launch(a, (hipStream_t)stream));
     return CSDR_OK;
 }
 

@@ -130,9 +130,12 @@ static int scb_sent(csdr_scope_batch *s, int slot, hipStream_t st)
     return CSDR_OK;
 }
 
-static int scb_put(csdr_scope_batch *s, const float *d_rows, long long stride, const int *n, const double *sample_rate,
-                   void *stream, int cpx)
+// kind: SCOPE_REAL .. SCOPE_STEREO16 (scope_kernels.h); d_rows points at rows of that kind
+static int scb_put(csdr_scope_batch *s, const void *d_rows, long long stride, const int *n, const double *sample_rate,
+                   void *stream, int kind)
 {
+    const int cpx = scope_kind_cpx(kind);
+    const unsigned align = kind == SCOPE_CPX ? 7u : kind == SCOPE_MONO16 ? 1u : 3u;
     if (!have_device()) return CSDR_EHIP;
     if (!s || !n || !sample_rate || stride < 0) return fail(CSDR_EINVAL, "bad argument");
     std::lock_guard<std::mutex> lock(s->mu);
@@ -148,7 +151,7 @@ static int scb_put(csdr_scope_batch *s, const float *d_rows, long long stride, c
             return fail(CSDR_EINVAL, "receiver %d: a sweep of more than 2^30 samples", c);
         any = true;
     }
-    if (any && (!d_rows || ((uintptr_t)d_rows & (cpx ? 7u : 3u)) != 0)) return fail(CSDR_EINVAL, "rows missing or misaligned");
+    if (any && (!d_rows || ((uintptr_t)d_rows & align) != 0)) return fail(CSDR_EINVAL, "rows missing or misaligned");
     bool work = any;
     for (int c = 0; c < s->channels; c++) work |= s->ch[c].flags != 0;
     if (!work) return CSDR_OK;
@@ -165,12 +168,12 @@ static int scb_put(csdr_scope_batch *s, const float *d_rows, long long stride, c
     if (s->last >= 0) CSDR_HIP(hipStreamWaitEvent(st, s->ev[s->last], 0));     // the state follows the previous put, whatever its stream
     CSDR_HIP(hipMemcpyAsync(s->d_par[slot], hp, sizeof(ChanParam) * (size_t)s->channels, hipMemcpyHostToDevice, st));
     ScopeArgs a;
-    a.rows = d_rows; a.stride = stride; a.par = s->d_par[slot]; a.state = s->d_state; a.ring = s->d_ring;
+    a.rows = (const float *)d_rows; a.stride = stride; a.par = s->d_par[slot]; a.state = s->d_state; a.ring = s->d_ring;
     a.screen = s->d_screen; a.w = s->w; a.channels = s->channels;
     a.fst = s->d_fst; a.carry = s->d_carry; a.bels = s->d_bels; a.fscreen = s->d_fscreen; a.peak = s->d_peak;
     a.win = s->d_tab; a.tw1 = s->d_tab + sc::kFftN; a.tw2 = s->d_tab + sc::kFftN + 2048;
     a.kc = (float)s->kc; a.kb = s->kb; a.max_count = max_count;
-    CSDR_HIP(scope_put_launch(a, cpx, st));
+    CSDR_HIP(scope_put_launch(a, kind, st));
     return scb_sent(s, slot, st);
 }
 
@@ -268,10 +271,16 @@ int csdr_scope_batch_enable_peak(csdr_scope_batch *s, int channel, int on)
 
 int csdr_scope_batch_put_real(csdr_scope_batch *s, const float *d_rows, long long stride, const int *n,
                               const double *sample_rate, void *stream)
-{ return scb_put(s, d_rows, stride, n, sample_rate, stream, 0); }
+{ return scb_put(s, d_rows, stride, n, sample_rate, stream, SCOPE_REAL); }
 int csdr_scope_batch_put_cpx(csdr_scope_batch *s, const float *d_rows, long long stride, const int *n,
                              const double *sample_rate, void *stream)
-{ return scb_put(s, d_rows, stride, n, sample_rate, stream, 1); }
+{ return scb_put(s, d_rows, stride, n, sample_rate, stream, SCOPE_CPX); }
+int csdr_scope_batch_put_mono16(csdr_scope_batch *s, const short *d_rows, long long stride, const int *n,
+                                const double *sample_rate, void *stream)
+{ return scb_put(s, d_rows, stride, n, sample_rate, stream, SCOPE_MONO16); }
+int csdr_scope_batch_put_stereo16(csdr_scope_batch *s, const short *d_rows, long long stride, const int *n,
+                                  const double *sample_rate, void *stream)
+{ return scb_put(s, d_rows, stride, n, sample_rate, stream, SCOPE_STEREO16); }
 
 int csdr_scope_batch_get_emits(csdr_scope_batch *s, int *h_emits)
 {

@@ -33,6 +33,7 @@ struct csdr_soundsink_batch {
     SinkBatchParam *h_par = nullptr, *d_par = nullptr;   // pinned, device-mapped: [channels]
     short *h_out = nullptr, *d_out = nullptr;        // pinned, device-mapped: [channels][kQ * w]
     int *h_cnt = nullptr, *d_cnt = nullptr;          // pinned, device-mapped: [channels]
+    bool tapped = false;                 // a put has filled the staging (get_tap)
 };
 
 static int sb_mapped(void **h, void **d, size_t bytes)
@@ -146,7 +147,8 @@ int csdr_soundsink_batch_put(csdr_soundsink_batch *s, const float *d_in, long lo
         s->h_par[c].rate = rate; s->h_par[c].gain = (float)gain; s->h_par[c].n = n;
     }
     if (!any) {
-        if (n_out) for (int c = 0; c < s->channels; c++) n_out[c] = 0;
+        for (int c = 0; c < s->channels; c++) { s->h_cnt[c] = 0; if (n_out) n_out[c] = 0; }    // (the tap of an empty put is empty)
+        s->tapped = true;
         return CSDR_OK;
     }
     const int w = s->stereo ? 2 : 1;
@@ -156,6 +158,7 @@ int csdr_soundsink_batch_put(csdr_soundsink_batch *s, const float *d_in, long lo
     a.out = s->d_out; a.out_stride = (long)kQ * w; a.count = s->d_cnt; a.out_cap = kQ; a.channels = s->channels;
     CSDR_HIP(soundsink_batch_launch(a, s->stereo, (hipStream_t)stream));
     CSDR_HIP(hipStreamSynchronize((hipStream_t)stream));
+    s->tapped = true;
     for (int c = 0; c < s->channels; c++) {
         if (n_in[c] == 0) { if (n_out) n_out[c] = 0; continue; }
         const int k = s->h_cnt[c];
@@ -165,6 +168,15 @@ int csdr_soundsink_batch_put(csdr_soundsink_batch *s, const float *d_in, long lo
         }
         if (n_out) n_out[c] = k;
     }
+    return CSDR_OK;
+}
+/* PROFILE_5 (soundout.cpp:207, :265): the staging the last put filled, as it is -- nothing is copied */
+int csdr_soundsink_batch_get_tap(csdr_soundsink_batch *s, const short **d_rows, long long *stride, const int **d_counts)
+{
+    if (!s || !d_rows || !stride || !d_counts) return fail(CSDR_EINVAL, "bad argument");
+    std::lock_guard<std::mutex> producer(s->mu_put);
+    if (!s->tapped) return fail(CSDR_ESTATE, "get_tap: no put yet");
+    *d_rows = s->d_out; *stride = kQ; *d_counts = s->d_cnt;
     return CSDR_OK;
 }
 /* CSoundOut::GetOutQueue (:311-375 mono, :381-445 stereo) of one receiver: n samples, or n L/R pairs */

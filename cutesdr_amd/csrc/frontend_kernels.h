@@ -36,6 +36,11 @@ struct NbArgs {
                                         // that is not the whole call is >= 32 tiles, four times the longest warm-up)
 };
 hipError_t noiseblank_launch(const NbArgs &a, hipStream_t stream);     // noiseblank_kernels.hip
+// the trace of a call that has run (noiseproc.cpp:159-175, m_TestBenchDataBuf): a.chan / a.hist the halves that call
+// began with, a.out the trace rows ([channels][out_stride] complex fp32, 16-byte aligned, out_stride even), a.form one
+// of the two sample forms with the sample form's segments; chan_next, hist_next and mask are not used, nothing but
+// a.out is written
+hipError_t noiseblank_trace_launch(const NbArgs &a, hipStream_t stream);
 
 // packets: [channels][npackets][pkt_len] bytes, pkt_len 1028 (16 bit, 256 samples) or 1444 (24 bit, 240);
 // out complex fp32 [channels][out_stride]; dc: optional [channels][2] doubles subtracted (I, Q)

@@ -530,6 +530,94 @@ void noiseblank_kernel(NbArgs a)
     nb_finish<MASK>(a, s, C, X, r.S0, r.last);
 }
 
+// ---- the trace form: m_TestBenchDataBuf (noiseproc.cpp:159-175, PROFILE_7) -------------------------------------------
+// What a user of the reference looks at to set threshold and width: re = m_MagAveSum / m_Ratio (0 while blanking),
+// im = oldest.re + oldest.im, the delayed sample; a channel with the blanker off shows its input (:127).  The sample
+// form's tile steps over the samples of a call that has ALREADY run, from the state and history that call began with
+// (a.chan, a.hist: the halves the call read; capi_frontend.hip): the same ring choice, the same segments, so the same
+// sums in the same order and the same decisions.  It has no sample output and no FINISH -- a.out is the trace row,
+// nothing else is written -- and it is a kernel of its own, so that the sample form does not carry the division's and
+// the wide stores' registers.  A thread's four trace entries are 32 contiguous bytes: two 16-byte stores (rows 16-byte
+// aligned, stride even: tiles and threads start on even samples), 8-byte ones at the ends of a segment.
+template <bool RING>
+__global__ __launch_bounds__(NB_T)
+void noiseblank_trace_kernel(NbArgs a)
+{
+    constexpr int PER = NbTile<false, RING>::PER, TILE = NbTile<false, RING>::TILE;
+    static_assert(PER % 2 == 0, "a thread's trace entries are whole 16-byte pairs");
+    __shared__ double wsum[NB_WAVES];
+    __shared__ int wmax[NB_WAVES];
+    extern __shared__ __attribute__((aligned(16))) float nb_ring[];    // [NB_RING] (RING)
+    const NbSeg s(a);
+    const int t = threadIdx.x;
+    const NbChan C = a.chan[s.ch];                          // state at the start of the traced call
+    const NbSrc<0> X(a, s.ch);
+    f2 *tr = reinterpret_cast<f2 *>(a.out) + (long)s.ch * a.out_stride;
+    if (!C.on) {
+        for (long i = s.a + t; i < s.b; i += NB_T) tr[i] = X.call(i);
+        return;
+    }
+    NbRun<double> r{C.sum, -C.since_trig, 0};
+    const int M1 = C.mag_n + 1, W = C.width_n;
+    const double ratio = C.ratio;
+    nb_seg_start<NbFloatMag, RING>(s, X, M1, W, TILE, nb_ring, wsum, r);
+    NbPrefetch<false, RING> pf;
+    pf.M1 = M1; pf.D1 = C.delay_n + 1;
+    pf.fetch(X, r.first, s.b);
+    int rb = RING ? nb_ring_pos(r.first) : 0;
+    for (long base = r.first; base < s.b; base += TILE) {
+        f2 xn[PER], xl[PER], xd[PER];
+        float mag[PER], far[PER];
+        double d[PER], run = 0.0;
+        pf.take(xn, xl, xd);
+        if constexpr (RING) nb_far_linear<PER>(nb_ring, rb, M1, far);
+#pragma unroll
+        for (int k = 0; k < PER; k++) {
+            mag[k] = 0.f; d[k] = 0.0;
+            if (base + (long)t * PER + k < s.b) {
+                mag[k] = NbFloatMag::of(xn[k]);
+                d[k] = (double)mag[k] - (double)(RING ? far[k] : NbFloatMag::of(xl[k]));
+            }
+            run += d[k];
+            d[k] = run;
+        }
+        if constexpr (RING) nb_ring_store<PER>(nb_ring, rb, mag);
+        if (base + TILE < s.b) pf.fetch(X, base + TILE, s.b);
+        double off, total;
+        nb_block_sum(run, r.S0, wsum, off, total);
+        const NbSpan v(s, base, TILE);
+        int lt[PER], runmax = NB_NEVER;
+#pragma unroll
+        for (int k = 0; k < PER; k++) {
+            const int p = t * PER + k;
+            const bool trig = p < v.nvalid && (double)mag[k] * ratio > off + d[k];
+            if (trig) runmax = p;
+            lt[k] = runmax;
+        }
+        int before, tile_last;
+        nb_block_max(runmax, nb_last_rel(r.last, base), wmax, before, tile_last);
+        if (v.nskip == 0) {                                 // (a warm-up tile is dropped whole: nskip is 0 or the tile)
+            f2 e[PER];
+#pragma unroll
+            for (int k = 0; k < PER; k++) {
+                const int p = t * PER + k;
+                const int l = lt[k] > before ? lt[k] : before;
+                e[k] = f2{(p - l < W) ? 0.f : (float)((off + d[k]) / ratio), (float)((double)xd[k].x + (double)xd[k].y)};
+            }
+#pragma unroll
+            for (int k = 0; k < PER; k += 2) {
+                const int p = t * PER + k;
+                if (p + 1 < v.nvalid) *reinterpret_cast<float4 *>(tr + base + p) = make_float4(e[k].x, e[k].y, e[k + 1].x, e[k + 1].y);
+                else if (p < v.nvalid) tr[base + p] = e[k];
+            }
+        }
+        r.S0 += total;
+        if (RING) { rb += TILE; rb = rb >= NB_RING ? rb - NB_RING : rb; }
+        if (tile_last > NB_NEVER) r.last = (long long)base + tile_last;
+        __syncthreads();                                    // wsum / wmax reused by the next tile
+    }
+}
+
 // ---- the mask form on DATAGRAM input in integers (round 6) ---------------------------------------------------------
 // A 16- or 24-bit datagram sample is an integer multiple of 2^-8
 // of the float the general kernel decodes (wire_format.hpp), so the magnitudes max(|I|, |Q|) are integers below 2^23 in
@@ -772,6 +860,14 @@ hipError_t noiseblank_launch(const NbArgs &a, hipStream_t stream)
     case NB_MASK_RING:    return nb_launch<noiseblank_kernel<true, true>>(a, RING_BYTES, stream);
     case NB_MASK_INT24:   return nb_launch<noiseblank_mask_int_kernel<1444>>(a, RING_BYTES, stream);
     case NB_MASK_INT16:   return nb_launch<noiseblank_mask_int_kernel<1028>>(a, RING_BYTES, stream);
+    }
+    return hipErrorInvalidValue;
+}
+hipError_t noiseblank_trace_launch(const NbArgs &a, hipStream_t stream)
+{
+    switch (a.form) {
+    case NB_SAMPLES:      return nb_launch<noiseblank_trace_kernel<false>>(a, 0, stream);
+    case NB_SAMPLES_RING: return nb_launch<noiseblank_trace_kernel<true>>(a, NB_RING * 4, stream);
     }
     return hipErrorInvalidValue;
 }

@@ -5,8 +5,13 @@
 
 namespace csdr {
 
+// the kinds of rows a put reads, one per DisplayData overload (gui/testbench.cpp:643, :583, :702, :761)
+enum { SCOPE_REAL = 0, SCOPE_CPX = 1, SCOPE_MONO16 = 2, SCOPE_STEREO16 = 3 };
+constexpr bool scope_kind_cpx(int kind) { return kind == SCOPE_CPX || kind == SCOPE_STEREO16; }      // m_NewDataIsCpx
+
 struct ScopeArgs {
-    const float *rows; long long stride;     // [channels][stride] fp32 real or complex fp32 pairs, stride in samples; never written
+    const float *rows; long long stride;     // [channels][stride] fp32 real or complex fp32 pairs -- or int16 / int16 pairs behind the
+                                             // same pointer (SCOPE_MONO16 / _STEREO16) --, stride in samples; never written
     const sc::ChanParam *par;                // [channels], device memory
     sc::ChanState *state;                    // [channels]
     int *ring;                               // [channels][2][kMaxW]: m_TimeBuf1/2
@@ -22,7 +27,7 @@ struct ScopeArgs {
     int max_count;                           // the largest number of used frames of a receiver in this call
 };
 // the put of every receiver: one launch, and one more for the used frames of the FFT-view receivers when there are any
-hipError_t scope_put_launch(const ScopeArgs &a, int cpx, hipStream_t s);
+hipError_t scope_put_launch(const ScopeArgs &a, int kind, hipStream_t s);
 
 struct ScopeFftScreenArgs {
     const int *fscreen, *peak;               // [channels][kMaxW]

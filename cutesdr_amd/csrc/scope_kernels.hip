@@ -30,13 +30,36 @@ namespace {
 
 constexpr int kThreads = 512;
 
+// The four overloads of DisplayData as row kinds: 0 TYPEREAL (:643-695), 1 TYPECPX (:583-636), 2 TYPEMONO16 (:702-754),
+// 3 TYPESTEREO16 (:761-814).  A kind says where row c begins, what an emission writes into the ring (get), what
+// ChkForTrigger and m_PreviousSample see (trig) and what a sample is in m_FftInBuf (frame).  They differ only for
+// TYPEMONO16: the trigger looks at pBuf[i<<1] (:741) -- index 2i inside the call's n samples, 0 past them (deviation (7):
+// the reference reads past its buffer) -- and the FFT frame entry is (x, x) (:718-719).
 template <int CPX> struct Row {
     const float *p; long long n;
+    static __device__ const float *at(const ScopeArgs &a, int c)
+    {
+        if constexpr (CPX >= 2) return (const float *)((const short *)a.rows + (size_t)c * (size_t)a.stride * (CPX == 3 ? 2 : 1));
+        else return a.rows + (size_t)c * (size_t)a.stride * (CPX ? 2 : 1);
+    }
     __device__ void get(long long s, int &re, int &im) const
     {
         s = s < n ? s : n - 1;                           // an emission's sample is < n by construction
-        if (CPX) { const float2 v = ((const float2 *)p)[s]; re = sc::sat_int(v.x); im = sc::sat_int(v.y); }
+        if constexpr (CPX == 3) { const short2 v = ((const short2 *)p)[s]; re = v.x; im = v.y; }
+        else if constexpr (CPX == 2) { re = ((const short *)p)[s]; im = 0; }
+        else if (CPX) { const float2 v = ((const float2 *)p)[s]; re = sc::sat_int(v.x); im = sc::sat_int(v.y); }
         else { re = sc::sat_int(p[s]); im = 0; }
+    }
+    __device__ int trig(long long s) const
+    {
+        if constexpr (CPX == 2) { s = s < n ? s : n - 1; return 2 * s < n ? ((const short *)p)[2 * s] : 0; }
+        else { int re, im; get(s, re, im); return re; }
+    }
+    static __device__ float2 frame(const float *row, long long s)
+    {
+        if constexpr (CPX == 3) { const short2 v = ((const short2 *)row)[s]; return make_float2((float)v.x, (float)v.y); }
+        else if constexpr (CPX == 2) { const float x = (float)((const short *)row)[s]; return make_float2(x, x); }
+        else return CPX ? ((const float2 *)row)[s] : make_float2(row[s], 0.f);
     }
 };
 
@@ -62,18 +85,18 @@ template <int CPX> __global__ __launch_bounds__(kThreads) void scope_put_kernel(
     sc::apply_flags(st, par.flags);
     if (par.view == sc::VIEW_FFT) {                      // :594-611 / :654-672 without the frames: scope_fft_kernel's
         if (par.n > 0) {
-            const float *row = a.rows + (size_t)c * (size_t)a.stride * (CPX ? 2 : 1);
+            const float *row = Row<CPX>::at(a, c);
             float2 *carry = (float2 *)a.carry + (size_t)c * 2 * sc::kFftN;
             // no frame completes: the samples join the partial frame; else the tail after the last complete frame
             // starts the other buffer
             float2 *dst = par.frames == 0 ? carry + (size_t)par.cur * sc::kFftN + par.fill : carry + (size_t)(par.cur ^ 1) * sc::kFftN;
             const int cnt = par.frames == 0 ? par.n : par.pos_end, from = par.n - cnt;
             for (int i = tid; i < cnt; i += kThreads)
-                dst[i] = CPX ? ((const float2 *)row)[from + i] : make_float2(row[from + i], 0.f);
+                dst[i] = Row<CPX>::frame(row, from + i);
             if (tid == 0) {
                 sc::FftState f = a.fst[c];
                 f.pos = par.pos_end; f.total += par.count;
-                if (par.count > 0) f.cpx = CPX;
+                if (par.count > 0) f.cpx = scope_kind_cpx(CPX);
                 a.fst[c] = f;
                 st.skipcounter = par.cnt_end; st.emits += (unsigned)par.count;     // emit NewFftData, :607
             }
@@ -86,7 +109,7 @@ template <int CPX> __global__ __launch_bounds__(kThreads) void scope_put_kernel(
         if (par.flags && tid == 0) a.state[c] = st;
         return;
     }
-    const Row<CPX> row = {a.rows + (size_t)c * (size_t)a.stride * (CPX ? 2 : 1), n};
+    const Row<CPX> row = {Row<CPX>::at(a, c), n};
     const sc::Plan pl = sc::make_plan(st.inpos, st.pos, par.pix, par.sr, w, n);
     const long long E = pl.emits;
     const int pos0 = st.pos;
@@ -99,9 +122,8 @@ template <int CPX> __global__ __launch_bounds__(kThreads) void scope_put_kernel(
             const long long e = base + tid;
             bool hit = false;
             if (e < E) {
-                int cur, prv, im;
-                row.get(pl.sample(e), cur, im);
-                if (e == 0) prv = st.prev; else row.get(pl.sample(e - 1), prv, im);
+                const int cur = row.trig(pl.sample(e));
+                const int prv = e == 0 ? st.prev : row.trig(pl.sample(e - 1));
                 hit = sc::crossing(par.mode, par.level, cur, prv);
             }
             if (__syncthreads_or(hit)) {
@@ -132,8 +154,7 @@ template <int CPX> __global__ __launch_bounds__(kThreads) void scope_put_kernel(
         ring[slot] = re; ring[sc::kMaxW + slot] = im;
     }
     if (tid == 0) {
-        int im;
-        if (E > 0) row.get(pl.sample(E - 1), st.prev, im);          // :897
+        if (E > 0) st.prev = row.trig(pl.sample(E - 1));            // :897
         st.inpos = pl.inpos_end; st.pos = pl.pos_end;
         a.state[c] = st;
     }
@@ -180,7 +201,7 @@ template <int CPX> __global__ __launch_bounds__(FftCfg::T) void scope_fft_kernel
     const long long j = (long long)par.first + (long long)k * par.step;          // < par.frames
     const int fill = par.fill;
     const v2f *carry = reinterpret_cast<const v2f *>(a.carry) + ((size_t)c * 2 + par.cur) * N;
-    const float *row = a.rows + (size_t)c * (size_t)a.stride * (CPX ? 2 : 1);
+    const float *row = Row<CPX>::at(a, c);
     v2f x[32];
 #pragma unroll
     for (int e = 0; e < G; e++)
@@ -190,6 +211,7 @@ template <int CPX> __global__ __launch_bounds__(FftCfg::T) void scope_fft_kernel
             const long long s = sc::fft_source(j, i, fill);                      // < par.n: frame j completes in the call
             v2f v;
             if (s < 0) v = carry[s + fill];
+            else if constexpr (CPX >= 2) { const float2 f = Row<CPX>::frame(row, s); v = v2f{f.x, f.y}; }
             else if (CPX) v = reinterpret_cast<const v2f *>(row)[s];
             else v = v2f{row[s], 0.f};
             const float w = a.win[i];
@@ -234,14 +256,20 @@ __global__ __launch_bounds__(256) void scope_fft_screens_kernel(ScopeFftScreenAr
 
 }  // namespace
 
-hipError_t scope_put_launch(const ScopeArgs &a, int cpx, hipStream_t s)
+template <int KIND> static void scope_put_kind(const ScopeArgs &a, hipStream_t s)
 {
-    if (cpx) hipLaunchKernelGGL(scope_put_kernel<1>, dim3(a.channels), dim3(kThreads), 0, s, a);
-    else hipLaunchKernelGGL(scope_put_kernel<0>, dim3(a.channels), dim3(kThreads), 0, s, a);
-    if (a.max_count > 0) {
-        const dim3 grid(a.max_count, a.channels);
-        if (cpx) hipLaunchKernelGGL(scope_fft_kernel<1>, grid, dim3(FftCfg::T), FftCfg::LDS_BYTES, s, a);
-        else hipLaunchKernelGGL(scope_fft_kernel<0>, grid, dim3(FftCfg::T), FftCfg::LDS_BYTES, s, a);
+    hipLaunchKernelGGL(scope_put_kernel<KIND>, dim3(a.channels), dim3(kThreads), 0, s, a);
+    if (a.max_count > 0)
+        hipLaunchKernelGGL(scope_fft_kernel<KIND>, dim3(a.max_count, a.channels), dim3(FftCfg::T), FftCfg::LDS_BYTES, s, a);
+}
+hipError_t scope_put_launch(const ScopeArgs &a, int kind, hipStream_t s)
+{
+    switch (kind) {
+    case SCOPE_REAL:     scope_put_kind<SCOPE_REAL>(a, s); break;
+    case SCOPE_CPX:      scope_put_kind<SCOPE_CPX>(a, s); break;
+    case SCOPE_MONO16:   scope_put_kind<SCOPE_MONO16>(a, s); break;
+    case SCOPE_STEREO16: scope_put_kind<SCOPE_STEREO16>(a, s); break;
+    default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }

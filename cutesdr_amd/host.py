@@ -327,6 +327,14 @@ class NoiseProcBatch(_Obj):
         sync(self.device)
         return dout.download(np.complex64, x.size).reshape(x.shape)
 
+    def trace_last(self, d_trace, trace_stride, n, d_in=0, in_stride=0, d_packets=0, npackets=0, pkt_len=0, stream=0):
+        """PROFILE_7 (noiseproc.cpp:159-175): m_TestBenchDataBuf of the object's last call into d_trace = device
+        [channels][trace_stride] complex fp32.  d_in / in_stride (float rows) or d_packets / npackets / pkt_len, and n,
+        are those of that call; writes the trace only.  Returns the status without raising on CSDR_ESTATE."""
+        rc = lib().csdr_noiseproc_batch_trace_last(self.h, C.c_void_p(d_in), in_stride, C.c_void_p(d_packets), npackets,
+                                                   pkt_len, n, C.c_void_p(d_trace), trace_stride, C.c_void_p(stream))
+        return rc if rc == _capi.CSDR_ESTATE else check(rc, "csdr_noiseproc_batch_trace_last")
+
 
 def unpack_packets(raw, pkt_len, device=0):
     """UDP datagrams (uint8 [npackets, pkt_len], 1028 = 16 bit / 1444 = 24 bit) -> complex128 samples
@@ -1235,6 +1243,17 @@ class SoundSinkBatch(_Obj):
         check(lib().csdr_soundsink_batch_get(self.h, channel, n, _vp(out)), "csdr_soundsink_batch_get")
         return out
 
+    def tap(self):
+        """PROFILE_5 (soundout.cpp:207, :265): (device pointer to the int16 rows of the last put, their stride in
+        samples or L/R pairs, device pointer to the int32 counts); nothing is copied.  None before the first put."""
+        rows, stride, counts = C.c_void_p(), C.c_longlong(), C.c_void_p()
+        rc = lib().csdr_soundsink_batch_get_tap(self.h, C.cast(C.byref(rows), C.c_void_p), C.cast(C.byref(stride), C.c_void_p),
+                                                C.cast(C.byref(counts), C.c_void_p))
+        if rc == _capi.CSDR_ESTATE:
+            return None
+        check(rc, "csdr_soundsink_batch_get_tap")
+        return rows.value, stride.value, counts.value
+
     def rate_correction(self, channel):
         return lib().csdr_soundsink_batch_get_rate_correction(self.h, channel)
 
@@ -1366,6 +1385,30 @@ class ScopeBatch(_Obj):
                      torch.cuda.current_stream(rows.device).cuda_stream, cpx=rows.dtype == torch.complex64)
 
     put_real = put_cpx = DisplayData
+
+    def put16_ptr(self, d_rows, stride, n, samplerate, stream=None, stereo=False):
+        """the TYPEMONO16 / TYPESTEREO16 overloads (:702-814): d_rows device [channels][stride] int16 (int16 pairs when
+        stereo); the rows may be a sound sink's tap"""
+        n = np.ascontiguousarray(np.broadcast_to(np.asarray(n, dtype=np.int32), (self.channels,)))
+        fs = np.ascontiguousarray(np.broadcast_to(np.asarray(samplerate, dtype=np.float64), (self.channels,)))
+        fn = lib().csdr_scope_batch_put_stereo16 if stereo else lib().csdr_scope_batch_put_mono16
+        check(fn(self.h, C.c_void_p(d_rows), stride, _vp(n), _vp(fs), C.c_void_p(stream) if stream else None),
+              "csdr_scope_batch_put16")
+
+    def put_mono16(self, rows, length, samplerate):
+        """rows: int16 device tensor [channels, T]"""
+        import torch
+        assert rows.is_cuda and rows.dtype == torch.int16 and rows.shape[0] == self.channels and rows.stride(1) == 1
+        assert int(np.max(length)) <= rows.shape[1]
+        self.put16_ptr(rows.data_ptr(), rows.stride(0), length, samplerate, torch.cuda.current_stream(rows.device).cuda_stream)
+
+    def put_stereo16(self, rows, length, samplerate):
+        """rows: int16 device tensor [channels, T, 2] (re, im)"""
+        import torch
+        assert rows.is_cuda and rows.dtype == torch.int16 and rows.shape[0] == self.channels and rows.shape[2] == 2
+        assert rows.stride(2) == 1 and rows.stride(1) == 2 and rows.stride(0) % 2 == 0 and int(np.max(length)) <= rows.shape[1]
+        self.put16_ptr(rows.data_ptr(), rows.stride(0) // 2, length, samplerate,
+                       torch.cuda.current_stream(rows.device).cuda_stream, stereo=True)
 
     def get_emits(self):
         out = np.zeros(self.channels, dtype=np.int32)

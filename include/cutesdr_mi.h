@@ -629,6 +629,16 @@ int csdr_soundsink_batch_put(csdr_soundsink_batch *s, const float *d_in, long lo
                              int *n_out, void *stream);
 /* GetOutQueue (:311-445) of one receiver: n samples, or n L/R pairs of a stereo sink; returns n */
 int csdr_soundsink_batch_get(csdr_soundsink_batch *s, int channel, int n, short *out);
+/* PROFILE_5 (interface/soundout.cpp:207, :265; gui/testbench.h:29-38): the resampled int16 samples of the LAST put on
+ * their way into the queues, at the sink's 48 kHz -- what the reference hands to DisplayData(n, m_pData, 48000,
+ * PROFILE_5).  *d_rows: device pointer to [channels][*stride] int16 (int16 L/R pairs of a stereo sink, *stride in
+ * pairs), *d_counts: device pointer to [channels] int32, the resampled count of each receiver (0 for a row with n_in =
+ * 0).  They are the staging the put itself fills (pinned host memory mapped into the device): nothing is copied, the
+ * pointers are the same after every put, the rows are complete when put returns (it has waited on its stream) and
+ * valid until the next put begins.  Made for csdr_scope_batch_put_mono16 / _stereo16.  CSDR_ESTATE before the first
+ * put.  Out of scope: a shard form, PROFILE_6 (the reference has it commented out: samdemod.cpp:91-92). */
+int csdr_soundsink_batch_get_tap(csdr_soundsink_batch *s, const short **d_rows, long long *stride,
+                                 const int **d_counts);
 double csdr_soundsink_batch_get_rate_correction(csdr_soundsink_batch *s, int channel);    /* m_RateCorrection */
 double csdr_soundsink_batch_get_ave_level(csdr_soundsink_batch *s, int channel);          /* m_AveOutQLevel */
 int csdr_soundsink_batch_get_level(csdr_soundsink_batch *s, int channel);                 /* m_OutQLevel */
@@ -658,6 +668,32 @@ int csdr_noiseproc_batch_setup(csdr_noiseproc_batch *b, int channel, int on, dou
                                double sample_rate);
 int csdr_noiseproc_batch_process(csdr_noiseproc_batch *b, const float *d_in, long long in_stride, int n_per_channel,
                                  float *d_out, long long out_stride, void *stream);
+/* PROFILE_7 (noiseproc.cpp:127, :159-175): the blanker's own trace m_TestBenchDataBuf of the object's LAST call, the
+ * picture a threshold and a width are set from.  That call may be csdr_noiseproc_batch_process or the blanker pass
+ * that csdr_demod_batch_process_blanked / _process_packets run on `b`; the trace re-reads its samples and starts from
+ * the state and history that call began with (kept untouched until the next call).  Per sample i of receiver c, into
+ * d_trace = device [channels][trace_stride] complex fp32:
+ *     blanker on:   re = blanked_i ? 0 : (float)(m_MagAveSum_i / m_Ratio)   (the fp64 moving sum after sample i entered
+ *                   it, :143-147; one fp64 division, :169), im = (float)((double)o.re + o.im) with o = x[i - delay - 1],
+ *                   the delayed sample, blanked or not (:159)
+ *     blanker off:  the input sample (:127)
+ * A threshold of 0 (m_Ratio = 0) gives IEEE's inf / NaN, as in the reference.
+ * Contract, as for the *_blanked display calls: d_in / in_stride / n_per_channel (float rows), or d_packets / npackets
+ * / pkt_len with n_per_channel = npackets x samples per datagram (d_in ignored), are those of that last call; same
+ * `stream`; before the next call on `b`; no csdr_noiseproc_batch_setup in between.  The object remembers buffer,
+ * stride, count and packet length of its last call: CSDR_ESTATE when they differ, when there was no call yet or a
+ * set-up since; CSDR_EINVAL for a bad argument (d_trace 16-byte aligned, trace_stride even and >= n_per_channel).  A
+ * refused call writes nothing.  An accepted one writes d_trace only -- no state, no history: the next call is what it
+ * would have been.
+ * Behind csdr_noiseproc_batch_process the trace's sums and decisions are that call's bit for bit (same kernel form,
+ * same segments).  Behind a chain's mask pass on arbitrary fp32 rows a decision that ties to the last bit of an fp64
+ * sum can differ from the mask (that pass cuts its segments differently); on datagram input every sum is exact and
+ * nothing can differ.
+ * Out of scope: shard forms, a trace that goes into the scope without rows in between, PROFILE_7 forwarding in the
+ * drop-in CNoiseProc. */
+int csdr_noiseproc_batch_trace_last(csdr_noiseproc_batch *b, const float *d_in, long long in_stride, const void *d_packets,
+                                    int npackets, int pkt_len, int n_per_channel, float *d_trace, long long trace_stride,
+                                    void *stream);
 
 /* IQ wire format (interface/netiobase.cpp:479-527): whole UDP datagrams, 4 header bytes then
  * little-endian I,Q pairs; pkt_len 1028 = 256 samples of 16 bit, 1444 = 240 samples of 24 bit
@@ -816,8 +852,14 @@ int csdr_testgen_batch_generate_real(csdr_testgen_batch *t, float *d_out, long l
  * view loses its ring, as in the reference; the flag itself is kept and only reported.
  *   An FFT-view receiver needs sample_rate < 2^31 - 16 ((qint32)fs and the + 5): CSDR_EINVAL before any state changes.
  *
- * Out of scope: the TYPEMONO16 / TYPESTEREO16 overloads in either view (the mono one reads pBuf[i<<1], past its
- * buffer), a drop-in CTestBench class (it is a QDialog), an automatic re-arm inside a call, a shard form (a shard host
+ * The int16 overloads (TYPESTEREO16 :761-814, TYPEMONO16 :702-754), the only ones PROFILE_5 reaches.  Stereo: the time
+ * view triggers on (int)re and the ring gets re and im; the FFT view takes (re, im), mapped as complex.  Mono: the FFT
+ * frame entry is (x, x), BOTH parts (:718-719), m_NewDataIsCpx is false and the screen starts at 0 Hz; in the time view
+ * the ring gets pBuf[i] and 0, but ChkForTrigger and m_PreviousSample see pBuf[i<<1] (:741).  Deviation (7): index 2i
+ * counts inside the call's n[c] samples, and for 2i >= n[c] the trigger sample is 0 (the reference reads past its
+ * buffer there).  Deviations (1)-(6) hold.
+ *
+ * Out of scope: a drop-in CTestBench class (it is a QDialog), an automatic re-arm inside a call, a shard form (a shard host
  * makes one scope per device, as for the batch sound sink), painting and overlays, a setter for the dB range (the
  * reference has none).
  * -------------------------------------------------------------------------------------- */
@@ -847,6 +889,13 @@ int csdr_scope_batch_put_real(csdr_scope_batch *s, const float *d_rows, long lon
 /* the TYPECPX overload (:583-636): rows of complex fp32, stride in complex samples; the trigger looks at re */
 int csdr_scope_batch_put_cpx(csdr_scope_batch *s, const float *d_rows, long long stride, const int *n,
                              const double *sample_rate, void *stream);
+/* the TYPEMONO16 overload (:702-754): rows of int16, 2-byte aligned; rules, bounds and ordering as put_real.  The rows
+ * may lie in device-mapped host memory (csdr_soundsink_batch_get_tap) */
+int csdr_scope_batch_put_mono16(csdr_scope_batch *s, const short *d_rows, long long stride, const int *n,
+                                const double *sample_rate, void *stream);
+/* the TYPESTEREO16 overload (:761-814): rows of int16 (re, im) pairs, 4-byte aligned, stride in pairs */
+int csdr_scope_batch_put_stereo16(csdr_scope_batch *s, const short *d_rows, long long stride, const int *n,
+                                  const double *sample_rate, void *stream);
 /* DrawTimePlot's re-arm (:995-999): the state goes back to WAIT unless the mode is one of the two single ones;
  * applied in stream order by the next put */
 int csdr_scope_batch_time_plot_done(csdr_scope_batch *s, int channel);
