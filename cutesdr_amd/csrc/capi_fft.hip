@@ -42,6 +42,10 @@ struct csdr_fft_batch {
     double disp_fs = 0; int disp_rate = 0;       // m_SampleRate and m_MaxDisplayRate (set_params re-derives the skip value)
     float *d_carry = nullptr;                    // [channels][N] complex: m_DataBuf of each channel, DC-corrected
     float *d_stage = nullptr; size_t stage_cap = 0;   // [channels][used frames][N] complex: the frames a call uses
+    // the batch form of FwdFFT / RevFFT at 32768 and 65536 points (csdr_fft_batch_fwd / _rev): the four-step form's
+    // tables and its intermediate, plain_group frames of every row; display calls never touch them
+    float *d_twp = nullptr, *d_pwork = nullptr;
+    int plain_group = 0;
 };
 
 // device -> host behind the object's own work: on the stream of its last put_display (until round 5: hipDeviceSynchronize)
@@ -69,7 +73,7 @@ static hipError_t fft_grow(E *&buf, size_t &cap, size_t need, hipStream_t st)
 
 static void fft_free_dev(csdr_fft_batch *f)
 {
-    float **ps[] = {&f->d_win, &f->d_tw1, &f->d_tw2, &f->d_sum, &f->d_pwr, &f->d_ave, &f->d_work, &f->d_carry};
+    float **ps[] = {&f->d_win, &f->d_tw1, &f->d_tw2, &f->d_sum, &f->d_pwr, &f->d_ave, &f->d_work, &f->d_carry, &f->d_twp, &f->d_pwork};
     for (auto p : ps) { if (*p) (void)hipFree(*p); *p = nullptr; }
 }
 
@@ -104,6 +108,20 @@ static int fft_set_params(csdr_fft_batch *f, int size, int invert, double db_com
         CSDR_HIP(hipMalloc((void **)&f->d_ave, nb));
         CSDR_HIP(hipMalloc((void **)&f->d_carry, nb * 2));
         if (l2 < 11 || l2 > 14) CSDR_HIP(hipMalloc((void **)&f->d_work, nb * 4));   // [2][channels][N] complex
+        f->plain_group = 0;
+        if (l2 > 14) {
+            // the work buffer holds 64 frames (a launch of 512 ... 1024 workgroups), and at least one of every row
+            f->plain_group = f->channels < 64 ? 64 / f->channels : 1;
+            CSDR_HIP(hipMalloc((void **)&f->d_twp, 512 * 8));
+            CSDR_HIP(hipMalloc((void **)&f->d_pwork, nb * 2 * f->plain_group));
+            std::vector<float> twp(1024);
+            for (int i = 0; i < 256; i++) {
+                const double a = kTwoPi * (double)i / 256.0, b = kTwoPi * (double)i / (double)n;
+                twp[2 * i] = (float)std::cos(a); twp[2 * i + 1] = (float)std::sin(a);
+                twp[512 + 2 * i] = (float)std::cos(b); twp[512 + 2 * i + 1] = (float)std::sin(b);
+            }
+            CSDR_HIP(hipMemcpy(f->d_twp, twp.data(), 512 * 8, hipMemcpyHostToDevice));
+        }
         CSDR_HIP(hipMemset(f->d_pwr, 0, nb));
         f->kb = f->db_comp - 20 * std::log10((double)n * refc::FFT_K_AMPMAX / 2.0);
         f->kc = std::pow(10.0, (refc::FFT_K_MINDB - f->kb) / 10.0);
@@ -498,6 +516,38 @@ int csdr_fft_batch_get_waterfall_all(csdr_fft_batch *f, int max_w, double max_db
     CSDR_HIP(waterfall_color_launch(f->d_scr, max_w, d_rgb, out_stride, max_w, f->channels, (hipStream_t)stream));
     return CSDR_OK;
 }
+
+/* CFft::FwdFFT / RevFFT (fft.cpp:416-426) of nframes frames of every row; asynchronous, nothing of the display state read
+ * or written (not last_stream either: the readers wait for display calls only) */
+static int fft_batch_plain(csdr_fft_batch *f, const float *d_in, long long in_stride, float *d_out, long long out_stride,
+                           int nframes, void *stream, int sign)
+{
+    if (!f || !d_in || !d_out || nframes < 0) return fail(CSDR_EINVAL, "bad argument");
+    if (nframes == 0) return CSDR_OK;
+    const long long need = (long long)nframes * f->size;
+    if (in_stride < need || out_stride < need) return fail(CSDR_EINVAL, "a row's stride must hold its %d frames of %d", nframes, f->size);
+    if (((uintptr_t)d_in | (uintptr_t)d_out) & 7) return fail(CSDR_EINVAL, "d_in and d_out must be 8-byte aligned");
+    if (!(d_in == d_out && in_stride == out_stride)) {
+        const uintptr_t a0 = (uintptr_t)d_in, a1 = a0 + (uintptr_t)((f->channels - 1) * in_stride + need) * 8;
+        const uintptr_t b0 = (uintptr_t)d_out, b1 = b0 + (uintptr_t)((f->channels - 1) * out_stride + need) * 8;
+        if (a0 < b1 && b0 < a1) return fail(CSDR_EINVAL, "d_out overlaps d_in (in place is d_out == d_in with equal strides)");
+    }
+    if ((long long)f->channels * nframes > 0x7fffffffll) return fail(CSDR_EINVAL, "channels * nframes must stay below 2^31");
+    if (!device_ok(f->device)) return CSDR_EHIP;
+    PlainBatchArgs a;
+    a.in = d_in; a.in_stride = (long)in_stride; a.out = d_out; a.out_stride = (long)out_stride;
+    a.channels = f->channels; a.nframes = nframes; a.sign = sign;
+    a.tw1 = f->d_tw1; a.tw2 = f->d_tw2; a.twp = f->d_twp; a.work = f->d_pwork; a.group = f->plain_group;
+    CSDR_HIP(fft_batch_plain_launch(log2_of(f->size), a, (hipStream_t)stream));
+    return CSDR_OK;
+}
+int csdr_fft_batch_fwd(csdr_fft_batch *f, const float *d_in, long long in_stride, float *d_out, long long out_stride,
+                       int nframes, void *stream)
+{ return fft_batch_plain(f, d_in, in_stride, d_out, out_stride, nframes, stream, +1); }
+int csdr_fft_batch_rev(csdr_fft_batch *f, const float *d_in, long long in_stride, float *d_out, long long out_stride,
+                       int nframes, void *stream)
+{ return fft_batch_plain(f, d_in, in_stride, d_out, out_stride, nframes, stream, -1); }
+int csdr_fft_batch_plain_group(csdr_fft_batch *f) { return f ? f->plain_group : fail(CSDR_EINVAL, "bad handle"); }
 
 // what csdr_plotter_batch_draw reads: nothing of the cached translate table, and nothing here is changed
 int csdr__fft_batch_view(csdr_fft_batch *f, FftView *v)

@@ -39,6 +39,18 @@ hipError_t spectrum_stream_launch(int log2n, const SpectrumArgs &a, int pkt_len,
 hipError_t fft_plain_launch(int log2n, int sign, const float *in, float *out, const float *tw1,
                             const float *tw2, hipStream_t stream);
 
+// plain transforms of nframes frames of every row (fft_batch_plain_kernels.hip), 512 ... 65536 points: frame k of row c
+// at in + 2 (c in_stride + k N) floats, its transform at the same place of out; in == out with equal strides is in place
+struct PlainBatchArgs {
+    const float *in;  long in_stride;   // complex fp32 [channels][in_stride]
+    float *out;       long out_stride;
+    int channels, nframes, sign;        // sign=+1 CFft::FwdFFT, -1 RevFFT
+    const float *tw1, *tw2;             // the object's tables (tw1 is W_N^i, i < 1024: all of it at 512 and 1024 points)
+    const float *twp;                   // 32768 and 65536 points: [256] W_256^m, then [256] W_N^m
+    float *work; int group;             // 32768 and 65536 points: the intermediate of `group` frames of every row,
+};                                      // [channels][group][N] complex; longer calls go through it in groups
+hipError_t fft_batch_plain_launch(int log2n, const PlainBatchArgs &a, hipStream_t stream);
+
 // CFft::GetScreenIntegerFFTData (fft.cpp:308-410) for every channel: ave [channels][n] bels (display order)
 // -> out [channels][out_stride] pixels; the bin range / pixel count come precomputed from the host
 struct ScreenArgs {

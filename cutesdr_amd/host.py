@@ -986,6 +986,47 @@ class FftBatch(_Obj):
         sync(self.device)
         din.free()
 
+    # ---- CFft::FwdFFT / RevFFT of every frame of every row: complex spectra, the display state untouched
+    def _plain_ptr(self, name, d_in, in_stride, d_out, out_stride, nframes, stream):
+        check(getattr(lib(), name)(self.h, C.c_void_p(d_in), in_stride, C.c_void_p(d_out), out_stride, nframes,
+                                   C.c_void_p(stream) if stream else None), name)
+
+    def fwd_ptr(self, d_in, in_stride, d_out, out_stride, nframes, stream=None):
+        """FwdFFT (positive exponent, unnormalised) of nframes frames per row, device pointers; d_out == d_in with equal
+        strides is in place; asynchronous"""
+        self._plain_ptr("csdr_fft_batch_fwd", d_in, in_stride, d_out, out_stride, nframes, stream)
+
+    def rev_ptr(self, d_in, in_stride, d_out, out_stride, nframes, stream=None):
+        """RevFFT (negative exponent, unnormalised), as fwd_ptr"""
+        self._plain_ptr("csdr_fft_batch_rev", d_in, in_stride, d_out, out_stride, nframes, stream)
+
+    def plain_group(self):
+        """frames per row that one pass of the 32768 / 65536-point transforms takes through the work buffer (else 0)"""
+        return check(lib().csdr_fft_batch_plain_group(self.h))
+
+    def _plain(self, call, x):
+        x = np.ascontiguousarray(x, dtype=np.complex64)
+        n = self.size()
+        assert x.ndim == 2 and x.shape[0] == self.channels and x.shape[1] % n == 0, x.shape
+        if x.shape[1] == 0:
+            return x.copy()
+        d = DeviceBuffer(x.nbytes, self.device)
+        d.upload(x)
+        try:
+            call(d.ptr, x.shape[1], d.ptr, x.shape[1], x.shape[1] // n)
+            sync(self.device)
+            return d.download(np.complex64, x.size).reshape(x.shape)
+        finally:
+            d.free()
+
+    def fwd(self, x):
+        """x complex [channels, frames*size] (host) -> FwdFFT of every frame, complex64"""
+        return self._plain(self.fwd_ptr, x)
+
+    def rev(self, x):
+        """x complex [channels, frames*size] (host) -> RevFFT of every frame, complex64"""
+        return self._plain(self.rev_ptr, x)
+
     def ave_buf(self, channel):
         out = np.zeros(self.size(), dtype=np.float32)
         check(lib().csdr_fft_batch_get_ave(self.h, channel, _vp(out)))

@@ -463,6 +463,27 @@ int csdr_fft_batch_reset(csdr_fft_batch *f);
 int csdr_fft_batch_size(csdr_fft_batch *f);
 int csdr_fft_batch_put_display(csdr_fft_batch *f, const float *d_in, long long in_stride, int nframes,
                                void *stream);
+/* CFft::FwdFFT / RevFFT (fft.cpp:416-426) of nframes frames of every row.
+ * The frame size is the object's (csdr_fft_batch_set_params, 512..65536).
+ * Frame k of row c is d_in[(c*in_stride + k*size) .. + size) complex fp32.
+ * Its transform goes to the same place in d_out with out_stride.
+ * Unnormalised; FwdFFT has the POSITIVE exponent, RevFFT the negative one, as csdr_fft_fwd / _rev.
+ * d_out == d_in with out_stride == in_stride transforms in place (what the reference does).
+ * Any other overlap of the two row blocks is refused.
+ * Bases 8-byte aligned, strides in complex samples, each >= nframes*size.
+ * Asynchronous on `stream`; nothing is allocated per call and the host waits for nothing.
+ * Reads and writes nothing of the display state (average, counters, overload flags, frame carry).
+ * The reference's FwdFFT also feeds the display average; this one does not.
+ * nframes == 0: CSDR_OK, no launch.
+ * CSDR_EINVAL before anything is written for NULL, nframes < 0, a short stride or a partial overlap. */
+int csdr_fft_batch_fwd(csdr_fft_batch *f, const float *d_in, long long in_stride, float *d_out,
+                       long long out_stride, int nframes, void *stream);
+int csdr_fft_batch_rev(csdr_fft_batch *f, const float *d_in, long long in_stride, float *d_out,
+                       long long out_stride, int nframes, void *stream);
+/* frames of every row that one pass of the 32768- and 65536-point transforms takes through the object's work buffer
+ * (sized in csdr_fft_batch_set_params); a longer call runs in groups of this many on the stream.  0 at the other sizes.
+ * Calls on one object share that buffer: keep them on one stream, or order them. */
+int csdr_fft_batch_plain_group(csdr_fft_batch *f);
 int csdr_fft_batch_get_ave(csdr_fft_batch *f, int channel, float *out);
 int csdr_fft_batch_get_total_count(csdr_fft_batch *f, int channel);
 int csdr_fft_batch_get_screen(csdr_fft_batch *f, int channel, int max_h, int max_w, double max_db,
