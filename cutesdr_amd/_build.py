@@ -255,6 +255,12 @@ TWREG3 = ("twreg3", ["-DK1_TWREG=3"])
 # ... and the build whose real-gain kernel rebuilds the outer-pass twiddle powers in every block (K1_PWRES = 0: the
 # instruction stream before the powers became resident), for the byte-for-byte test tests/test_fastfir_pwres_gpu.py
 PWRES0 = ("pwres0", ["-DK1_PWRES=0"])
+# ... and the build whose 16384-point kernels talk to HBM as they did before K1_RUNEND, K1_PROLOGUE, K1_TW2LDS and
+# K1_LDSPREAD (all four 0: that instruction stream line for line), for tests/test_fastfir_runend_gpu.py
+HBM_KNOBS = ("K1_RUNEND", "K1_PROLOGUE", "K1_TW2LDS", "K1_LDSPREAD")
+RUNEND0 = ("runend0", ["-D%s=0" % k for k in HBM_KNOBS])
+# ... and the build with all four at 1 (the product ships K1_RUNEND and K1_LDSPREAD; the other two stay tested through it)
+HBMALL = ("hbmall", ["-D%s=1" % k for k in HBM_KNOBS])
 
 
 if __name__ == "__main__":

@@ -510,6 +510,18 @@ int csdr__fastfir_last_kernel(const csdr_fastfir_batch *b, int *kernel, int *twr
     return CSDR_OK;
 }
 
+/* test-only hook, not part of the public ABI: both halves of the ping-pong history to the host, 2 x [channels][n/2] complex
+ * fp32 as they lie on the device, and *cur = the half the next call reads (the one the last call wrote) */
+int csdr__fastfir_read_history(csdr_fastfir_batch *b, float *out, int *cur)
+{
+    if (!b || !out || !cur) return CSDR_EINVAL;
+    if (!device_ok(b->device)) return CSDR_EHIP;
+    CSDR_HIP(hipDeviceSynchronize());
+    CSDR_HIP(hipMemcpy(out, b->d_hist, 2 * (size_t)b->channels * (b->n / 2) * 8, hipMemcpyDeviceToHost));
+    *cur = b->hist_cur;
+    return CSDR_OK;
+}
+
 /* test-only hook, not part of the public ABI: dump the LDS image after a pass */
 int csdr__dbg_fastfir_stage(csdr_fastfir_batch *b, int stage, float *d_dbg)
 {

@@ -100,6 +100,8 @@ int csdr__host_tw_factors(int k, int sign, double *m, double *tau)
 }
 int csdr__host_fastfir2_radix4(void) { return fastfir2_radix4(); }
 int csdr__host_fastfir2_pwres(void) { return fastfir2_pwres(); }
+int csdr__host_fastfir2_hbm_knobs(void) { return fastfir2_hbm_knobs(); }
+int csdr__host_fastfir2_gain_lds_bytes(void) { return fastfir2_gain_lds_bytes(); }
 
 int csdr__host_fastfir_design(int n, double flo, double fhi, double off, double fs, double *h_out)
 {

@@ -63,6 +63,25 @@ namespace csdr {
 #define K1_PWRES 1          // real-gain kernel: the outer-pass twiddle powers are built once in front of the block loop and stay
                             // in registers for the whole run (0: rebuilt at the top of every I3, as in every other kernel)
 #endif
+// How the 16384-point kernels talk to HBM over a block and over a run (HISTORY.md, "A block's HBM traffic spread
+// out"; every one at 0 gives the instruction stream before them, line for line).  Kernel time of bench.py's C3, parent 0.5739 ms:
+#ifndef K1_RUNEND
+#define K1_RUNEND 1         // the prefetch behind the last block of a run asks an EMPTY buffer range (zeros, no fetch), and the
+                            // history tail is stored from inside the call's last block instead of behind the block loop (alone
+                            // +0.2 %, within the visit's spread; beside K1_LDSPREAD -0.15 %; kept for the bytes it no longer moves)
+#endif
+#ifndef K1_PROLOGUE
+#define K1_PROLOGUE 0       // in front of the block loop every load is issued before the first wait: one round trip, not two
+                            // (alone 0.6 % SLOWER, beside K1_LDSPREAD -0.25 %, on top of K1_RUNEND and K1_LDSPREAD nothing: off)
+#endif
+#ifndef K1_TW2LDS
+#define K1_TW2LDS 0         // 1: the real-gain kernel with all sixteen pass twiddles in registers neither copies the table into
+                            // LDS nor reserves its 8 KiB (alone 0.8 % SLOWER, beside K1_LDSPREAD -0.3 %, on top of the two nothing: off)
+#endif
+#ifndef K1_LDSPREAD
+#define K1_LDSPREAD 1       // real-gain kernel: the next new half's eight loads as four pairs in front of F2, F3, I2 and I3 instead
+                            // of one burst in F1 (-1.1 % alone, -1.25 % with K1_RUNEND: every run under every parent run of two visits)
+#endif
 static_assert(K1_TWREG >= 0 && K1_TWREG <= 16, "K1_TWREG");
 
 #define CSDR_SB() __builtin_amdgcn_sched_barrier(0)
@@ -176,7 +195,6 @@ struct K1Cfg {
     static constexpr int VW = LOG2N == 12 ? 2 : (LOG2N == 11 ? 4 : 1);      // virtual workgroups per workgroup
     static constexpr int TV = Base::T;                                      // threads of one block
     static constexpr int T = VW * TV;
-    static constexpr int LDS_BYTES = (VW * Base::LDS_DATA + 1024) * 8;
 
     static constexpr int N = Base::N, R0 = Base::R0, G = Base::G, L = N / 2, HALF = R0 / 2;
     static_assert(R0 == 16 || R0 == 8 || R0 == 4 || R0 == 2, "the grouped outer pass is written for N = 2048 ... 16384");
@@ -199,6 +217,11 @@ struct K1Cfg {
     static constexpr int TWREG = RG ? K1_TWREG : 0;      // pass twiddles k1 = 1 ... TWREG of F2 / I2 that stay in registers
     static constexpr bool R4 = RG && K1_RADIX4 != 0;     // tail groups in the radix-4 form (other rounding order: this kernel only)
     static constexpr bool PW_RESIDENT = RG && K1_PWRES != 0;   // the outer-pass powers are built once per run, not once per block
+    static constexpr bool TW2_LDS = !(RG && TWREG == 16 && K1_TW2LDS != 0);      // some pass reads a twiddle from the table in LDS
+    static constexpr int LDS_BYTES = (VW * Base::LDS_DATA + (TW2_LDS ? 1024 : 0)) * 8;
+    static constexpr bool RUNEND = LOG2N == 14 && K1_RUNEND != 0;                // (the 16384-point kernels, real gains and complex H)
+    static constexpr bool PROLOGUE = LOG2N == 14 && K1_PROLOGUE != 0;
+    static constexpr bool LDSPREAD = RG && K1_LDSPREAD != 0;       // (on complex H the pairs would move the waits of H's fetches)
 
     // the register arrays a thread carries through the block loop
     using Y = v2f[G][R0];                   // F1 / I3: the R0 points of this thread's G columns
@@ -224,6 +247,10 @@ struct K1Thread {
     const v2f_h *tw1;               // FastFirArgs: the base twiddles, the block count, and the buffers of this channel
     int nblocks;
     rsrc_t r_in, r_h, r_out;
+    const void *in;                 // K1_RUNEND: this channel's input and its bytes (k1_next_half builds the range per block), the end
+    unsigned in_bytes;              // of this workgroup's run, and the history half the call's last block writes
+    int run_end;
+    rsrc_t r_hn;
 #ifdef K1_ABLATE
     v4f habl;
     v2f twabl;
@@ -281,17 +308,54 @@ template <int LOG2N> __device__ __forceinline__ void k1_store_out(const K1Thread
 }
 
 // one hop-half of samples: rows n1 = 0..HALF-1 of 1024 samples, this thread's G / 2 column pairs
-template <int LOG2N> __device__ __forceinline__ void k1_load_half(rsrc_t r, int voff, int soff, v2f (&dst)[16])
+// (K1_LDSPREAD: rows N1A ... N1B - 1 of it)
+template <int LOG2N, int N1A = 0, int N1B = K1Cfg<LOG2N>::HALF>
+__device__ __forceinline__ void k1_load_half(rsrc_t r, int voff, int soff, v2f (&dst)[16])
 {
     using Cfg = K1Cfg<LOG2N>;
 #pragma unroll
-    for (int n1 = 0; n1 < Cfg::HALF; n1++)
+    for (int n1 = N1A; n1 < N1B; n1++)
 #pragma unroll
         for (int pp = 0; pp < Cfg::G / 2; pp++) {
             v4f v = buf_load16_aux<K1_LDAUX>(r, voff + pp * Cfg::PSTEP_B, soff + n1 * 8192);
             dst[(2 * pp) * Cfg::HALF + n1] = v2f{v.x, v.y};
             dst[(2 * pp + 1) * Cfg::HALF + n1] = v2f{v.z, v.w};
         }
+}
+// Where block b's prefetch -- the new half of block b + 1 -- is asked for.  The block is one straight line of code, so the
+// loads are issued behind every block.  K1_RUNEND: behind the last block of a run they ask a buffer range of NO bytes, which
+// the range check answers with zeros and without a fetch (the offset stays one inside the input all the same); before,
+// they fetched block b + 1 where the input has one -- a run that ends inside the call -- and the last block again
+// where it has not, and nobody used the samples
+struct K1Next { rsrc_t r; int soff; };
+template <int LOG2N> __device__ __forceinline__ K1Next k1_next_half(const K1Thread &c, int b)
+{
+    using Cfg = K1Cfg<LOG2N>;
+    if constexpr (Cfg::RUNEND) {
+        const bool more = b + 1 < c.run_end;
+        return K1Next{make_rsrc(c.in, more ? c.in_bytes : 0u), (more ? b + 1 : b) * (Cfg::L * 8)};
+    } else {
+        return K1Next{c.r_in, (b + 1 < c.nblocks ? b + 1 : c.nblocks - 1) * (Cfg::L * 8)};
+    }
+}
+// The tail of this call's input is the overlap of the next call (fastfir.cpp:280-300): the new half of the call's last
+// block, written to the other half of the ping-pong history so no workgroup can still be reading it
+template <int LOG2N> __device__ __forceinline__ void k1_store_hist(rsrc_t r_hn, int voff, const K1Half &h)
+{
+    using Cfg = K1Cfg<LOG2N>;
+    constexpr int G = Cfg::G, HALF = Cfg::HALF;
+    v4f sv[8];
+#pragma unroll
+    for (int n1 = 0; n1 < HALF; n1++)
+#pragma unroll
+        for (int pp = 0; pp < G / 2; pp++)
+            sv[n1 * (G / 2) + pp] = store_operand(h.v[(2 * pp) * HALF + n1], h.v[(2 * pp + 1) * HALF + n1]);
+    CSDR_STORE_GROUP_BEGIN();
+#pragma unroll
+    for (int n1 = 0; n1 < HALF; n1++)
+#pragma unroll
+        for (int pp = 0; pp < G / 2; pp++) buf_store16(r_hn, voff + pp * Cfg::PSTEP_B, n1 * 8192, sv[n1 * (G / 2) + pp]);
+    CSDR_STORE_GROUP_END();
 }
 
 // outer-pass twiddles W_N^{n2 k0}, n2 = 2t+e: pw[e][k0], k0 = 1 ... PWN - 1.  On complex H (and at the smaller sizes) rebuilt
@@ -416,9 +480,17 @@ template <int LOG2N, bool RG> __device__ __forceinline__ void k1_pass_f1(const K
     }
     CSDR_SB();
     // block b+1's new half: into the registers of the old half, which the butterflies above have read
-    // (unconditional, so that the block stays one straight line of code: after the last block of the
-    // call the last block is fetched again, after the last of a run the samples are simply not used)
-    k1_load_half<LOG2N>(c.r_in, c.voff, (b + 1 < c.nblocks ? b + 1 : c.nblocks - 1) * (Cfg::L * 8), oldh.v);
+    // (unconditional, so that the block stays one straight line of code: k1_next_half).  K1_RUNEND: the call's last block
+    // first stores its new half -- the next call's history, whole in registers here -- while the CUs still have a block of
+    // arithmetic in front of them: a uniform branch that one block of the call's last run takes
+    if constexpr (Cfg::RUNEND) {
+        if (b + 1 == c.nblocks) k1_store_hist<LOG2N>(c.r_hn, c.voff, newh);
+        CSDR_SB();
+    }
+    if constexpr (!K1Cfg<LOG2N, RG>::LDSPREAD) {
+        const K1Next nx = k1_next_half<LOG2N>(c, b);
+        k1_load_half<LOG2N>(nx.r, c.voff, nx.soff, oldh.v);
+    }
     CSDR_SB();
     CSDR_PRIO(0);
     if constexpr (R0 == 16) k1_f1_rows16<LOG2N, RG>(c, y, pw);
@@ -794,7 +866,8 @@ template <int LOG2N, bool RG> __device__ __forceinline__ void fastfir_os2_body(c
 #endif
     if (ch >= a.channels || b0 >= b1) return;          // uniform per (virtual) workgroup
 
-    if constexpr (VW == 1)
+    // K1_PROLOGUE: the table's words are fetched with everything else and written behind the powers (tw2_words)
+    if constexpr (VW == 1 && Cfg::TW2_LDS && !Cfg::PROLOGUE)
         for (int i = t; i < 1024; i += T) tw2[i] = a.tw2[i];
 
     K1Thread c;
@@ -805,11 +878,27 @@ template <int LOG2N, bool RG> __device__ __forceinline__ void fastfir_os2_body(c
     c.r_h = make_rsrc(a.h + (long)ch * a.h_stride, N * 8u);
     const rsrc_t r_g = make_rsrc(a.gain + (long)ch * (a.h_stride / 2), N * 4u);      // (RG; half of H's bytes per filter)
     c.voff = t * 16;
+    if constexpr (Cfg::RUNEND) {
+        c.in = a.in + (long)ch * a.in_stride; c.in_bytes = (unsigned)a.nblocks * L * 8u; c.run_end = b1;
+        c.r_hn = make_rsrc(a.hist_next + (long)ch * L, L * 8u);
+    }
 
     typename Cfg::W1 w1;
     k1_load_w1<LOG2N>(c, w1);
     typename Cfg::Pw pw;
-    if constexpr (Cfg::R0 > 2) {
+    // K1_PROLOGUE: the powers are built behind the LAST load of this prologue, not here.  Everything the run needs is then
+    // asked for before the first wait, the base twiddles first: the vector-memory counter retires loads in the order of
+    // issue, so the powers wait for these alone and are built while the samples are in flight.  Before: base twiddles,
+    // wait, powers, and only then the rest -- two round trips at the one moment every workgroup of the launch asks at once
+    v2f tw2_words[1024 / T];
+    if constexpr (Cfg::PROLOGUE) {
+        if constexpr (Cfg::TW2_LDS) {
+#pragma unroll
+            for (int i = 0; i < 1024 / T; i++) tw2_words[i] = a.tw2[t + i * T];
+        }
+        CSDR_SB();
+    }
+    if constexpr (Cfg::R0 > 2 && !Cfg::PROLOGUE) {
 #pragma unroll
         for (int e = 0; e < G; e++) twiddle_powers<Cfg::PWN>(opaque(w1[e]), pw[e]);
     }
@@ -846,6 +935,15 @@ template <int LOG2N, bool RG> __device__ __forceinline__ void fastfir_os2_body(c
     typename Cfg::Twr twr;
 #pragma unroll
     for (int k1 = 1; k1 <= Cfg::TWREG; k1++) twr[k1 - 1] = a.tw2[32 * k1 + sn];
+    if constexpr (Cfg::PROLOGUE) {
+        CSDR_SB();
+#pragma unroll
+        for (int e = 0; e < G; e++) twiddle_powers<Cfg::PWN>(opaque(w1[e]), pw[e]);
+        if constexpr (Cfg::TW2_LDS) {
+#pragma unroll
+            for (int i = 0; i < 1024 / T; i++) tw2[t + i * T] = tw2_words[i];
+        }
+    }
     c.rowp = lds + 34 * t;
     c.outer = lds + lds_pad(2 * t);
 
@@ -860,24 +958,36 @@ template <int LOG2N, bool RG> __device__ __forceinline__ void fastfir_os2_body(c
     auto one_block = [&](const int b, K1Half &oldh, K1Half &newh) {
         CSDR_SB();
         CSDR_PRIO(1);
+        // K1_LDSPREAD: quarter Q of the next new half, asked for at the head of a later pass (into registers F1 has read)
+        auto spread = [&](auto Q) {
+            if constexpr (Cfg::LDSPREAD) {
+                const K1Next nx = k1_next_half<LOG2N>(c, b);
+                k1_load_half<LOG2N, Q.value * (HALF / 4), (Q.value + 1) * (HALF / 4)>(nx.r, c.voff, nx.soff, oldh.v);
+                CSDR_SB();
+            }
+        };
         k1_pass_f1<LOG2N, RG>(c, b, oldh, newh, pw);
         CSDR_STAMP(0);                             // F1 (and the loop-carried moves)
         k1_block_barrier<LOG2N>();
         CSDR_STAMP(1);                             // barrier after F1
         CSDR_PRIO(3);
+        spread(int_c<0>{});
         k1_pass_f2<LOG2N, RG>(c, x, hv, twr CSDR_STAMP_ARGS);
         CSDR_STAMP(2);                             // F2
         wave_sync();                                   // F2 -> F3 stays inside the half-wave that owns sub-transform sb
         CSDR_PRIO(2);
+        spread(int_c<1>{});
         k1_pass_f3<LOG2N, RG>(c, x, hv, pv);
         CSDR_STAMP(3);                             // F3 + H + I1
         wave_sync();
         CSDR_PRIO(0);
+        spread(int_c<2>{});
         k1_pass_i2<LOG2N, RG>(c, x, twr);
         CSDR_STAMP(4);                             // I2
         k1_block_barrier<LOG2N>();
         CSDR_STAMP(5);                             // barrier after I2
         CSDR_PRIO(3);
+        spread(int_c<3>{});
         k1_pass_i3<LOG2N, RG>(c, b, w1, pw);
         CSDR_STAMP(6);                             // I3
     };
@@ -908,7 +1018,8 @@ template <int LOG2N, bool RG> __device__ __forceinline__ void fastfir_os2_body(c
 #endif
     // the tail of this call's input is the overlap of the next call (fastfir.cpp:280-300);
     // written to the other half of the ping-pong history so no workgroup can still be reading it
-    if (b1 == a.nblocks) {
+    // (K1_RUNEND: the call's last block has stored it, k1_pass_f1)
+    if constexpr (!Cfg::RUNEND) if (b1 == a.nblocks) {
         const rsrc_t r_hn = make_rsrc(a.hist_next + (long)ch * L, L * 8u);
         v4f sv[8];
 #pragma unroll
@@ -951,16 +1062,18 @@ static hipError_t launch2_one(const FastFirArgs &a, hipStream_t stream, int *whi
     if (which) *which = (LOG2N == 14 && kernel != &fastfir_os2h_kernel) ? FASTFIR_KERNEL_PIPELINED_GAIN : FASTFIR_KERNEL_PIPELINED_H;
     // once per device and kernel (the attribute belongs to the device, and a process may drive several): the per-launch
     // call cost the per-datagram host form microseconds
+    // (the real-gain kernel reserves no twiddle table where it reads none: K1Cfg::TW2_LDS)
+    const int lds_bytes = kernel == &fastfir_os2h_kernel ? Cfg::LDS_BYTES : K1Cfg<LOG2N, LOG2N == 14>::LDS_BYTES;
     hipError_t e = kernel == &fastfir_os2h_kernel ? CSDR_MAX_LDS_ONCE(&fastfir_os2h_kernel, Cfg::LDS_BYTES)
-                                                  : CSDR_MAX_LDS_ONCE(&fastfir_os2_kernel<LOG2N>, Cfg::LDS_BYTES);
+                                                  : CSDR_MAX_LDS_ONCE(&fastfir_os2_kernel<LOG2N>, (K1Cfg<LOG2N, LOG2N == 14>::LDS_BYTES));
     if (e != hipSuccess) return e;
 #ifdef CSDR_WG_TRACE
     FastFirArgs b = a;
     b.trace = wgtrace_next();
-    hipLaunchKernelGGL(kernel, dim3((a.channels * a.runs + Cfg::VW - 1) / Cfg::VW), dim3(Cfg::T), Cfg::LDS_BYTES, stream, b);
+    hipLaunchKernelGGL(kernel, dim3((a.channels * a.runs + Cfg::VW - 1) / Cfg::VW), dim3(Cfg::T), lds_bytes, stream, b);
     return hipGetLastError();
 #endif
-    hipLaunchKernelGGL(kernel, dim3((a.channels * a.runs + Cfg::VW - 1) / Cfg::VW), dim3(Cfg::T), Cfg::LDS_BYTES, stream, a);
+    hipLaunchKernelGGL(kernel, dim3((a.channels * a.runs + Cfg::VW - 1) / Cfg::VW), dim3(Cfg::T), lds_bytes, stream, a);
     return hipGetLastError();
 }
 
@@ -978,6 +1091,13 @@ hipError_t fastfir2_launch(int log2n, const FastFirArgs &a, hipStream_t stream, 
 int fastfir2_twreg() { return K1_TWREG; }
 int fastfir2_radix4() { return K1Cfg<14, true>::R4 ? 1 : 0; }
 int fastfir2_pwres() { return K1Cfg<14, true>::PW_RESIDENT ? 1 : 0; }
+// bit 0: K1_RUNEND, 1: K1_PROLOGUE, 2: the real-gain kernel keeps no twiddle table in LDS (K1_TW2LDS and K1_TWREG = 16), 3: K1_LDSPREAD
+int fastfir2_hbm_knobs()
+{
+    using Cfg = K1Cfg<14, true>;
+    return (Cfg::RUNEND ? 1 : 0) | (Cfg::PROLOGUE ? 2 : 0) | (Cfg::TW2_LDS ? 0 : 4) | (Cfg::LDSPREAD ? 8 : 0);
+}
+int fastfir2_gain_lds_bytes() { return K1Cfg<14, true>::LDS_BYTES; }
 
 // Host mirror of the kernel's index algebra: thread t of pass F3 owns k0 = t >> 5 (sub-transform) and k1 = t & 31
 // (its row), and consumes H in the order its tail groups finish bins: float4 j = 2 i + h of thread t, half e,

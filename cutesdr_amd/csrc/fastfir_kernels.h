@@ -47,6 +47,12 @@ int fastfir2_twreg();
 int fastfir2_radix4();
 // 1 where that unit's real-gain kernel keeps the outer-pass twiddle powers in registers for the whole run (K1_PWRES)
 int fastfir2_pwres();
+// how that unit's 16384-point kernels talk to HBM: bit 0 K1_RUNEND (no fetch behind a run's last block, the history tail
+// stored inside the call's last block), bit 1 K1_PROLOGUE (one round trip in front of the block loop), bit 2 the real-gain
+// kernel keeps no twiddle table in LDS (K1_TW2LDS, at K1_TWREG = 16), bit 3 K1_LDSPREAD (a block's loads in four pairs);
+// and the dynamic LDS the real-gain kernel is launched with
+int fastfir2_hbm_knobs();
+int fastfir2_gain_lds_bytes();
 // natural-order spectrum bin of H slot (float4 index j*(N/32) + t, half e) of that kernel
 int fastfir2_bin_of(int log2n, int t, int j, int e);
 // natural-order spectrum bin of gain slot (float4 index i*(N/32) + t, component c): the same per-thread order, four
