@@ -261,6 +261,12 @@ HBM_KNOBS = ("K1_RUNEND", "K1_PROLOGUE", "K1_TW2LDS", "K1_LDSPREAD")
 RUNEND0 = ("runend0", ["-D%s=0" % k for k in HBM_KNOBS])
 # ... and the build with all four at 1 (the product ships K1_RUNEND and K1_LDSPREAD; the other two stay tested through it)
 HBMALL = ("hbmall", ["-D%s=1" % k for k in HBM_KNOBS])
+# ... and the diagnostic build of K4 that records the path every tile took through its guessed solves and can force the rare
+# ones (postchain.h: PC_CENSUS), for tests/test_pc_paths_gpu.py: the walk, the setter's unit and every unit that fills a PcArgs.
+# (One wave per SIMD for the lean walk too: with the census it needs 264 registers, and at the product's budget of 256 the
+# compiler's spill code for a 64-bit value does not assemble.  The allocation changes no arithmetic: the test holds the
+# build's words to the product's byte for byte.)
+PCCENSUS = ("pccensus", ["-DPC_CENSUS", "-DCSDR_PC_LEAN_WAVES_PER_EU=1"], ("postchain_kernels", "capi_core", "capi_postchain", "capi_demod", "capi_demod_batch"))
 
 
 if __name__ == "__main__":

@@ -56,6 +56,16 @@ int csdr__wgtrace_set(void *buf)
     return CSDR_OK;
 }
 #endif
+#ifdef PC_CENSUS
+/* diagnostic builds only (tests/test_pc_paths_gpu.py): the device buffer the post-chain walk leaves its per-tile path
+ * records in and reads its force word from (postchain.h; words [1] = capacity and [2] = force word set by the caller,
+ * the rest zero), or NULL to stop */
+int csdr__pc_census_set(void *buf)
+{
+    pc_census_host() = PcCensusHost{(unsigned *)buf, 0, 0, 0};
+    return CSDR_OK;
+}
+#endif
 /* internal (tests/test_reference_constants.py): the reference's named constants as this library's arithmetic uses them
  * (ref_constants.hpp) -- fills up to cap entries, returns how many there are */
 int csdr__constants(const char **names, double *values, int cap)

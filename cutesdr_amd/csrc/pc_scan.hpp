@@ -118,6 +118,14 @@ struct Wg {
     int t, lane, w;
     PcSync *S;
     mutable int bank = 0;                // exchange bank of the next workgroup scan (uniform)
+#ifdef PC_CENSUS
+    // diagnostic builds (postchain.h): the force word and what it asks of this tile, the tile's record so far, the rounds of
+    // the last AGC scan that converged -- uniform over the workgroup
+    mutable unsigned cen_force = 0, cen_rec = 0;
+    mutable int cen_limit = 0, cen_rounds = 0;
+    mutable bool cen_fail_overlap = false;
+    __device__ __forceinline__ void cen_or(unsigned bits) const { cen_rec |= (unsigned)__builtin_amdgcn_readfirstlane((int)bits); }   // (scalar registers)
+#endif
     __device__ __forceinline__ double (*xbank() const)[8] { double (*b)[8] = S->xch[bank]; bank ^= 1; return b; }
     // this thread's chunk of a tile of n samples: its first sample, and how many of its LC lie inside the tile
     __device__ __forceinline__ int base() const { return LC * t; }

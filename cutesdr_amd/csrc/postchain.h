@@ -74,7 +74,33 @@ enum { PC_DO_SMETER = 1, PC_DO_AGC = 2, PC_DO_DEMOD = 4, PC_STEREO = 8, PC_AGC_R
        PC_LEAN = 256 };                 // set by PcUnit::run: no S-meter in this launch, every AGC row has its peaks in pkbuf,
                                         // every FM row's squelch is deferred -- the walk may take its lean instantiation
 
+#ifdef PC_CENSUS
+// DIAGNOSTIC BUILDS ONLY (-DPC_CENSUS, cutesdr_amd/_build.py: PCCENSUS; tests/test_pc_paths_gpu.py): the walk records which
+// of its guessed solves every tile took, and can be sent down the rarely taken ones on purpose.  The production library
+// is compiled without the macro: no field, no instruction of this is in it.
+// The buffer (unsigned words), set with csdr__pc_census_set:
+//   [0] unused   [1] capacity in records (caller)   [2] force word (caller)
+//   [3] the last walk's instantiation: NW | LEAN << 8   [4] records written so far   [5] walks launched so far   [6..7] unused
+//   then records of 4 words, one per (walk, channel, tile of the call), in that order:
+//     [0] path (below)   [1] samples of the tile | (mode + 1) << 16 | NW << 20 | LEAN << 28   [2] walk number | channel << 16 | (output row & 255) << 24
+//     [3] the tile's ordinal in its channel since csdr__pc_census_set
+// path word:  bits 0-2 AGC: 0 not in this launch, 1 manual gain, 2 averagers solved by the scans, 3 walked (hang timer), 4 walked
+//             (the rounds ran out);  4-7 rounds of agc_ave_scan2 / of the first agc_ave_scan;  8-11 rounds of the second
+//             agc_ave_scan (NW = 1);  12-13 NW = 1: 1 the first scan failed, 2 the first succeeded and the second failed;
+//             16-17 PLL: 0 none, 1 pll_scan, 2 pll_overlap, 3 pll_walk;  18 pll_scan's own check failed;  19 a zero-sample
+//             code in the tile;  20 pll_scan skipped (forced);  21 pll_overlap skipped: PC_PLL_WARM_MAX;  22 skipped:
+//             PC_PLL_SEQ;  23 pll_overlap's mismatch forced
+// force word: bits 0-3 AGC round limit + 1 (0: PC_AGC_ROUNDS);  4 skip pll_scan;  8-15 m, 16-23 r: pll_overlap reports a
+//             mismatch on the tiles whose ordinal is r mod m (m = 0: never).  Forcing picks the path, never its arithmetic.
+constexpr unsigned long long PC_ARGS_TAG = 0x5043454e53555331ull;
+struct PcCensusArg { unsigned *buf = nullptr; int base = 0, tiles = 0, tile0 = 0, launch = 0, inst = 0, pad = 0; };
+struct PcCensusHost { unsigned *buf = nullptr; int next = 0, tiles = 0, launches = 0; };
+inline PcCensusHost &pc_census_host() { static PcCensusHost h; return h; }
+#endif
 struct PcArgs {
+#ifdef PC_CENSUS
+    unsigned long long layout_tag = PC_ARGS_TAG;   // first, so that a unit compiled without the macro is found out at the launch
+#endif
     PcChannel *chan;                    // [channels]
     float *agc_dly;                     // [channels][PC_AGC_RING] complex (2 floats each)
     float *agc_mag;                     // [channels][PC_AGC_RING]
@@ -91,6 +117,9 @@ struct PcArgs {
     int pre_bpw;                        // PC_AGC_PRE: bursts per workgroup of the peaks kernel
 #ifdef CSDR_WG_TRACE
     WgTraceArg trace;
+#endif
+#ifdef PC_CENSUS
+    PcCensusArg census;
 #endif
 };
 constexpr int PC_SQ_REC = 12;           // per burst: squelch-average map (2), low-pass state map (4 + 2), decision, start state (2)

@@ -486,7 +486,11 @@ __device__ __forceinline__ bool agc_ave_scan(const Wg<NW> &g, const float *pk, i
         pv[j] = j < cnt ? pk[base + j] : 0.f;
         if (j < cnt && (double)pv[j] > ave0) sel |= 1u << j;
     }
+#ifdef PC_CENSUS
+    for (int round = 0; round < g.cen_limit; round++) {
+#else
     for (int round = 0; round < PC_AGC_ROUNDS; round++) {
+#endif
         Aff1 m = Aff1::identity(), tot;
 #pragma unroll
         for (int j = 0; j < LC; j++) {
@@ -513,6 +517,9 @@ __device__ __forceinline__ bool agc_ave_scan(const Wg<NW> &g, const float *pk, i
 #pragma unroll
             for (int j = 0; j < LC; j++) if (j < cnt) emit(base + j, val[j]);
             ave = tot(ave0);
+#ifdef PC_CENSUS
+            g.cen_rounds = round + 1;
+#endif
             return true;
         }
         sel = nsel;
@@ -537,7 +544,11 @@ __device__ __forceinline__ bool agc_ave_scan2(const Wg<NW> &g, const float *pk, 
         if (j < cnt && (double)pv[j] > att0) sa |= 1u << j;
         if (j < cnt && (double)pv[j] > dec0) sd |= 1u << j;
     }
+#ifdef PC_CENSUS
+    for (int round = 0; round < g.cen_limit; round++) {
+#else
     for (int round = 0; round < PC_AGC_ROUNDS; round++) {
+#endif
         Both<Aff1, Aff1> m = Both<Aff1, Aff1>::identity(), tot;
 #pragma unroll
         for (int j = 0; j < LC; j++) {
@@ -566,6 +577,9 @@ __device__ __forceinline__ bool agc_ave_scan2(const Wg<NW> &g, const float *pk, 
 #pragma unroll
             for (int j = 0; j < LC; j++) if (j < cnt) emit(base + j, va[j], vd[j]);
             att = tot.p(att0); dec = tot.q(dec0);
+#ifdef PC_CENSUS
+            g.cen_rounds = round + 1;
+#endif
             return true;
         }
         sa = na; sd = nd;
@@ -602,6 +616,14 @@ __device__ __forceinline__ bool pll_scan(const Wg<NW> &g, const float *th, int n
 {
     constexpr int LC = Wg<NW>::LC;
     const int base = g.base(), cnt = g.count(n);
+#ifdef PC_CENSUS
+    if (g.cen_force & 16u) {                                          // skipped: the record still says whether the tile holds a zero code
+        bool cen_zero = false;
+        for (int j = 0; j < LC; j++) if (j < cnt) cen_zero = cen_zero || pll_theta_is_zero_code(th[base + j]);
+        g.cen_or(1u << 20 | (g.any(cen_zero) ? 1u << 19 : 0u));
+        return false;
+    }
+#endif
     float tv[LC];
     bool zero = false;
 #pragma unroll
@@ -653,7 +675,13 @@ __device__ __forceinline__ bool pll_scan(const Wg<NW> &g, const float *th, int n
             x0 = x0 + f + alpha * e;
         }
     }
+#ifdef PC_CENSUS
+    g.cen_or((g.any(bad) ? 1u << 18 : 0u) | (g.any(zero) ? 1u << 19 : 0u));
+#endif
     if (g.any(bad || zero)) return false;
+#ifdef PC_CENSUS
+    g.cen_or(1u << 16);
+#endif
     double nph, nfr;
     tot(ph, fr, nph, nfr);
     ph = nph - rint(nph); fr = nfr;
@@ -709,7 +737,13 @@ __device__ __forceinline__ bool pll_overlap(const Wg<NW> &g, const float *th, in
     }
     const int tl = n > 0 ? (n - 1) / LC : 0;
     const double pe = xp[tl], fe = xf[tl];
+#ifdef PC_CENSUS
+    if (g.cen_fail_overlap) { g.cen_rec |= 1u << 23; bad = true; }
+#endif
     if (g.any(bad)) return false;
+#ifdef PC_CENSUS
+    g.cen_or(2u << 16);
+#endif
     if (n > 0) { ph = pe; fr = fe; }
     return true;
 }
@@ -720,6 +754,9 @@ template <int NW, class F>
 __device__ __forceinline__ void pll_walk(const Wg<NW> &g, const float *th, int n, double alpha, double beta, double lo, double hi,
                                          double sgn, double &ph, double &fr, F emit)
 {
+#ifdef PC_CENSUS
+    g.cen_or(3u << 16);
+#endif
     g.sync();
     if (g.t == 0) {
         const double lo_t = lo * kInvTwoPiD, hi_t = hi * kInvTwoPiD;
@@ -968,6 +1005,9 @@ __device__ __forceinline__ void pc_agc_stage(const PcThread<NW, LEAN> &c, PcStat
     constexpr int NT = Wg<NW>::NT, LC = Wg<NW>::LC;
     PcLds &S = c.S; PcAgc &agc = st.agc; const Wg<NW> &g = c.g; const int t = c.t;
     if (!c.do_agc) return;
+#ifdef PC_CENSUS
+    if (!agc.on) g.cen_or(1u);
+#endif
     if (!agc.on) {
         const float gm = (float)agc.manual_gain;
         for (int i = t; i < n; i += NT) { x[i].x *= gm; x[i].y *= gm; }
@@ -998,12 +1038,25 @@ __device__ __forceinline__ void pc_agc_stage(const PcThread<NW, LEAN> &c, PcStat
             if constexpr (NW == 4) {           // (16 samples per thread would not fit the registers twice)
                 if (ok) ok = agc_ave_scan2(g, S.pk, n, agc.att_rise, agc.att_fall, agc.dec_rise, agc.dec_fall, att, dec,
                                            [&](int i, double va, double vd) { S.pk[i] = fmaxf((float)va, (float)vd); });
+#ifdef PC_CENSUS
+                if (ok) g.cen_or(2u | (unsigned)g.cen_rounds << 4);
+#endif
             } else {
                 if (ok) ok = agc_ave_scan(g, S.pk, n, agc.att_rise, agc.att_fall, att,
                                           [&](int i, double v) { S.w2[i] = (float)v; });
+#ifdef PC_CENSUS
+                const bool cen_first = ok;
+                if (!agc.hang) g.cen_or(ok ? (unsigned)g.cen_rounds << 4 : 1u << 12);
+#endif
                 if (ok) ok = agc_ave_scan(g, S.pk, n, agc.dec_rise, agc.dec_fall, dec,
                                           [&](int i, double v) { S.pk[i] = fmaxf(S.w2[i], (float)v); });
+#ifdef PC_CENSUS
+                if (cen_first) g.cen_or(ok ? (2u | (unsigned)g.cen_rounds << 8) : 2u << 12);
+#endif
             }
+#ifdef PC_CENSUS
+            if (!ok) g.cen_or(agc.hang ? 3u : 4u);
+#endif
             if (ok) { agc.attack_ave = att; agc.decay_ave = dec; }
             else {
                 g.sync();
@@ -1098,6 +1151,9 @@ __device__ __forceinline__ void pc_fm_tile(const PcThread<NW, LEAN> &c, PcState 
     const auto to_au = [&](int i, double, double f) { au[i] = (float)f; };           // NCO frequency, turns per sample
     double ph = st.fm_ph * kInvTwoPiD, fr = st.fm_fr * kInvTwoPiD;                   // (the solvers move them only when they succeed)
     bool scanned = pll_scan(g, th, n, F.alpha, F.beta, F.lo * kInvTwoPiD, F.hi * kInvTwoPiD, ph, fr, S.pm, to_au);
+#ifdef PC_CENSUS
+    if (!scanned) g.cen_or((c.fm_warm > PC_PLL_WARM_MAX ? 1u << 21 : 0u) | ((a.flags & PC_PLL_SEQ) ? 1u << 22 : 0u));
+#endif
     if (!scanned && c.fm_warm <= PC_PLL_WARM_MAX && !(a.flags & PC_PLL_SEQ)) {       // unlocked: overlapped exact walks, verified
         g.sync();
         ph = wrap_turn(ph);
@@ -1270,6 +1326,10 @@ void postchain_kernel(PcArgs a)
     extern __shared__ __attribute__((aligned(16))) unsigned char pc_smem[];
     PcLds &S = *reinterpret_cast<PcLds *>(pc_smem);
     const int ch = blockIdx.x;
+#ifdef PC_CENSUS
+    unsigned *const cen = a.census.buf;
+    if (cen && ch == 0 && threadIdx.x == 0) { cen[3] = (unsigned)a.census.inst; cen[4] = (unsigned)(a.census.base + a.channels * a.census.tiles); cen[5] = (unsigned)a.census.launch; }
+#endif
     // A channel's bursts are a sequential walk: this kernel is bound by its own latency, not by throughput, and
     // in the batch chain it shares CUs with the down-converter of other groups / the next call, whose 12-16 waves
     // per CU would otherwise take most issue slots.  Highest issue priority for these few waves costs the
@@ -1281,6 +1341,12 @@ void postchain_kernel(PcArgs a)
     PcState st{C.sm, C.agc, C.am.z1, C.sam.z1, C.sam.y1, C.sam.phase, C.sam.freq, C.fm.phase, C.fm.freq, C.fm.err_dc, C.fm.sq_ave,
                C.fm.squelched, C.fm.lp, 0.0, 0.0};
     PcRegs<NW> r;
+#ifdef PC_CENSUS
+    const unsigned cen_force = cen ? (unsigned)__builtin_amdgcn_readfirstlane((int)cen[2]) : 0u;
+    c.g.cen_force = cen_force;
+    c.g.cen_limit = (cen_force & 15u) ? (int)(cen_force & 15u) - 1 : PC_AGC_ROUNDS;
+    int cen_tile = 0;
+#endif
     pc_stage_histories(c, st);
     if (c.kPrefetch && c.total > 0) pc_fetch(c, r, 0, a.burst < PT ? a.burst : PT);
 #ifdef PC_PROFILE
@@ -1293,6 +1359,11 @@ void postchain_kernel(PcArgs a)
             const int n = (a.burst - t0) < PT ? (a.burst - t0) : PT;
             const long gi = (long)b * a.burst + t0;
             float2 *x = S.dl + ((c.do_agc && st.agc.on) ? c.D : 0);       // tile samples (AGC: behind the delay history)
+#ifdef PC_CENSUS
+            c.g.cen_rec = 0;
+            { const unsigned fm = cen_force >> 8 & 255u, fr = cen_force >> 16 & 255u;
+              c.g.cen_fail_overlap = fm != 0 && (unsigned)(a.census.tile0 + cen_tile) % fm == fr; }
+#endif
             pc_load_tile(c, r, x, n, gi, t0);
             PC_TICK(0);
             pc_smeter_stage(c, st, x, n);
@@ -1310,6 +1381,17 @@ void postchain_kernel(PcArgs a)
                 if (c.mode == PC_MODE_FM) pc_fm_tile(c, st, r, x, n, gi);
                 else pc_sam_tile(c, st, x, n, gi);
             }
+#ifdef PC_CENSUS
+            if (cen && c.t == 0) {                                        // this tile's record: one 16-byte vector store
+                const int idx = a.census.base + ch * a.census.tiles + cen_tile;
+                const int orow = a.out_rows ? a.out_rows[ch] : ch;
+                if (idx >= 0 && (unsigned)idx < cen[1])
+                    reinterpret_cast<uint4 *>(cen + 8)[idx] = make_uint4(c.g.cen_rec, (unsigned)n | (unsigned)(c.mode + 1) << 16 | (unsigned)a.census.inst << 20,
+                        (unsigned)(a.census.launch & 0xffff) | (unsigned)(ch & 255) << 16 | (unsigned)(orow & 255) << 24,
+                        (unsigned)(a.census.tile0 + cen_tile));
+            }
+            cen_tile++;
+#endif
         }
         pc_fm_burst_end(c, st, r, b);
     }
@@ -1379,6 +1461,9 @@ void agc_peaks_kernel(PcArgs a)
 
 hipError_t agc_peaks_launch(const PcArgs &a, hipStream_t stream)
 {
+#ifdef PC_CENSUS
+    if (a.layout_tag != PC_ARGS_TAG) return hipErrorInvalidValue;   // the caller's unit was compiled without the macro
+#endif
     static_assert(sizeof(PreLds) <= 40 * 1024, "four peaks workgroups per CU");
     PcArgs b = a;
     b.pre_bpw = pc_bursts_per_wg(a);
@@ -1446,6 +1531,9 @@ void smeter_call_kernel(PcArgs a)
 }
 hipError_t smeter_call_launch(const PcArgs &a, hipStream_t stream)
 {
+#ifdef PC_CENSUS
+    if (a.layout_tag != PC_ARGS_TAG) return hipErrorInvalidValue;   // the caller's unit was compiled without the macro
+#endif
     hipLaunchKernelGGL(smeter_call_kernel, dim3(a.channels), dim3(256), 0, stream, pc_traced(a));
     return hipGetLastError();
 }
@@ -1642,6 +1730,9 @@ void fm_squelch_apply_kernel(PcArgs a)
 
 hipError_t fm_squelch_launch(const PcArgs &a, hipStream_t stream)
 {
+#ifdef PC_CENSUS
+    if (a.layout_tag != PC_ARGS_TAG) return hipErrorInvalidValue;   // the caller's unit was compiled without the macro
+#endif
     static_assert(sizeof(SqLds) <= 20 * 1024, "eight squelch workgroups per CU");
     PcArgs b = a;
     b.sq_bpw = pc_bursts_per_wg(a);
@@ -1712,11 +1803,25 @@ static hipError_t pc_launch_nw(const PcArgs &a, hipStream_t stream)
         hipError_t e = CSDR_MAX_LDS_ONCE((&postchain_kernel<NW, LEAN>), sizeof(PcLds));
         if (e != hipSuccess) return e;
     }
+#ifdef PC_CENSUS
+    {   // this walk's place in the census buffer: channels x tiles records behind those of the walks before it
+        PcCensusHost &h = pc_census_host();
+        const int tiles = a.nbursts * ((a.burst + PT - 1) / PT);
+        PcArgs b = a;
+        b.census = PcCensusArg{h.buf, h.next, tiles, h.tiles, h.launches + 1, NW | (LEAN ? 1 : 0) << 8, 0};
+        if (h.buf) { h.next += a.channels * tiles; h.tiles += tiles; h.launches++; }
+        hipLaunchKernelGGL((postchain_kernel<NW, LEAN>), dim3(a.channels), dim3(64 * NW), sizeof(PcLds), stream, pc_traced(b));
+        return hipGetLastError();
+    }
+#endif
     hipLaunchKernelGGL((postchain_kernel<NW, LEAN>), dim3(a.channels), dim3(64 * NW), sizeof(PcLds), stream, pc_traced(a));
     return hipGetLastError();
 }
 hipError_t postchain_launch(const PcArgs &a, hipStream_t stream)
 {
+#ifdef PC_CENSUS
+    if (a.layout_tag != PC_ARGS_TAG) return hipErrorInvalidValue;   // the caller's unit was compiled without the macro
+#endif
     // waves per channel: four when the channels alone cannot fill the chip, else one; CSDR_POSTCHAIN_WAVES=1|4 overrides
     static int forced = -1;
     if (forced < 0) { const char *env = getenv("CSDR_POSTCHAIN_WAVES"); forced = env ? atoi(env) : 0; }

@@ -1,8 +1,14 @@
 """Seeded differential sweep of the sample-rate stages against the oracle: random AGC settings
 (hang on/off, threshold, slope, decay, sample rate), random signal envelopes (steps, fades,
 bursts, silence) and random call lengths.  The AGC averagers and the PLLs are solved per tile
-under a guess that is verified afterwards; this sweep is there to hit the guesses' failure and
-re-entry paths with inputs nobody hand-picked."""
+under a guess that is verified afterwards.  What this sweep reaches of that, counted under the path
+census (tests/test_pc_paths_gpu.py::test_what_the_randomized_sweeps_reach, table in DESIGN.md
+section 6): the AGC tiles with the hang off all converge, in 1 (375 tiles), 2 (115) or 3 (1) rounds
+of guessed selectors -- the walk behind a failed guess runs only where the hang timer asks for it
+(90 tiles); FM tiles are solved by pll_scan (102) or, where its check fails, by pll_overlap (90),
+never walked by one thread; SAM tiles by pll_scan (90) or pll_walk (102); no tile holds a
+zero-sample code.  The failure and re-entry paths this sweep does not reach are run on purpose by
+tests/test_pc_paths_gpu.py."""
 import numpy as np
 import pytest
 from util_signals import FULL_SCALE
