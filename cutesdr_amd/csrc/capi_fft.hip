@@ -215,14 +215,14 @@ struct FrameSrc {
 };
 
 // PutInDisplayFFT of nframes frames of `size` samples per channel, back to back in each row (src == nullptr), or as src
-// says; asynchronous.  clear_over = false: a later launch of the same call -- the overload flag stays what the call's
-// earlier frames left.
+// says; asynchronous.  nframes >= 1.  The overload flag is the last put frame's (m_Overload = FALSE at the top of every
+// PutInDisplayFFT, fft.cpp:270): every launch clears the words and its kernels set them for its last frame alone, so
+// of the launches of one stream call the one that holds the last used frame decides.
 static int fft_put_frames(csdr_fft_batch *f, const float *d_in, long long in_stride, int nframes, void *stream,
-                          const FrameSrc *src = nullptr, bool clear_over = true)
+                          const FrameSrc *src = nullptr)
 {
     f->last_stream = (hipStream_t)stream; f->have_stream = true;
-    if (clear_over)
-        CSDR_HIP(hipMemsetAsync(f->d_over, 0, sizeof(int) * f->channels, (hipStream_t)stream));   // m_Overload = FALSE
+    CSDR_HIP(hipMemsetAsync(f->d_over, 0, sizeof(int) * f->channels, (hipStream_t)stream));
     SpectrumArgs a;
     a.in = d_in; a.in_stride = in_stride; a.win = f->d_win; a.tw1 = f->d_tw1; a.tw2 = f->d_tw2;
     a.sum = f->d_sum; a.pwr = f->d_pwr; a.ave = f->d_ave; a.counters = f->d_cnt; a.overload = f->d_over;
@@ -299,7 +299,6 @@ static int fft_put_stream(csdr_fft_batch *f, const float *d_in, long long in_str
     a.nb_state = blank ? (const NbChan *)blank->state : nullptr; a.nb_hist = blank ? blank->hist : nullptr;
     long long start = p.start;
     int left = p.count;
-    bool clear_over = true;
     auto in_place = [&](int k) { return !blank && !wire.pk && !d_dc && start >= 0 && (k == 1 || p.step == N); };
     if (left > 0 && !in_place(left) && (start < first_loaded || !loaders)) {
         int ng = left;
@@ -309,14 +308,14 @@ static int fft_put_stream(csdr_fft_batch *f, const float *d_in, long long in_str
         CSDR_HIP(display_gather_launch(a, start, p.step, ng, N, f->d_stage, st));
         const int rc = fft_put_frames(f, f->d_stage, (long long)ng * N, ng, stream);
         if (rc) return rc;
-        clear_over = false; start += (long long)ng * p.step; left -= ng;
+        start += (long long)ng * p.step; left -= ng;
     }
     if (left > 0) {
         int rc;
-        if (in_place(left)) rc = fft_put_frames(f, d_in + 2 * start, in_stride, left, stream, nullptr, clear_over);
+        if (in_place(left)) rc = fft_put_frames(f, d_in + 2 * start, in_stride, left, stream);
         else {
             const FrameSrc src{start, p.step, d_dc, wire.pk, wire.chan_stride, wire.pkt_len, blank};
-            rc = fft_put_frames(f, d_in, in_stride, left, stream, &src, clear_over);
+            rc = fft_put_frames(f, d_in, in_stride, left, stream, &src);
         }
         if (rc) return rc;
     }

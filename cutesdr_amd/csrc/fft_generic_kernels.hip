@@ -28,14 +28,15 @@ __global__ void stockham_pass_kernel(const v2f *x, v2f *y, int n0, int n, int s,
     y[q + s * (2 * p + 1)] = cmul(a - b, w);
 }
 
-// frame f of every channel: window, I/Q swap (fft.cpp:280-281), overload flag (fft.cpp:275-276)
+// frame f of every channel: window, I/Q swap (fft.cpp:280-281), overload flag (fft.cpp:270, :275-276: the flag is
+// the last put frame's, so only the launch's last frame writes the word the launcher cleared)
 __global__ void spec_prep_kernel(SpectrumArgs a, int n, int frame, v2f *work, long wstride)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, ch = blockIdx.y;
     if (i >= n) return;
     const v2f s = reinterpret_cast<const v2f *>(a.in)[(long)ch * a.in_stride + (long)frame * n + i];
     const float w = a.win[i];
-    if (s.x > refc::FFT_OVER_LIMIT_F) a.overload[ch] = 1;
+    if (frame == a.nframes - 1 && s.x > refc::FFT_OVER_LIMIT_F) a.overload[ch] = 1;
     work[(long)ch * wstride + i] = v2f{w * s.y, w * s.x};
 }
 __global__ void spec_count_kernel(SpectrumArgs a)

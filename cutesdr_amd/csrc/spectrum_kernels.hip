@@ -367,6 +367,7 @@ __device__ __forceinline__ void spectrum_frames(const SpectrumArgs &a)
     if (f0 < f1) fetch(f0);
     for (int f = f0; f < f1; f++) {
         v2f x[P];
+        over = 0;                                                 // m_Overload = FALSE at the top of every put, fft.cpp:270
         static_for<0, P>([&](auto Q) {
             constexpr int q = Q.value;
             v2f s;
@@ -402,7 +403,9 @@ __device__ __forceinline__ void spectrum_frames(const SpectrumArgs &a)
         });
     }
     if (t == 0 && a.nparts == 1) { a.counters[2 * ch] = ave_count; a.counters[2 * ch + 1] = total; }
-    if (over) a.overload[ch] = 1;
+    // the flag is the last put frame's: `over` is that of the group's last frame, and only the group that holds the
+    // call's last frame writes it (the launcher cleared the word)
+    if (over && part == a.nparts - 1) a.overload[ch] = 1;
 }
 
 template <int LOG2N, class Ld = RowLoad>

@@ -2,7 +2,8 @@
 against the fp64 oracle, through the C ABI.  K3 tolerance: 0.01 dB on every bin within 60 dB of
 the frame's strongest bin, 0.5 dB down to 90 dB below it, 2 dB on every other bin above -150 dBFS
 (an fp32 transform has its rounding floor ~125 dB below the strongest component, so weak bins beside a
-strong carrier cannot hold 0.01 dB); plain transforms 2e-5 * N * max|x|; resampler 1e-5 * max|x|, counts exact,
+strong carrier cannot hold 0.01 dB; the bin-resolving rule of the display spectrum is tests/test_spectrum_bins_gpu.py's);
+plain transforms 2e-5 * N * max|x| and, per bin on a flat probe, the rule of fft_plain_ref.py; resampler 1e-5 * max|x|, counts exact,
 int16 outputs within 1 LSB."""
 import numpy as np
 import pytest
@@ -86,6 +87,14 @@ def test_plain_transforms(oracle, n):
     assert np.abs(f.RevFFT(x) - oracle.fft(x, -1)).max() <= tol
     back = f.RevFFT(f.FwdFFT(x)) / n                          # Rev(Fwd(x)) = N x
     assert np.abs(back - x).max() <= 2e-5 * np.abs(x).max() * 20
+    # the one-object launch path (csdr_fft_fwd / _rev) under the batch form's rule: E <= m E_y per bin on the flat probe
+    import fft_plain_ref as P
+    for i in range(2):
+        seed = P.seed_of(n, 900 + i)
+        p = P.probe(n, seed).astype(np.complex128)
+        for sign, fn in ((+1, f.FwdFFT), (-1, f.RevFFT)):
+            r = P.check_frame(fn(p), n, seed, sign, "CFft one-object")
+            print("CFft one-object n=%d sign=%+d seed=%d: E / E_y = %.2f (m = %g)" % (n, sign, seed, r, P.margin(n)))
 
 
 def test_fft_batch_frames_and_channels(oracle):
