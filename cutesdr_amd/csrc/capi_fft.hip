@@ -46,7 +46,24 @@ struct csdr_fft_batch {
     // tables and its intermediate, plain_group frames of every row; display calls never touch them
     float *d_twp = nullptr, *d_pwork = nullptr;
     int plain_group = 0;
+    // the row form: averaging length (rows_ave) and skip value, counter, gate and ready (rows_disp) per row; the frame
+    // position ds.pos and the carry stay one per object.  While a flag is clear, its rows follow ave_size / ds (copied in
+    // front of a row-form put).  rate_r: each row's m_MaxDisplayRate, for set_params.
+    bool rows_ave = false, rows_disp = false;
+    std::vector<DisplayState> rs, rs_next;
+    std::vector<int> ave_r, rate_r;
+    // the frames each row used in the last put: `emits` after a row-form put, emit_all of every row after a uniform one
+    std::vector<int> emits, emits_next;
+    int emit_all = 0; bool emits_by_row = false;
+    // the active-row tables of a row-form put travel as the plotter's parameters do (capi_plotter.hip): a ring of pinned
+    // slots, [2][channels] entries each (gathered launch, loaded launch), copied on the caller's stream
+    static constexpr int kTabRing = 16;
+    SpecRow *h_tab[kTabRing] = {}, *d_tab[kTabRing] = {};
+    hipEvent_t tab_ev[kTabRing] = {};
+    bool tab_busy[kTabRing] = {};
+    int tab_next = 0;
 };
+static bool fft_row_form(const csdr_fft_batch *f) { return f->rows_ave || f->rows_disp; }
 
 // device -> host behind the object's own work: on the stream of its last put_display (until round 5: hipDeviceSynchronize)
 static int fft_read(csdr_fft_batch *f, void *dst, const void *src, size_t bytes)
@@ -83,6 +100,60 @@ static int fft_reset(csdr_fft_batch *f)
     CSDR_HIP(hipMemset(f->d_ave, 0, nb));
     CSDR_HIP(hipMemset(f->d_sum, 0, nb));
     CSDR_HIP(hipMemset(f->d_cnt, 0, sizeof(int) * 2 * f->channels));
+    return CSDR_OK;
+}
+
+// one row's part of ResetFFT
+static int fft_reset_row(csdr_fft_batch *f, int row)
+{
+    const size_t nb = (size_t)f->size * 4;
+    CSDR_HIP(hipMemset(f->d_ave + (size_t)row * f->size, 0, nb));
+    CSDR_HIP(hipMemset(f->d_sum + (size_t)row * f->size, 0, nb));
+    CSDR_HIP(hipMemset(f->d_cnt + 2 * row, 0, sizeof(int) * 2));
+    return CSDR_OK;
+}
+
+// into the row form: the table ring on first use, and the rows of a still-uniform half take the object's values
+static int fft_rows_enter(csdr_fft_batch *f, bool ave, bool disp)
+{
+    if (!f->h_tab[0]) {
+        if (!device_ok(f->device)) return CSDR_EHIP;
+        const size_t bytes = sizeof(SpecRow) * 2 * (size_t)f->channels;
+        for (int i = 0; i < csdr_fft_batch::kTabRing; i++) {
+            if (!f->h_tab[i] && hipHostMalloc((void **)&f->h_tab[i], bytes, hipHostMallocDefault) != hipSuccess)
+                return fail(CSDR_ENOMEM, "hipHostMalloc(%zu) failed", bytes);
+            if (!f->d_tab[i]) CSDR_HIP(hipMalloc((void **)&f->d_tab[i], bytes));
+            if (!f->tab_ev[i]) CSDR_HIP(hipEventCreateWithFlags(&f->tab_ev[i], hipEventDisableTiming));
+        }
+    }
+    if (ave && !f->rows_ave) { f->ave_r.assign((size_t)f->channels, f->ave_size); f->rows_ave = true; }
+    if (disp && !f->rows_disp) {
+        f->rs.assign((size_t)f->channels, f->ds);
+        f->rate_r.assign((size_t)f->channels, f->disp_rate);
+        f->rows_disp = true;
+    }
+    return CSDR_OK;
+}
+// a free slot of the table ring: waits, on that put's event only, when the put kTabRing before has not finished
+static int fft_tab_slot(csdr_fft_batch *f, int *slot)
+{
+    *slot = f->tab_next;
+    if (f->tab_busy[*slot]) { CSDR_HIP(hipEventSynchronize(f->tab_ev[*slot])); f->tab_busy[*slot] = false; }
+    return CSDR_OK;
+}
+static int fft_tab_sent(csdr_fft_batch *f, int slot, hipStream_t st)
+{
+    CSDR_HIP(hipEventRecord(f->tab_ev[slot], st));
+    f->tab_busy[slot] = true;
+    f->tab_next = (slot + 1) % csdr_fft_batch::kTabRing;
+    return CSDR_OK;
+}
+// row < 0: every row (the plotter's view < 0); [lo, hi) or CSDR_EINVAL with nothing changed
+static int fft_row_range(csdr_fft_batch *f, int row, int *lo, int *hi)
+{
+    if (!f) return have_device() ? fail(CSDR_EINVAL, "bad handle") : CSDR_EHIP;      // (an object has a device)
+    if (row >= f->channels) return fail(CSDR_EINVAL, "row %d of %d", row, f->channels);
+    *lo = row < 0 ? 0 : row; *hi = row < 0 ? f->channels : row + 1;
     return CSDR_OK;
 }
 
@@ -156,8 +227,12 @@ csdr_fft_batch *csdr_fft_batch_create(int device, int channels)
     f->size = 1024; f->last_size = 0; f->ave_size = 1; f->invert = 0; f->db_comp = 0.0; f->fs = 1000;
     f->d_win = f->d_tw1 = f->d_tw2 = f->d_sum = f->d_pwr = f->d_ave = f->d_work = nullptr;
     f->d_cnt = nullptr; f->d_over = nullptr;
+    f->rs.assign((size_t)channels, f->ds); f->rs_next = f->rs;
+    f->ave_r.assign((size_t)channels, 1); f->rate_r.assign((size_t)channels, 0);
+    f->emits.assign((size_t)channels, 0); f->emits_next = f->emits;
     if (hipMalloc((void **)&f->d_cnt, sizeof(int) * 2 * channels) != hipSuccess ||
         hipMalloc((void **)&f->d_over, sizeof(int) * channels) != hipSuccess ||
+        hipMemset(f->d_over, 0, sizeof(int) * channels) != hipSuccess ||     // (the row form clears a word with the row's frames only)
         fft_set_params(f, 2048, 0, 0.0, 1000) != CSDR_OK) {          // ctor, fft.cpp:41-62
         csdr_fft_batch_destroy(f);
         return nullptr;
@@ -174,6 +249,12 @@ void csdr_fft_batch_destroy(csdr_fft_batch *f)
     if (f->d_scr) (void)hipFree(f->d_scr);
     if (f->d_part) (void)hipFree(f->d_part);
     if (f->d_stage) (void)hipFree(f->d_stage);
+    for (int i = 0; i < csdr_fft_batch::kTabRing; i++) {
+        if (f->tab_busy[i]) (void)hipEventSynchronize(f->tab_ev[i]);      // its put still reads the slot
+        if (f->tab_ev[i]) (void)hipEventDestroy(f->tab_ev[i]);
+        if (f->h_tab[i]) (void)hipHostFree(f->h_tab[i]);
+        if (f->d_tab[i]) (void)hipFree(f->d_tab[i]);
+    }
     delete f;
 }
 int csdr_fft_batch_set_params(csdr_fft_batch *f, int size, int invert, double db_comp, double fs)
@@ -187,14 +268,46 @@ int csdr_fft_batch_set_params(csdr_fft_batch *f, int size, int invert, double db
     f->ds.pos = 0;
     if (fs > 0) f->disp_fs = fs;
     if (f->disp_rate > 0) { f->ds.skip = display_skip_value(f->disp_fs, f->size, f->disp_rate); f->ds.counter = 0; }
+    if (f->rows_disp)                                    // every row from ITS stored rate
+        for (int r = 0; r < f->channels; r++)
+            if (f->rate_r[r] > 0) { f->rs[r].skip = display_skip_value(f->disp_fs, f->size, f->rate_r[r]); f->rs[r].counter = 0; }
     return CSDR_OK;
 }
 int csdr_fft_batch_set_ave(csdr_fft_batch *f, int ave)
-{   // CFft::SetFFTAve (fft.cpp:103-113)
+{   // CFft::SetFFTAve (fft.cpp:103-113); every row, and the averaging half of the row form ends
     if (!f) return fail(CSDR_EINVAL, "bad handle");
     if (!device_ok(f->device)) return CSDR_EHIP;
     if (f->ave_size != ave) f->ave_size = ave > 0 ? ave : 1;
+    f->rows_ave = false;
     return fft_reset(f);
+}
+int csdr_fft_batch_set_ave_row(csdr_fft_batch *f, int row, int ave)
+{   // CFft::SetFFTAve of one row: its length, then ResetFFT of that row alone
+    int lo, hi;
+    if (int rc = fft_row_range(f, row, &lo, &hi)) return rc;
+    if (!device_ok(f->device)) return CSDR_EHIP;
+    if (int rc = fft_rows_enter(f, true, false)) return rc;
+    for (int r = lo; r < hi; r++) {
+        f->ave_r[r] = ave > 0 ? ave : 1;
+        if (int rc = fft_reset_row(f, r)) return rc;
+    }
+    return CSDR_OK;
+}
+int csdr_fft_batch_reset_row(csdr_fft_batch *f, int row)
+{
+    int lo, hi;
+    if (int rc = fft_row_range(f, row, &lo, &hi)) return rc;
+    if (!device_ok(f->device)) return CSDR_EHIP;
+    for (int r = lo; r < hi; r++)
+        if (int rc = fft_reset_row(f, r)) return rc;
+    return CSDR_OK;
+}
+int csdr_fft_batch_row_form(csdr_fft_batch *f) { return f ? (int)fft_row_form(f) : fail(CSDR_EINVAL, "bad handle"); }
+int csdr_fft_batch_get_emits(csdr_fft_batch *f, int *out)
+{   // host state only: the frames each row used in the last put
+    if (!f || !out) return fail(CSDR_EINVAL, "bad argument");
+    for (int r = 0; r < f->channels; r++) out[r] = f->emits_by_row ? f->emits[r] : f->emit_all;
+    return CSDR_OK;
 }
 int csdr_fft_batch_reset(csdr_fft_batch *f)
 {
@@ -218,15 +331,20 @@ struct FrameSrc {
 // says; asynchronous.  nframes >= 1.  The overload flag is the last put frame's (m_Overload = FALSE at the top of every
 // PutInDisplayFFT, fft.cpp:270): every launch clears the words and its kernels set them for its last frame alone, so
 // of the launches of one stream call the one that holds the last used frame decides.
+// The row form (rows): the launch's table of active rows, nframes the largest frame count among them; each row's
+// frames, averaging length, start and step are its entry's, and the launch clears the overload words of ITS rows.
+struct RowTable { const SpecRow *dev, *host; int n; };
 static int fft_put_frames(csdr_fft_batch *f, const float *d_in, long long in_stride, int nframes, void *stream,
-                          const FrameSrc *src = nullptr)
+                          const FrameSrc *src = nullptr, const RowTable *rows = nullptr)
 {
     f->last_stream = (hipStream_t)stream; f->have_stream = true;
-    CSDR_HIP(hipMemsetAsync(f->d_over, 0, sizeof(int) * f->channels, (hipStream_t)stream));
+    if (!rows) CSDR_HIP(hipMemsetAsync(f->d_over, 0, sizeof(int) * f->channels, (hipStream_t)stream));
     SpectrumArgs a;
     a.in = d_in; a.in_stride = in_stride; a.win = f->d_win; a.tw1 = f->d_tw1; a.tw2 = f->d_tw2;
     a.sum = f->d_sum; a.pwr = f->d_pwr; a.ave = f->d_ave; a.counters = f->d_cnt; a.overload = f->d_over;
     a.channels = f->channels; a.nframes = nframes; a.ave_size = f->ave_size;
+    if (rows) { a.rows = rows->dev; a.nrows = rows->n; }
+    const int active = rows ? rows->n : f->channels;       // the channels that get workgroups
     // long calls on few channels: cut each channel's frames into groups so that ONE round of workgroups fills the chip --
     // 4 / 2 / 1 workgroups per CU at 4096 / 8192 / 16384 points (their LDS images; 2048 points fit eight, and measure 2 %
     // better with four).  (Until round 4 the target was 1024 workgroups for every size: at 16384 points that was four
@@ -237,7 +355,7 @@ static int fft_put_frames(csdr_fft_batch *f, const float *d_in, long long in_str
     {
         const long per_cu = l2 <= 12 ? 4 : (l2 == 13 ? 2 : 1);
         const long slots = (l2 >= 11 && l2 <= 14) ? 256 * per_cu : 1024;
-        long np = (slots + f->channels - 1) / f->channels;
+        long np = (slots + active - 1) / active;
         if (np > nframes / 8) np = nframes / 8;
         if (np > 1) {
             const size_t need = (size_t)f->channels * np * f->size + (size_t)f->channels * (np + 1);   // + the group weights
@@ -255,7 +373,7 @@ static int fft_put_frames(csdr_fft_batch *f, const float *d_in, long long in_str
     a.nb_state = blank ? (const NbChan *)blank->state : nullptr;
     if (src) CSDR_HIP(spectrum_stream_launch(l2, a, src->pkt_len, (hipStream_t)stream));
     else if (l2 >= 11 && l2 <= 14) CSDR_HIP(spectrum_launch(l2, a, (hipStream_t)stream));
-    else CSDR_HIP(spectrum_generic_launch(l2, a, f->d_work, (hipStream_t)stream));
+    else CSDR_HIP(spectrum_generic_launch(l2, a, f->d_work, (hipStream_t)stream, rows ? rows->host : nullptr));
     return CSDR_OK;
 }
 /* nframes frames of `size` samples per channel, back to back in each row; asynchronous */
@@ -264,7 +382,24 @@ int csdr_fft_batch_put_display(csdr_fft_batch *f, const float *d_in, long long i
     if (!f || !d_in || nframes < 0) return fail(CSDR_EINVAL, "bad argument");
     if (nframes == 0) return CSDR_OK;
     if (!device_ok(f->device)) return CSDR_EHIP;
-    return fft_put_frames(f, d_in, in_stride, nframes, stream);
+    if (!fft_row_form(f)) {
+        const int rc = fft_put_frames(f, d_in, in_stride, nframes, stream);
+        if (rc == CSDR_OK) { f->emit_all = nframes; f->emits_by_row = false; }
+        return rc;
+    }
+    // the row form: every row nframes frames, each with its own averaging length
+    int slot;
+    if (int rc = fft_tab_slot(f, &slot)) return rc;
+    SpecRow *h = f->h_tab[slot];
+    for (int r = 0; r < f->channels; r++)
+        h[r] = SpecRow{r, nframes, f->rows_ave ? f->ave_r[r] : f->ave_size, 0, 0, f->size};
+    hipStream_t st = (hipStream_t)stream;
+    CSDR_HIP(hipMemcpyAsync(f->d_tab[slot], h, sizeof(SpecRow) * (size_t)f->channels, hipMemcpyHostToDevice, st));
+    const RowTable tab{f->d_tab[slot], h, f->channels};
+    if (int rc = fft_put_frames(f, d_in, in_stride, nframes, stream, nullptr, &tab)) return rc;
+    if (int rc = fft_tab_sent(f, slot, st)) return rc;
+    f->emit_all = nframes; f->emits_by_row = false;
+    return CSDR_OK;
 }
 
 /* ---- the display stream (ProcessIQData, sdrinterface.cpp:886-907) ---- */
@@ -279,11 +414,59 @@ int csdr_fft_batch_put_display(csdr_fft_batch *f, const float *d_in, long long i
 // here is that a frame whose delayed samples may reach in front of the call -- first sample below the largest
 // delay_n + 1, NB_MAX_WIDTH / 2 + 1 -- is gathered like the frame that begins in the carry (with step >= N >= 2048
 // that is at most the first two used frames of a call), instead of teaching the loaders the history branch.
+// The row form of a stream call: display_rows_plan over the rows' states and the shared position, then at most two
+// launches, each over its table of active rows: the gathered frames (the frame that begins in the carry; every frame at
+// 16384 points, at the multi-launch sizes and behind a blanker), then the frames the stream loaders read where they lie,
+// with each row's start and step.  A row that uses no frame is in neither table: nothing of it is read or written.
+static int fft_put_stream_rows(csdr_fft_batch *f, const float *d_in, long long in_stride, const WireIn &wire, long long n,
+                               const double *d_dc, void *stream, const DcBlank *blank)
+{
+    const int N = f->size, l2 = log2_of(N), C = f->channels;
+    const bool loaders = !blank && l2 >= 11 && l2 <= 13;
+    hipStream_t st = (hipStream_t)stream;
+    if (!f->rows_disp) f->rs.assign((size_t)C, f->ds);
+    if (!f->rows_ave) f->ave_r.assign((size_t)C, f->ave_size);
+    int slot;
+    if (int rc = fft_tab_slot(f, &slot)) return rc;
+    SpecRow *hg = f->h_tab[slot], *hl = hg + C;
+    SpecRow *dg = f->d_tab[slot], *dl = dg + C;
+    const DisplayRowsSplit d = display_rows_plan(f->rs.data(), f->ave_r.data(), C, f->ds.pos, n, N, loaders, 0,
+                                                 l2 < 11 || l2 > 14, f->rs_next.data(), f->emits_next.data(), hg, hl);
+    StreamSrc a;
+    a.in = d_in; a.in_stride = (long)in_stride; a.wire = wire; a.dc = d_dc;
+    a.carry = f->d_carry; a.pos = f->ds.pos; a.carry_stride = N; a.channels = C;
+    a.nb_mask = blank ? blank->mask : nullptr; a.nb_mask_stride = blank ? blank->mask_stride : 0;
+    a.nb_state = blank ? (const NbChan *)blank->state : nullptr; a.nb_hist = blank ? blank->hist : nullptr;
+    if (d.ngath > 0) {
+        CSDR_HIP(fft_grow(f->d_stage, f->stage_cap, (size_t)C * d.max_gath * N * 2, st));
+        CSDR_HIP(hipMemcpyAsync(dg, hg, sizeof(SpecRow) * (size_t)d.ngath, hipMemcpyHostToDevice, st));
+        CSDR_HIP(display_gather_rows_launch(a, dg, d.ngath, d.max_gath, N, f->d_stage, st));
+        const RowTable tab{dg, hg, d.ngath};
+        if (int rc = fft_put_frames(f, f->d_stage, (long long)d.max_gath * N, d.max_gath, stream, nullptr, &tab)) return rc;
+    }
+    if (d.nload > 0) {
+        CSDR_HIP(hipMemcpyAsync(dl, hl, sizeof(SpecRow) * (size_t)d.nload, hipMemcpyHostToDevice, st));
+        const FrameSrc src{0, 0, d_dc, wire.pk, wire.chan_stride, wire.pkt_len, nullptr};
+        const RowTable tab{dl, hl, d.nload};
+        if (int rc = fft_put_frames(f, d_in, in_stride, d.max_load, stream, &src, &tab)) return rc;
+    }
+    if (d.ngath + d.nload > 0)
+        if (int rc = fft_tab_sent(f, slot, st)) return rc;
+    if (f->ds.pos + n < N) CSDR_HIP(display_carry_launch(a, f->d_carry, f->ds.pos, 0, (int)n, st));
+    else CSDR_HIP(display_carry_launch(a, f->d_carry, 0, n - d.next_pos, d.next_pos, st));
+    f->rs.swap(f->rs_next);
+    f->emits.swap(f->emits_next); f->emits_by_row = true;
+    if (!f->rows_disp) f->ds = f->rs[0];
+    f->ds.pos = d.next_pos;
+    return d.max_count;
+}
+
 static int fft_put_stream(csdr_fft_batch *f, const float *d_in, long long in_stride, const WireIn &wire, long long n,
                           const double *d_dc, void *stream, const DcBlank *blank = nullptr)
 {
-    if (n == 0) return 0;
+    if (n == 0) { f->emit_all = 0; f->emits_by_row = false; return 0; }
     if (!device_ok(f->device)) return CSDR_EHIP;
+    if (fft_row_form(f)) return fft_put_stream_rows(f, d_in, in_stride, wire, n, d_dc, stream, blank);
     const int N = f->size, l2 = log2_of(N);
     // (CSDR_DISPLAY_BLANKED_LOADERS=0: every used frame of a blanked call through the gather -- the A/B of
     // tools/bench_display_blanked.py; the words are the same)
@@ -323,6 +506,7 @@ static int fft_put_stream(csdr_fft_batch *f, const float *d_in, long long in_str
     if (f->ds.pos + n < N) CSDR_HIP(display_carry_launch(a, f->d_carry, f->ds.pos, 0, (int)n, st));
     else CSDR_HIP(display_carry_launch(a, f->d_carry, 0, n - p.next.pos, p.next.pos, st));
     f->ds = p.next;
+    f->emit_all = p.count; f->emits_by_row = false;
     return p.count;
 }
 
@@ -334,18 +518,48 @@ int csdr_fft_batch_set_display_rate(csdr_fft_batch *f, double sample_rate, int m
     f->ds.skip = display_skip_value(sample_rate, f->size, max_display_rate);
     f->ds.counter = 0;
     f->ds.gated = gated != 0;
+    if (f->rows_disp) {          // every row takes these settings and the display half of the row form ends; the one gate
+        f->ds.ready = 1;                                                         // left is open if every row's was
+        for (int r = 0; r < f->channels; r++) f->ds.ready &= f->rs[r].ready;
+        f->rows_disp = false;
+    }
+    return CSDR_OK;
+}
+int csdr_fft_batch_set_display_rate_row(csdr_fft_batch *f, int row, int max_display_rate, int gated)
+{   // SetMaxDisplayRate of one row at the object's sample rate and size; its handshake on or off
+    int lo, hi;
+    if (int rc = fft_row_range(f, row, &lo, &hi)) return rc;
+    if (max_display_rate < 1) return fail(CSDR_EINVAL, "display rate >= 1");
+    if (int rc = fft_rows_enter(f, false, true)) return rc;
+    const double fs = f->disp_fs > 0 ? f->disp_fs : f->fs;
+    for (int r = lo; r < hi; r++) {
+        f->rate_r[r] = max_display_rate;
+        f->rs[r].skip = display_skip_value(fs, f->size, max_display_rate);
+        f->rs[r].counter = 0;
+        f->rs[r].gated = gated != 0;
+    }
     return CSDR_OK;
 }
 int csdr_fft_batch_screen_update_done(csdr_fft_batch *f)
-{   // CSdrInterface::ScreenUpdateDone (sdrinterface.h:67)
+{   // CSdrInterface::ScreenUpdateDone (sdrinterface.h:67), of every listener
     if (!f) return fail(CSDR_EINVAL, "bad handle");
     f->ds.ready = 1;
+    if (f->rows_disp) for (auto &r : f->rs) r.ready = 1;
+    return CSDR_OK;
+}
+int csdr_fft_batch_screen_update_done_row(csdr_fft_batch *f, int row)
+{   // ScreenUpdateDone() of one listener
+    int lo, hi;
+    if (int rc = fft_row_range(f, row, &lo, &hi)) return rc;
+    if (int rc = fft_rows_enter(f, false, true)) return rc;          // (host state only from the second call on)
+    for (int r = lo; r < hi; r++) f->rs[r].ready = 1;
     return CSDR_OK;
 }
 int csdr_fft_batch_stream_reset(csdr_fft_batch *f)
-{   // CSdrInterface::StartSdr (sdrinterface.cpp:512, 591): m_FftBufPos = 0, m_ScreenUpateFinished = TRUE
+{   // CSdrInterface::StartSdr (sdrinterface.cpp:512, 591): m_FftBufPos = 0, m_ScreenUpateFinished = TRUE (every row's)
     if (!f) return fail(CSDR_EINVAL, "bad handle");
     f->ds.pos = 0; f->ds.ready = 1;
+    if (f->rows_disp) for (auto &r : f->rs) r.ready = 1;
     return CSDR_OK;
 }
 int csdr_fft_batch_put_display_stream(csdr_fft_batch *f, const float *d_in, long long in_stride, int n,
@@ -548,6 +762,14 @@ int csdr_fft_batch_rev(csdr_fft_batch *f, const float *d_in, long long in_stride
 { return fft_batch_plain(f, d_in, in_stride, d_out, out_stride, nframes, stream, -1); }
 int csdr_fft_batch_plain_group(csdr_fft_batch *f) { return f ? f->plain_group : fail(CSDR_EINVAL, "bad handle"); }
 
+// for the tests: one row's running sum [size] and {ave_count, total_count}, behind the object's last put
+int csdr__fft_batch_row_state(csdr_fft_batch *f, int row, float *sum, int *counters2)
+{
+    if (!f || !sum || !counters2 || row < 0 || row >= f->channels) return fail(CSDR_EINVAL, "bad argument");
+    if (!device_ok(f->device)) return CSDR_EHIP;
+    if (int rc = fft_read(f, sum, f->d_sum + (size_t)row * f->size, (size_t)f->size * 4)) return rc;
+    return fft_read(f, counters2, f->d_cnt + 2 * row, 2 * sizeof(int));
+}
 // what csdr_plotter_batch_draw reads: nothing of the cached translate table, and nothing here is changed
 int csdr__fft_batch_view(csdr_fft_batch *f, FftView *v)
 {

@@ -15,6 +15,7 @@
 #include "fastfir_kernels.h"
 #include "fft_core.hpp"
 #include <cstring>
+#include <vector>
 
 using namespace csdr;
 
@@ -211,6 +212,28 @@ void csdr__host_display_plan(const int *state5, long long n, int N, long long *o
     const DisplayPlan p = display_plan(s, n, N);
     out8[0] = p.start; out8[1] = p.step; out8[2] = p.count;
     out8[3] = p.next.pos; out8[4] = p.next.skip; out8[5] = p.next.counter; out8[6] = p.next.gated; out8[7] = p.next.ready;
+}
+// the row form's planner (display_rows_plan): states [nrows][4] = {skip, counter, gated, ready} in and out, ave [nrows];
+// counts [nrows]; gath / load [nrows][6] = {row, nframes, ave, start, step, 0} with room for nrows entries;
+// split6 = {ngath, nload, max_gath, max_load, max_count, next_pos}
+void csdr__host_display_rows_plan(int *states4, const int *ave, int nrows, int pos, long long n, int N, int loaders,
+                                  long long first_loaded, int sorted, int *counts, long long *gath6, long long *load6,
+                                  int *split6)
+{
+    std::vector<DisplayState> rs((size_t)nrows), next((size_t)nrows);
+    std::vector<SpecRow> g((size_t)nrows), l((size_t)nrows);
+    for (int r = 0; r < nrows; r++) {
+        rs[r].skip = states4[4 * r]; rs[r].counter = states4[4 * r + 1]; rs[r].gated = states4[4 * r + 2]; rs[r].ready = states4[4 * r + 3];
+    }
+    const DisplayRowsSplit d = display_rows_plan(rs.data(), ave, nrows, pos, n, N, loaders != 0, first_loaded, sorted != 0,
+                                                 next.data(), counts, g.data(), l.data());
+    for (int r = 0; r < nrows; r++) {
+        states4[4 * r] = next[r].skip; states4[4 * r + 1] = next[r].counter; states4[4 * r + 2] = next[r].gated; states4[4 * r + 3] = next[r].ready;
+    }
+    auto put = [](long long *o, const SpecRow &e) { o[0] = e.row; o[1] = e.nframes; o[2] = e.ave_size; o[3] = e.start; o[4] = e.step; o[5] = 0; };
+    for (int i = 0; i < d.ngath; i++) put(gath6 + 6 * i, g[i]);
+    for (int i = 0; i < d.nload; i++) put(load6 + 6 * i, l[i]);
+    split6[0] = d.ngath; split6[1] = d.nload; split6[2] = d.max_gath; split6[3] = d.max_load; split6[4] = d.max_count; split6[5] = d.next_pos;
 }
 int csdr__host_display_skip_value(double sample_rate, int fft_size, int max_display_rate)
 {

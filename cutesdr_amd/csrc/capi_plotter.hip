@@ -237,7 +237,9 @@ int csdr_plotter_batch_set_ad_overload(csdr_plotter_batch *p, int view, int on)
 int csdr_plotter_batch_set_running(csdr_plotter_batch *p, int view, int on)
 { return plb_each(p, view, [=](View &k) { k.running = on ? 1 : 0; }); }
 
-int csdr_plotter_batch_draw(csdr_plotter_batch *p, csdr_fft_batch *f, void *stream)
+// draw of every view (emitted_only: of the running views whose row used a frame in f's last put; the others are skipped
+// whole, a pending pen command included)
+static int plb_draw(csdr_plotter_batch *p, csdr_fft_batch *f, void *stream, bool emitted_only)
 {
     if (!have_device()) return CSDR_EHIP;
     if (!p || !f) return fail(CSDR_EINVAL, "bad argument");
@@ -248,6 +250,11 @@ int csdr_plotter_batch_draw(csdr_plotter_batch *p, csdr_fft_batch *f, void *stre
     for (int i = 0; i < p->views; i++)
         if (p->v[i].running && p->v[i].row >= fv.channels)
             return fail(CSDR_EINVAL, "view %d plots row %d of %d", i, p->v[i].row, fv.channels);
+    std::vector<int> emits;
+    if (emitted_only) {
+        emits.resize((size_t)fv.channels);
+        if (int rc = csdr_fft_batch_get_emits(f, emits.data())) return rc;
+    }
     CSDR_HIP(hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
     int slot;
@@ -261,6 +268,7 @@ int csdr_plotter_batch_draw(csdr_plotter_batch *p, csdr_fft_batch *f, void *stre
     for (int i = 0; i < p->views; i++) {
         View &k = nv[i];
         if (!k.running && k.ad_cmd < 0) continue;
+        if (emitted_only && !(k.running && emits[k.row] > 0)) continue;
         ViewParam &q = hp[a.count++];
         memset(&q, 0, sizeof(q));
         q.view = i; q.row = k.running ? k.row : 0; q.draws = k.running; q.ad_cmd = k.ad_cmd; q.group = 1;
@@ -285,6 +293,8 @@ int csdr_plotter_batch_draw(csdr_plotter_batch *p, csdr_fft_batch *f, void *stre
     p->v.swap(nv);
     return drawn;
 }
+int csdr_plotter_batch_draw(csdr_plotter_batch *p, csdr_fft_batch *f, void *stream) { return plb_draw(p, f, stream, false); }
+int csdr_plotter_batch_draw_emitted(csdr_plotter_batch *p, csdr_fft_batch *f, void *stream) { return plb_draw(p, f, stream, true); }
 
 int csdr_plotter_batch_get_geometry(csdr_plotter_batch *p, int view, int *w, int *h2d, int *wf_h, int *min_db)
 {

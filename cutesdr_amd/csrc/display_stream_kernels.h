@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "wire_format.hpp"
 #include "frontend_kernels.h"
+#include "display_plan.hpp"
 
 namespace csdr {
 
@@ -30,6 +31,10 @@ struct StreamSrc {
 // out[ch][k * N + i] = stream sample start + k * step + i, for k < count, i < N
 hipError_t display_gather_launch(const StreamSrc &a, long long start, long long step, int count, int N, float *out,
                                  hipStream_t stream);
+// the row form: out[row][k * N + i] (rows max_count * N apart) = stream sample start + k * step + i of the row, for the
+// nrows entries {row, count, start, step} of the device table d_rows; max_count is the largest count among them
+hipError_t display_gather_rows_launch(const StreamSrc &a, const SpecRow *d_rows, int nrows, int max_count, int N, float *out,
+                                      hipStream_t stream);
 // carry[ch][dst + i] = stream sample src + i, i < len (src >= 0: never reads the carry it writes)
 hipError_t display_carry_launch(const StreamSrc &a, float *carry, int dst, long long src, int len, hipStream_t stream);
 

@@ -52,6 +52,19 @@ void display_gather_kernel(StreamSrc a, long start, long step, long total, int l
     reinterpret_cast<v2s *>(out)[(long)ch * total + j] = stream_sample<BLK>(a, ch, start + k * step + i);
 }
 
+// the row form: entry e of the table gathers ITS frames (start, step and count of its own) into out[row][...]; a row
+// without a frame is in no table and its staging row is not touched
+template <bool BLK>
+__global__ __launch_bounds__(256)
+void display_gather_rows_kernel(StreamSrc a, const SpecRow *rows, int log2n, float *out, long out_stride)
+{
+    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const SpecRow e = rows[blockIdx.y];
+    if (j >= ((long)e.nframes << log2n)) return;
+    const long k = j >> log2n, i = j & ((1l << log2n) - 1);
+    reinterpret_cast<v2s *>(out)[(long)e.row * out_stride + j] = stream_sample<BLK>(a, e.row, (long)e.start + k * (long)e.step + i);
+}
+
 template <bool BLK>
 __global__ __launch_bounds__(256)
 void display_carry_kernel(StreamSrc a, float *carry, int dst, long src, int len)
@@ -74,6 +87,21 @@ hipError_t display_gather_launch(const StreamSrc &a, long long start, long long 
         hipLaunchKernelGGL(display_gather_kernel<true>, grid, dim3(256), 0, stream, a, (long)start, (long)step, total, l2, out);
     else
         hipLaunchKernelGGL(display_gather_kernel<false>, grid, dim3(256), 0, stream, a, (long)start, (long)step, total, l2, out);
+    return hipGetLastError();
+}
+
+hipError_t display_gather_rows_launch(const StreamSrc &a, const SpecRow *d_rows, int nrows, int max_count, int N, float *out,
+                                      hipStream_t stream)
+{
+    int l2 = 0;
+    while ((1 << l2) < N) l2++;
+    const long total = (long)max_count * N;
+    if (total == 0 || nrows == 0) return hipSuccess;
+    const dim3 grid((unsigned)((total + 255) / 256), nrows);
+    if (a.nb_mask)
+        hipLaunchKernelGGL(display_gather_rows_kernel<true>, grid, dim3(256), 0, stream, a, d_rows, l2, out, total);
+    else
+        hipLaunchKernelGGL(display_gather_rows_kernel<false>, grid, dim3(256), 0, stream, a, d_rows, l2, out, total);
     return hipGetLastError();
 }
 

@@ -30,29 +30,43 @@ __global__ void stockham_pass_kernel(const v2f *x, v2f *y, int n0, int n, int s,
 
 // frame f of every channel: window, I/Q swap (fft.cpp:280-281), overload flag (fft.cpp:270, :275-276: the flag is
 // the last put frame's, so only the launch's last frame writes the word the launcher cleared)
+// The row form (a.rows: the table of the launch's active rows, by falling frame count): work slot e belongs to table
+// entry e, whose channel, frame count and averaging length replace the block's index and the uniform values; `active`
+// entries have a frame of this index.
 __global__ void spec_prep_kernel(SpectrumArgs a, int n, int frame, v2f *work, long wstride)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x, ch = blockIdx.y;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    int ch = blockIdx.y, last = a.nframes - 1;
+    if (a.rows) { ch = a.rows[blockIdx.y].row; last = a.rows[blockIdx.y].nframes - 1; }
     if (i >= n) return;
     const v2f s = reinterpret_cast<const v2f *>(a.in)[(long)ch * a.in_stride + (long)frame * n + i];
     const float w = a.win[i];
-    if (frame == a.nframes - 1 && s.x > refc::FFT_OVER_LIMIT_F) a.overload[ch] = 1;
-    work[(long)ch * wstride + i] = v2f{w * s.y, w * s.x};
+    if (frame == last && s.x > refc::FFT_OVER_LIMIT_F) a.overload[ch] = 1;
+    work[(long)blockIdx.y * wstride + i] = v2f{w * s.y, w * s.x};
 }
-__global__ void spec_count_kernel(SpectrumArgs a)
+__global__ void spec_count_kernel(SpectrumArgs a, int active)
 {
-    const int ch = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ch >= a.channels) return;
+    int ch = blockIdx.x * blockDim.x + threadIdx.x, ave_size = a.ave_size;
+    if (ch >= active) return;
+    if (a.rows) { ave_size = a.rows[ch].ave_size; ch = a.rows[ch].row; }
     a.counters[2 * ch + 1]++;                                        // CpxFFT counters, fft.cpp:515-517
-    if (a.counters[2 * ch] < a.ave_size) a.counters[2 * ch]++;
+    if (a.counters[2 * ch] < ave_size) a.counters[2 * ch]++;
+}
+// the row form clears the overload words of ITS rows (the uniform form's launcher clears every word)
+__global__ void spec_clear_rows_kernel(SpectrumArgs a)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < a.nrows) a.overload[a.rows[e].row] = 0;
 }
 // power, running mean, log10, display order (fft.cpp:564-589)
 __global__ void spec_finish_kernel(SpectrumArgs a, int n, const v2f *X, long wstride)
 {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x, ch = blockIdx.y;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    int ch = blockIdx.y;
+    if (a.rows) { a.ave_size = a.rows[blockIdx.y].ave_size; ch = a.rows[blockIdx.y].row; }
     if (k >= n) return;
     const int ave_count = a.counters[2 * ch], total = a.counters[2 * ch + 1];
-    const v2f v = X[(long)ch * wstride + k];
+    const v2f v = X[(long)blockIdx.y * wstride + k];
     const int j = (k + n / 2) & (n - 1);
     const long o = (long)ch * n + j;
     const float p = v.x * v.x + v.y * v.y;
@@ -77,16 +91,22 @@ static const v2f *stockham_run(int log2n, float sign, v2f *A, v2f *B, long wstri
     return x;
 }
 
-// work: [2][channels][N] complex
-hipError_t spectrum_generic_launch(int log2n, const SpectrumArgs &a, float *work, hipStream_t st)
+// work: [2][channels][N] complex.  h_rows: the host's copy of a.rows in the row form -- the frame loop runs over the
+// rows that still have a frame of that index, the first entries of the table
+hipError_t spectrum_generic_launch(int log2n, const SpectrumArgs &a, float *work, hipStream_t st, const SpecRow *h_rows)
 {
     const int n = 1 << log2n;
     v2f *A = reinterpret_cast<v2f *>(work), *B = A + (long)a.channels * n;
-    for (int f = 0; f < a.nframes; f++) {
-        hipLaunchKernelGGL(spec_prep_kernel, dim3(n / 256, a.channels), dim3(256), 0, st, a, n, f, A, (long)n);
-        hipLaunchKernelGGL(spec_count_kernel, dim3((a.channels + 63) / 64), dim3(64), 0, st, a);
-        const v2f *X = stockham_run(log2n, +1.0f, A, B, n, a.channels, st);
-        hipLaunchKernelGGL(spec_finish_kernel, dim3(n / 256, a.channels), dim3(256), 0, st, a, n, X, (long)n);
+    if (a.rows && (!h_rows || a.nrows < 1 || a.nrows > a.channels)) return hipErrorInvalidValue;
+    int active = a.rows ? a.nrows : a.channels;
+    const int nframes = a.rows ? h_rows[0].nframes : a.nframes;
+    if (a.rows) hipLaunchKernelGGL(spec_clear_rows_kernel, dim3((a.nrows + 63) / 64), dim3(64), 0, st, a);
+    for (int f = 0; f < nframes; f++) {
+        if (a.rows) while (h_rows[active - 1].nframes <= f) active--;
+        hipLaunchKernelGGL(spec_prep_kernel, dim3(n / 256, active), dim3(256), 0, st, a, n, f, A, (long)n);
+        hipLaunchKernelGGL(spec_count_kernel, dim3((active + 63) / 64), dim3(64), 0, st, a, active);
+        const v2f *X = stockham_run(log2n, +1.0f, A, B, n, active, st);
+        hipLaunchKernelGGL(spec_finish_kernel, dim3(n / 256, active), dim3(256), 0, st, a, n, X, (long)n);
     }
     return hipGetLastError();
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "frontend_kernels.h"
+#include "display_plan.hpp"
 
 namespace csdr {
 
@@ -27,6 +28,10 @@ struct SpectrumArgs {
     // zero under the mask.  The blanked loaders read no history: frame_start >= NB_MAX_WIDTH / 2 + 1 with them.
     const unsigned *nb_mask; long nb_mask_stride;   // [channels][stride] words; nullptr: no blanker
     const NbChan *nb_state;                         // [channels]: on, delay_n
+    // the row form (display_plan.hpp): a table of the nrows ACTIVE rows of this launch.  A workgroup finds its channel
+    // through its entry and takes nframes, ave_size, frame_start and frame_step from it; the fields above of those names
+    // are not read.  part and alpha stay indexed by channel.  nullptr: the uniform form, every channel nframes frames.
+    const SpecRow *rows = nullptr; int nrows = 0;
 };
 // which sizes have a blanked form of the stream loaders (pkt_len 0: fp32 rows); the others gather their frames
 bool spectrum_stream_blanked_ok(int log2n, int pkt_len);
@@ -67,7 +72,8 @@ hipError_t waterfall_color_launch(const int *levels, long stride, unsigned *rgb,
 
 // sizes outside 2048..16384 (512, 1024, 32768, 65536): multi-launch transform through HBM.
 // work: [2][channels][N] complex for the spectrum, [2][N] for the plain transform
-hipError_t spectrum_generic_launch(int log2n, const SpectrumArgs &a, float *work, hipStream_t stream);
+hipError_t spectrum_generic_launch(int log2n, const SpectrumArgs &a, float *work, hipStream_t stream,
+                                   const SpecRow *h_rows = nullptr);
 hipError_t fft_generic_plain_launch(int log2n, int sign, const float *in, float *out, float *work, hipStream_t stream);
 
 }  // namespace csdr

@@ -324,8 +324,11 @@ struct Wide16 {
 };
 
 // ---- the frame loop: one workgroup walks the frames f0 ... f1 of its channel through transform X, loaded by Ld -------
-template <class X, class Ld>
-__device__ __forceinline__ void spectrum_frames(const SpectrumArgs &a)
+// ROWS: the row form -- the workgroup's channel, frame count, averaging length and frame positions come from its entry
+// of the launch's table (spectrum_frames_rows, below); the channel's overload word is written, set or clear, by the
+// workgroup that holds the row's last frame.
+template <class X, class Ld, bool ROWS = false>
+__device__ __forceinline__ void spectrum_frames(const SpectrumArgs &a, const int ch, const int part)
 {
     constexpr int N = X::N, P = X::P;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -333,7 +336,7 @@ __device__ __forceinline__ void spectrum_frames(const SpectrumArgs &a)
     // With nparts > 1 the frames of a channel are cut into nparts groups, one workgroup each: the
     // running sum is the linear map sum <- alpha_f sum + p_f, so a group accumulates its frames from
     // zero into `part` and spectrum_combine_kernel folds the groups in order.
-    const int t = threadIdx.x, ch = blockIdx.x / a.nparts, part = blockIdx.x % a.nparts;
+    const int t = threadIdx.x;
     const int f0 = (int)((long)a.nframes * part / a.nparts), f1 = (int)((long)a.nframes * (part + 1) / a.nparts);
     X xf(a, lds);
     const Ld ld(a, ch);
@@ -342,6 +345,9 @@ __device__ __forceinline__ void spectrum_frames(const SpectrumArgs &a)
     total += f0;                                              // counters at this group's first frame
     ave_count = ave_count + f0 < a.ave_size ? ave_count + f0 : (ave_count > a.ave_size ? ave_count : a.ave_size);
     int over = 0;
+    // (the row form: no launcher cleared the word -- the group that holds the row's last frame, never an empty one, does,
+    // and the barriers of that frame's transform lie between this store and the one at the end)
+    if constexpr (ROWS) if (t == 0 && part == a.nparts - 1) a.overload[ch] = 0;
     // every thread owns the same P bins in every frame: the running sum and mean stay in registers
     // for the whole call, only the last frame's bels are written
     int tt = t;
@@ -407,19 +413,61 @@ __device__ __forceinline__ void spectrum_frames(const SpectrumArgs &a)
     // call's last frame writes it (the launcher cleared the word)
     if (over && part == a.nparts - 1) a.overload[ch] = 1;
 }
+// the uniform form: workgroup = (channel, frame group)
+template <class X, class Ld>
+__device__ __forceinline__ void spectrum_frames_uniform(const SpectrumArgs &a)
+{
+    spectrum_frames<X, Ld>(a, blockIdx.x / a.nparts, blockIdx.x % a.nparts);
+}
+// The row form: a copy of the arguments with the entry's values in the uniform form's fields (wave-uniform loads, once
+// per workgroup).  A row cuts ITS frame count into frame groups by the uniform form's rule, eight frames a group at
+// least, and takes the first row_groups() of the launch's nparts workgroups per row; the others leave at once.  So what a
+// row computes depends on its own frames alone -- not on how many frames the other rows of the launch have -- and a row
+// below sixteen frames runs the one-group path, whose words are those of the frames in order.  Its groups' partial sums
+// and weights lie in the row's own [nparts] slots.
+__device__ __forceinline__ int row_groups(int nframes, int nparts)
+{
+    const int g = nframes / 8;
+    return g < 1 ? 1 : (g < nparts ? g : nparts);
+}
+template <class X, class Ld>
+__device__ __forceinline__ void spectrum_frames_rows(const SpectrumArgs &a)
+{
+    const SpecRow e = a.rows[blockIdx.x / a.nparts];
+    const int part = blockIdx.x % a.nparts, groups = row_groups(e.nframes, a.nparts);
+    if (part >= groups) return;
+    SpectrumArgs b = a;
+    b.nframes = e.nframes; b.ave_size = e.ave_size;
+    b.frame_start = (long)e.start; b.frame_step = (long)e.step;
+    b.nparts = groups; b.part = a.part + (long)e.row * (a.nparts - groups) * X::N;     // [row][nparts][N] seen as [row][groups][N]
+    spectrum_frames<X, Ld, true>(b, e.row, part);
+}
 
 template <int LOG2N, class Ld = RowLoad>
 __global__ __launch_bounds__(SpecCfg<LOG2N>::T) __attribute__((amdgpu_waves_per_eu(1)))
-void spectrum_kernel(SpectrumArgs a) { spectrum_frames<Passes32<LOG2N>, Ld>(a); }
+void spectrum_kernel(SpectrumArgs a) { spectrum_frames_uniform<Passes32<LOG2N>, Ld>(a); }
 template <class Ld = RowLoad>
 __global__ __launch_bounds__(128)
-void spectrum8_kernel(SpectrumArgs a) { spectrum_frames<Wide16<PassB2048>, Ld>(a); }
+void spectrum8_kernel(SpectrumArgs a) { spectrum_frames_uniform<Wide16<PassB2048>, Ld>(a); }
 template <class Ld = RowLoad>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1)))
-void spectrum16_kernel(SpectrumArgs a) { spectrum_frames<Wide16<PassB4096>, Ld>(a); }
+void spectrum16_kernel(SpectrumArgs a) { spectrum_frames_uniform<Wide16<PassB4096>, Ld>(a); }
 template <class Ld = RowLoad>
 __global__ __launch_bounds__(512)
-void spectrum32_kernel(SpectrumArgs a) { spectrum_frames<Wide16<PassB8192>, Ld>(a); }
+void spectrum32_kernel(SpectrumArgs a) { spectrum_frames_uniform<Wide16<PassB8192>, Ld>(a); }
+// the same four behind a row table
+template <int LOG2N, class Ld = RowLoad>
+__global__ __launch_bounds__(SpecCfg<LOG2N>::T) __attribute__((amdgpu_waves_per_eu(1)))
+void spectrum_rows_kernel(SpectrumArgs a) { spectrum_frames_rows<Passes32<LOG2N>, Ld>(a); }
+template <class Ld = RowLoad>
+__global__ __launch_bounds__(128)
+void spectrum8_rows_kernel(SpectrumArgs a) { spectrum_frames_rows<Wide16<PassB2048>, Ld>(a); }
+template <class Ld = RowLoad>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1)))
+void spectrum16_rows_kernel(SpectrumArgs a) { spectrum_frames_rows<Wide16<PassB4096>, Ld>(a); }
+template <class Ld = RowLoad>
+__global__ __launch_bounds__(512)
+void spectrum32_rows_kernel(SpectrumArgs a) { spectrum_frames_rows<Wide16<PassB8192>, Ld>(a); }
 
 // plain transform: out[k] = sum_n in[n] e^{sign j 2 pi n k / N}; sign=-1 via conjugation
 template <int LOG2N>
@@ -463,9 +511,10 @@ void fft_plain_kernel(const v2f *in, v2f *out, const v2f *tw1g, const v2f *tw2g,
 // 40 us of the C1 call's 940 for its 512 sequential divisions).
 // One workgroup per channel (thread g = frame group g, in rounds of the block size): once every thread has read the
 // counters, thread 0 moves them -- what spectrum_count_kernel did in a launch of its own.
-__global__ void spectrum_alpha_kernel(SpectrumArgs a)
+// al: the channel's [nparts] weights; after: its average count after the call
+static __device__ __forceinline__ void spectrum_alpha(const SpectrumArgs &a, const int ch, const int nparts, float *al_out,
+                                                      float *after)
 {
-    const int ch = blockIdx.x;
     const int ave0 = a.counters[2 * ch], total0 = a.counters[2 * ch + 1];
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -473,11 +522,11 @@ __global__ void spectrum_alpha_kernel(SpectrumArgs a)
         a.counters[2 * ch] = ave_count < a.ave_size ? ave_count : (ave0 > a.ave_size ? ave0 : a.ave_size);
         a.counters[2 * ch + 1] = total0 + a.nframes;
     }
-    for (int g = threadIdx.x; g < a.nparts; g += blockDim.x) {
+    for (int g = threadIdx.x; g < nparts; g += blockDim.x) {
         // after k frames: total0 + k, and the average count saturates at ave_size (a count above it -- the average was
         // shortened -- stays)
         auto ave_after = [&](int k) { return ave0 < a.ave_size ? (ave0 + k < a.ave_size ? ave0 + k : a.ave_size) : ave0; };
-        const int f0 = (int)((long)a.nframes * g / a.nparts), f1 = (int)((long)a.nframes * (g + 1) / a.nparts);
+        const int f0 = (int)((long)a.nframes * g / nparts), f1 = (int)((long)a.nframes * (g + 1) / nparts);
         int ave_count = ave_after(f0), total = total0 + f0;
         float al = 1.f;                                                // product of the group's alpha_f
         for (int f = f0; f < f1; f++) {
@@ -487,9 +536,25 @@ __global__ void spectrum_alpha_kernel(SpectrumArgs a)
             if (total > a.ave_size) al = al - al / prev;
             if (al == 0.f) break;                                      // (no averaging: the first frame already forgets everything)
         }
-        a.alpha[(long)ch * a.nparts + g] = al;
-        if (g == 0) a.alpha[(long)a.channels * a.nparts + ch] = (float)ave_after(a.nframes);
+        al_out[g] = al;
+        if (g == 0) *after = (float)ave_after(a.nframes);
     }
+}
+__global__ void spectrum_alpha_kernel(SpectrumArgs a)
+{
+    spectrum_alpha(a, blockIdx.x, a.nparts, a.alpha + (long)blockIdx.x * a.nparts, a.alpha + (long)a.channels * a.nparts + blockIdx.x);
+}
+// the row form: one workgroup per table entry, over the row's own groups.  A row of one group is finished by its frame
+// loop, counters included: nothing here or in the combine.  (A row without a frame is in no table: ave_after(0) of a
+// fresh row is 0, and the combine would divide by it.)
+__global__ void spectrum_alpha_rows_kernel(SpectrumArgs a)
+{
+    const SpecRow e = a.rows[blockIdx.x];
+    const int groups = row_groups(e.nframes, a.nparts);
+    if (groups == 1) return;
+    SpectrumArgs b = a;
+    b.nframes = e.nframes; b.ave_size = e.ave_size;
+    spectrum_alpha(b, e.row, groups, a.alpha + (long)e.row * a.nparts, a.alpha + (long)a.channels * a.nparts + e.row);
 }
 // folds the frame groups of spectrum_kernel (nparts > 1) into the running sum, writes mean and bels
 __global__ void spectrum_combine_kernel(SpectrumArgs a, int n)
@@ -503,18 +568,32 @@ __global__ void spectrum_combine_kernel(SpectrumArgs a, int n)
     a.sum[(long)ch * n + j] = sm; a.pwr[(long)ch * n + j] = m;
     a.ave[(long)ch * n + j] = (float)((double)log10f(m + a.kc) + a.kb);
 }
+// the row form: the row's own groups, in its [nparts] slots; a row of one group was finished by its frame loop
+__global__ void spectrum_combine_rows_kernel(SpectrumArgs a, int n)
+{
+    const SpecRow e = a.rows[blockIdx.y];
+    const int j = blockIdx.x * blockDim.x + threadIdx.x, ch = e.row, groups = row_groups(e.nframes, a.nparts);
+    if (j >= n || groups == 1) return;
+    float sm = a.sum[(long)ch * n + j];
+    for (int g = 0; g < groups; g++)
+        sm = a.alpha[(long)ch * a.nparts + g] * sm + a.part[((long)ch * a.nparts + g) * n + j];
+    const float m = sm / a.alpha[(long)a.channels * a.nparts + ch];
+    a.sum[(long)ch * n + j] = sm; a.pwr[(long)ch * n + j] = m;
+    a.ave[(long)ch * n + j] = (float)((double)log10f(m + a.kc) + a.kb);
+}
 // (the kernel is a template argument: CSDR_MAX_LDS_ONCE keeps its flag per launch site, so per kernel)
-template <class X, auto Kernel>
+template <class X, auto Kernel, bool ROWS = false>
 static hipError_t spec_launch_one(const SpectrumArgs &a, hipStream_t s)
 {
     if constexpr (X::LDS_BYTES > 64 * 1024) {             // more LDS than a kernel gets unasked
         const hipError_t e = CSDR_MAX_LDS_ONCE(Kernel, X::LDS_BYTES);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(Kernel, dim3(a.channels * a.nparts), dim3(X::T), X::LDS_BYTES, s, a);
+    const int rows = ROWS ? a.nrows : a.channels;
+    hipLaunchKernelGGL(Kernel, dim3(rows * a.nparts), dim3(X::T), X::LDS_BYTES, s, a);
     if (a.nparts > 1) {
-        hipLaunchKernelGGL(spectrum_alpha_kernel, dim3(a.channels), dim3(64), 0, s, a);
-        hipLaunchKernelGGL(spectrum_combine_kernel, dim3(X::N / 256, a.channels), dim3(256), 0, s, a, (int)X::N);
+        hipLaunchKernelGGL(ROWS ? spectrum_alpha_rows_kernel : spectrum_alpha_kernel, dim3(rows), dim3(64), 0, s, a);
+        hipLaunchKernelGGL(ROWS ? spectrum_combine_rows_kernel : spectrum_combine_kernel, dim3(X::N / 256, rows), dim3(256), 0, s, a, (int)X::N);
     }
     return hipGetLastError();
 }
@@ -526,6 +605,16 @@ static hipError_t spec_launch_one(const SpectrumArgs &a, hipStream_t s)
 // 124 on 24-bit datagrams.
 constexpr int PLAIN_MAX_LOG2N = 14, STREAM_MAX_LOG2N = 13, BLANKED_MAX_LOG2N = 12;
 // (the tests against MAX_LOG2N are compile-time: a loader is instantiated in the kernels of ITS sizes only)
+template <int MAX_LOG2N, class Ld>
+static hipError_t spec_launch_rows(int log2n, const SpectrumArgs &a, hipStream_t s)
+{
+    if (a.nrows < 1) return hipErrorInvalidValue;
+    if (log2n == 11) return spec_launch_one<Wide16<PassB2048>, &spectrum8_rows_kernel<Ld>, true>(a, s);
+    if (log2n == 12) return spec_launch_one<Wide16<PassB4096>, &spectrum16_rows_kernel<Ld>, true>(a, s);
+    if constexpr (MAX_LOG2N >= 13) if (log2n == 13) return spec_launch_one<Wide16<PassB8192>, &spectrum32_rows_kernel<Ld>, true>(a, s);
+    if constexpr (MAX_LOG2N >= 14) if (log2n == 14) return spec_launch_one<Passes32<14>, &spectrum_rows_kernel<14, Ld>, true>(a, s);
+    return hipErrorInvalidValue;
+}
 template <int MAX_LOG2N, class Ld>
 static hipError_t spec_launch(int log2n, const SpectrumArgs &a, hipStream_t s)
 {
@@ -548,6 +637,7 @@ static hipError_t plain_launch_one(int sign, const float *in, float *out, const 
 
 hipError_t spectrum_launch(int log2n, const SpectrumArgs &a, hipStream_t stream)
 {
+    if (a.rows) return spec_launch_rows<PLAIN_MAX_LOG2N, RowLoad>(log2n, a, stream);
     return spec_launch<PLAIN_MAX_LOG2N, RowLoad>(log2n, a, stream);
 }
 bool spectrum_stream_blanked_ok(int log2n, int pkt_len)
@@ -556,6 +646,13 @@ bool spectrum_stream_blanked_ok(int log2n, int pkt_len)
 }
 hipError_t spectrum_stream_launch(int log2n, const SpectrumArgs &a, int pkt_len, hipStream_t stream)
 {
+    if (a.rows) {                // the row form has no blanked loaders: a blanked call's frames are gathered (capi_fft.hip)
+        if (a.nb_mask) return hipErrorInvalidValue;
+        if (!a.pk) return spec_launch_rows<STREAM_MAX_LOG2N, RowDcLoad>(log2n, a, stream);
+        if (pkt_len == 1444) return spec_launch_rows<STREAM_MAX_LOG2N, WireLoad<1444>>(log2n, a, stream);
+        if (pkt_len == 1028) return spec_launch_rows<STREAM_MAX_LOG2N, WireLoad<1028>>(log2n, a, stream);
+        return hipErrorInvalidValue;
+    }
     if (a.nb_mask) {
         if (!spectrum_stream_blanked_ok(log2n, a.pk ? pkt_len : 0)) return hipErrorInvalidValue;
         if (!a.pk) return spec_launch<BLANKED_MAX_LOG2N, BlankedLoad<RowDcLoad>>(log2n, a, stream);

@@ -1075,6 +1075,31 @@ class FftBatch(_Obj):
     def stream_reset(self):
         check(lib().csdr_fft_batch_stream_reset(self.h), "csdr_fft_batch_stream_reset")
 
+    # ---- the row form: averaging length, display rate, gate and acknowledge per row (row < 0: every row)
+    def set_ave_row(self, row, ave):
+        """SetFFTAve of one row, then ResetFFT of that row alone; the object enters the row form"""
+        check(lib().csdr_fft_batch_set_ave_row(self.h, int(row), int(ave)), "csdr_fft_batch_set_ave_row")
+
+    def reset_row(self, row):
+        check(lib().csdr_fft_batch_reset_row(self.h, int(row)), "csdr_fft_batch_reset_row")
+
+    def set_display_rate_row(self, row, max_display_rate, gated=False):
+        """SetMaxDisplayRate of one row at the object's sample rate and size; gated: that row's handshake"""
+        check(lib().csdr_fft_batch_set_display_rate_row(self.h, int(row), int(max_display_rate), int(bool(gated))),
+              "csdr_fft_batch_set_display_rate_row")
+
+    def screen_update_done_row(self, row):
+        check(lib().csdr_fft_batch_screen_update_done_row(self.h, int(row)), "csdr_fft_batch_screen_update_done_row")
+
+    def row_form(self):
+        return bool(check(lib().csdr_fft_batch_row_form(self.h), "csdr_fft_batch_row_form"))
+
+    def emits(self):
+        """the frames each row used in the last put call (host state: waits for nothing) -> int32 [channels]"""
+        out = np.zeros(self.channels, dtype=np.int32)
+        check(lib().csdr_fft_batch_get_emits(self.h, _vp(out)), "csdr_fft_batch_get_emits")
+        return out
+
     def put_display_stream_ptr(self, d_in, in_stride, n, d_dc=None, stream=None):
         """n samples of every row appended to the display stream; returns the frames that entered the average"""
         return check(lib().csdr_fft_batch_put_display_stream(self.h, C.c_void_p(d_in), in_stride, n, C.c_void_p(d_dc or 0),
@@ -1562,6 +1587,11 @@ class PlotterBatch(_Obj):
         running views"""
         return check(lib().csdr_plotter_batch_draw(self.h, fft.h, C.c_void_p(stream) if stream else None),
                      "csdr_plotter_batch_draw")
+
+    def draw_emitted(self, fft, stream=None):
+        """draw of the running views whose row used a frame in fft's last put call -> views drawn"""
+        return check(lib().csdr_plotter_batch_draw_emitted(self.h, fft.h, C.c_void_p(stream) if stream else None),
+                     "csdr_plotter_batch_draw_emitted")
 
     def geometry(self, view):
         """(w, 2D height, waterfall height, m_MindB)"""

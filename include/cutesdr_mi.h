@@ -509,8 +509,13 @@ int csdr_fft_batch_get_waterfall_all(csdr_fft_batch *f, int max_w, double max_db
  * appends n samples of every row to the display stream.  Each sample has the channel's DC offset subtracted
  * (:889-894) and goes into the frame being filled (m_DataBuf, kept per channel on the device across calls).  When a
  * frame of `size` samples completes, the skip counter (:898-900) and, if enabled, the screen gate (:901-906) decide
- * whether it reaches PutInDisplayFFT.  The frame position, skip value, skip counter and gate are ONE set per object:
- * every row gets the same sample count per call.  Used frames go through exactly the averaging, log and overload code
+ * whether it reaches PutInDisplayFFT.  The frame position and the partial frame's length are one per object: every row
+ * gets the same sample count per call.  Skip value, skip counter, gate and ready flag -- and the averaging length -- are
+ * one set per object in the UNIFORM form, which the object-wide setters keep, and one set per ROW in the row form, which
+ * any csdr_fft_batch_*_row setter below enters: there each row is one listener with its own display rate, smoothing and
+ * ScreenUpdateDone(), a row that uses no frame in a call is not touched (average, counters and overload word as they
+ * were), and the put calls return the largest per-row count; csdr_fft_batch_get_emits tells which rows emitted.  Used
+ * frames go through exactly the averaging, log and overload code
  * of csdr_fft_batch_put_display, so get_ave / get_total_count / get_screen_all / get_waterfall_all work unchanged.
  * With the blanker on, the reference's display sees the blanked, delayed samples (:884 runs in place first):
  * csdr_fft_batch_put_display_stream_blanked / _packets_blanked below give that picture behind a blanked chain call,
@@ -528,8 +533,30 @@ int csdr_fft_batch_get_waterfall_all(csdr_fft_batch *f, int max_w, double max_db
 int csdr_fft_batch_set_display_rate(csdr_fft_batch *f, double sample_rate, int max_display_rate, int gated);
 /* ScreenUpdateDone() (sdrinterface.h:67) */
 int csdr_fft_batch_screen_update_done(csdr_fft_batch *f);
-/* StartSdr (:512, :591): frame position 0, gate open */
+/* StartSdr (:512, :591): frame position 0, gate open (in the row form: every row's) */
 int csdr_fft_batch_stream_reset(csdr_fft_batch *f);
+/* The row form.  row in [0, channels) is one row, row < 0 every row; any other row: CSDR_EINVAL, nothing changed.
+ * After one of the three setters the object is in the row form (csdr_fft_batch_row_form: 1) -- also when every row then
+ * holds the same values: nothing looks for uniformity.  There the five put calls plan each row by itself
+ * (put_display: every row nframes frames with the row's averaging length).  The object-wide csdr_fft_batch_set_ave
+ * and csdr_fft_batch_set_display_rate write every row and end their half (averaging / display) of the row form; with
+ * both ended the object is uniform again and runs the uniform code.  set_display_rate leaves ONE ready flag: set if every
+ * row's was.  csdr_fft_batch_screen_update_done sets every row ready.  csdr_fft_batch_set_params re-derives every row's
+ * skip value from that row's stored display rate and zeroes the counters.
+ * set_ave_row: CFft::SetFFTAve of that row (ave <= 0: 1), then ResetFFT of THAT row: average, sum and both counters of
+ * the other rows stay as they are.  reset_row: ResetFFT of one row (changes no form).
+ * set_display_rate_row: SetMaxDisplayRate at the object's sample rate (the last set_display_rate's, else set_params's fs)
+ * and size, counter 0; gated switches that row's m_ScreenUpateFinished handshake.  max_display_rate >= 1.
+ * screen_update_done_row: ScreenUpdateDone() of one listener.
+ * Not per row: FFT size, sample rate, invert flag, dB compensation, frame position, stream_reset. */
+int csdr_fft_batch_set_ave_row(csdr_fft_batch *f, int row, int ave);
+int csdr_fft_batch_reset_row(csdr_fft_batch *f, int row);
+int csdr_fft_batch_set_display_rate_row(csdr_fft_batch *f, int row, int max_display_rate, int gated);
+int csdr_fft_batch_screen_update_done_row(csdr_fft_batch *f, int row);
+int csdr_fft_batch_row_form(csdr_fft_batch *f);
+/* out[channels]: the frames each row used in the object's last put call, each one an emit NewFftData() for that
+ * listener (uniform form: every entry the call's return value).  Host state only: waits for nothing. */
+int csdr_fft_batch_get_emits(csdr_fft_batch *f, int *out);
 /* n samples of every row of d_in ([channels][in_stride] complex fp32, 8-byte aligned) appended to the display stream;
  * returns the number of frames that entered the average in this call (each one an emit NewFftData()), >= 0, or CSDR_E*.
  * d_dc: optional [channels][2] doubles (I, Q), subtracted as csdr_ingest_unpack does, (float)((double)v - dc); read on
@@ -1019,6 +1046,10 @@ int csdr_plotter_batch_set_running(csdr_plotter_batch *p, int view, int on);    
  * only; 2D height 0: a waterfall only, the trace all 0).  CSDR_EINVAL, nothing changed: f NULL or on another device, a running view whose row is >= f's
  * channels. */
 int csdr_plotter_batch_draw(csdr_plotter_batch *p, csdr_fft_batch *f, void *stream);
+/* csdr_plotter_batch_draw of the running views whose row emitted in f's last put call (csdr_fft_batch_get_emits > 0):
+ * every other view is left alone -- it does not scroll, keeps its trace and takes no pen step, and a pending
+ * set_ad_overload stays pending.  Returns the views drawn, as above. */
+int csdr_plotter_batch_draw_emitted(csdr_plotter_batch *p, csdr_fft_batch *f, void *stream);
 /* host readers: wait for the object's last call only (its event, on a stream of the object's own).
  * get_trace: the last draw's w levels into out_y and its pen into pen_red (1 red, 0 green; may be NULL); all 0 before
  * the first draw since the size changed; returns w.  get_waterfall: the image [wf_h][w], newest line first, black below the lines
