@@ -13,13 +13,6 @@
 
 using namespace csdr;
 
-static int log2_of(int n)
-{
-    int l = 0;
-    while ((1 << l) < n) l++;
-    return ((1 << l) == n) ? l : -1;
-}
-
 struct csdr_fastfir_batch {
     int device, channels, n, log2n;
     int cus;                          // compute units of the device (run-length heuristic)

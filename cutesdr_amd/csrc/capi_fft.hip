@@ -12,13 +12,6 @@
 
 using namespace csdr;
 
-static int log2_of(int n)
-{
-    int l = 0;
-    while ((1 << l) < n) l++;
-    return ((1 << l) == n) ? l : -1;
-}
-
 struct csdr_fft_batch {
     int device, channels;
     int size, last_size, ave_size, invert;       // m_FFTSize, m_LastFFTSize, m_AveSize, m_Invert
@@ -52,9 +45,8 @@ struct csdr_fft_batch {
     bool rows_ave = false, rows_disp = false;
     std::vector<DisplayState> rs, rs_next;
     std::vector<int> ave_r, rate_r;
-    // the frames each row used in the last put: `emits` after a row-form put, emit_all of every row after a uniform one
+    // the frames each row used in the last put (a uniform put fills it with its count)
     std::vector<int> emits, emits_next;
-    int emit_all = 0; bool emits_by_row = false;
     // the active-row tables of a row-form put travel as the plotter's parameters do (capi_plotter.hip): a ring of pinned
     // slots, [2][channels] entries each (gathered launch, loaded launch), copied on the caller's stream
     static constexpr int kTabRing = 16;
@@ -134,20 +126,37 @@ static int fft_rows_enter(csdr_fft_batch *f, bool ave, bool disp)
     }
     return CSDR_OK;
 }
-// a free slot of the table ring: waits, on that put's event only, when the put kTabRing before has not finished
-static int fft_tab_slot(csdr_fft_batch *f, int *slot)
-{
-    *slot = f->tab_next;
-    if (f->tab_busy[*slot]) { CSDR_HIP(hipEventSynchronize(f->tab_ev[*slot])); f->tab_busy[*slot] = false; }
-    return CSDR_OK;
-}
-static int fft_tab_sent(csdr_fft_batch *f, int slot, hipStream_t st)
-{
-    CSDR_HIP(hipEventRecord(f->tab_ev[slot], st));
-    f->tab_busy[slot] = true;
-    f->tab_next = (slot + 1) % csdr_fft_batch::kTabRing;
-    return CSDR_OK;
-}
+// One put's slot of the table ring: acquire() waits, on that put's event only, when the put kTabRing before has not
+// finished; send() copies the first n entries of a table behind the stream's work.  A slot that something was sent from
+// is marked busy behind the stream when the put leaves, by whichever return: its copies may be in flight after an error
+// too, and the ring moves on only past a used slot.
+struct TabSlot {
+    csdr_fft_batch *f; hipStream_t st; int slot; bool sent = false;
+    TabSlot(csdr_fft_batch *f_, hipStream_t st_) : f(f_), st(st_), slot(f_->tab_next) {}
+    TabSlot(const TabSlot &) = delete;
+    SpecRow *host(int table = 0) const { return f->h_tab[slot] + (size_t)table * f->channels; }
+    SpecRow *dev(int table = 0) const { return f->d_tab[slot] + (size_t)table * f->channels; }
+    int acquire()
+    {
+        if (f->tab_busy[slot]) { CSDR_HIP(hipEventSynchronize(f->tab_ev[slot])); f->tab_busy[slot] = false; }
+        return CSDR_OK;
+    }
+    hipError_t send(int table, int n)
+    {
+        sent = true;
+        return hipMemcpyAsync(dev(table), host(table), sizeof(SpecRow) * (size_t)n, hipMemcpyHostToDevice, st);
+    }
+    int done()                           // the put's last use of the slot is on the stream
+    {
+        if (!sent) return CSDR_OK;
+        sent = false;
+        f->tab_next = (slot + 1) % csdr_fft_batch::kTabRing;
+        CSDR_HIP(hipEventRecord(f->tab_ev[slot], st));
+        f->tab_busy[slot] = true;
+        return CSDR_OK;
+    }
+    ~TabSlot() { (void)done(); }         // (an error return)
+};
 // row < 0: every row (the plotter's view < 0); [lo, hi) or CSDR_EINVAL with nothing changed
 static int fft_row_range(csdr_fft_batch *f, int row, int *lo, int *hi)
 {
@@ -178,9 +187,9 @@ static int fft_set_params(csdr_fft_batch *f, int size, int invert, double db_com
         CSDR_HIP(hipMalloc((void **)&f->d_pwr, nb));
         CSDR_HIP(hipMalloc((void **)&f->d_ave, nb));
         CSDR_HIP(hipMalloc((void **)&f->d_carry, nb * 2));
-        if (l2 < 11 || l2 > 14) CSDR_HIP(hipMalloc((void **)&f->d_work, nb * 4));   // [2][channels][N] complex
+        if (!spectrum_single_launch(l2)) CSDR_HIP(hipMalloc((void **)&f->d_work, nb * 4));   // [2][channels][N] complex
         f->plain_group = 0;
-        if (l2 > 14) {
+        if (l2 > PLAIN_MAX_LOG2N) {
             // the work buffer holds 64 frames (a launch of 512 ... 1024 workgroups), and at least one of every row
             f->plain_group = f->channels < 64 ? 64 / f->channels : 1;
             CSDR_HIP(hipMalloc((void **)&f->d_twp, 512 * 8));
@@ -306,7 +315,7 @@ int csdr_fft_batch_row_form(csdr_fft_batch *f) { return f ? (int)fft_row_form(f)
 int csdr_fft_batch_get_emits(csdr_fft_batch *f, int *out)
 {   // host state only: the frames each row used in the last put
     if (!f || !out) return fail(CSDR_EINVAL, "bad argument");
-    for (int r = 0; r < f->channels; r++) out[r] = f->emits_by_row ? f->emits[r] : f->emit_all;
+    std::copy(f->emits.begin(), f->emits.end(), out);
     return CSDR_OK;
 }
 int csdr_fft_batch_reset(csdr_fft_batch *f)
@@ -345,24 +354,15 @@ static int fft_put_frames(csdr_fft_batch *f, const float *d_in, long long in_str
     a.channels = f->channels; a.nframes = nframes; a.ave_size = f->ave_size;
     if (rows) { a.rows = rows->dev; a.nrows = rows->n; }
     const int active = rows ? rows->n : f->channels;       // the channels that get workgroups
-    // long calls on few channels: cut each channel's frames into groups so that ONE round of workgroups fills the chip --
-    // 4 / 2 / 1 workgroups per CU at 4096 / 8192 / 16384 points (their LDS images; 2048 points fit eight, and measure 2 %
-    // better with four).  (Until round 4 the target was 1024 workgroups for every size: at 16384 points that was four
-    // rounds, and a workgroup's start -- tables, window, sums, the first frame's latency -- costs five frames' time:
-    // 0.39 ms for 256 channels x 32 frames against 0.33; 8192 points -2 %.)
+    // long calls on few channels: cut each channel's frames into groups so that ONE round of workgroups fills the chip
     a.nparts = 1; a.part = nullptr; a.alpha = nullptr;
     const int l2 = log2_of(f->size);
-    {
-        const long per_cu = l2 <= 12 ? 4 : (l2 == 13 ? 2 : 1);
-        const long slots = (l2 >= 11 && l2 <= 14) ? 256 * per_cu : 1024;
-        long np = (slots + active - 1) / active;
-        if (np > nframes / 8) np = nframes / 8;
-        if (np > 1) {
-            const size_t need = (size_t)f->channels * np * f->size + (size_t)f->channels * (np + 1);   // + the group weights
-            CSDR_HIP(fft_grow(f->d_part, f->part_cap, need, (hipStream_t)stream));
-            a.nparts = (int)np; a.part = f->d_part;
-            a.alpha = f->d_part + (size_t)f->channels * np * f->size;
-        }
+    const size_t np = (size_t)spectrum_groups(nframes, (spectrum_round_slots(l2) + active - 1) / active);
+    if (np > 1) {
+        const size_t need = (size_t)f->channels * np * f->size + (size_t)f->channels * (np + 1);   // + the group weights
+        CSDR_HIP(fft_grow(f->d_part, f->part_cap, need, (hipStream_t)stream));
+        a.nparts = (int)np; a.part = f->d_part;
+        a.alpha = f->d_part + (size_t)f->channels * np * f->size;
     }
     a.kc = (float)f->kc; a.kb = f->kb;
     a.frame_start = src ? src->start : 0; a.frame_step = src ? src->step : f->size;
@@ -372,7 +372,7 @@ static int fft_put_frames(csdr_fft_batch *f, const float *d_in, long long in_str
     a.nb_mask = blank ? blank->mask : nullptr; a.nb_mask_stride = blank ? blank->mask_stride : 0;
     a.nb_state = blank ? (const NbChan *)blank->state : nullptr;
     if (src) CSDR_HIP(spectrum_stream_launch(l2, a, src->pkt_len, (hipStream_t)stream));
-    else if (l2 >= 11 && l2 <= 14) CSDR_HIP(spectrum_launch(l2, a, (hipStream_t)stream));
+    else if (spectrum_single_launch(l2)) CSDR_HIP(spectrum_launch(l2, a, (hipStream_t)stream));
     else CSDR_HIP(spectrum_generic_launch(l2, a, f->d_work, (hipStream_t)stream, rows ? rows->host : nullptr));
     return CSDR_OK;
 }
@@ -383,22 +383,19 @@ int csdr_fft_batch_put_display(csdr_fft_batch *f, const float *d_in, long long i
     if (nframes == 0) return CSDR_OK;
     if (!device_ok(f->device)) return CSDR_EHIP;
     if (!fft_row_form(f)) {
-        const int rc = fft_put_frames(f, d_in, in_stride, nframes, stream);
-        if (rc == CSDR_OK) { f->emit_all = nframes; f->emits_by_row = false; }
-        return rc;
+        if (int rc = fft_put_frames(f, d_in, in_stride, nframes, stream)) return rc;
+    } else {             // every row nframes frames, each with its own averaging length
+        TabSlot slot(f, (hipStream_t)stream);
+        if (int rc = slot.acquire()) return rc;
+        SpecRow *h = slot.host();
+        for (int r = 0; r < f->channels; r++)
+            h[r] = SpecRow{r, nframes, f->rows_ave ? f->ave_r[r] : f->ave_size, 0, 0, f->size};
+        CSDR_HIP(slot.send(0, f->channels));
+        const RowTable tab{slot.dev(), h, f->channels};
+        if (int rc = fft_put_frames(f, d_in, in_stride, nframes, stream, nullptr, &tab)) return rc;
+        if (int rc = slot.done()) return rc;
     }
-    // the row form: every row nframes frames, each with its own averaging length
-    int slot;
-    if (int rc = fft_tab_slot(f, &slot)) return rc;
-    SpecRow *h = f->h_tab[slot];
-    for (int r = 0; r < f->channels; r++)
-        h[r] = SpecRow{r, nframes, f->rows_ave ? f->ave_r[r] : f->ave_size, 0, 0, f->size};
-    hipStream_t st = (hipStream_t)stream;
-    CSDR_HIP(hipMemcpyAsync(f->d_tab[slot], h, sizeof(SpecRow) * (size_t)f->channels, hipMemcpyHostToDevice, st));
-    const RowTable tab{f->d_tab[slot], h, f->channels};
-    if (int rc = fft_put_frames(f, d_in, in_stride, nframes, stream, nullptr, &tab)) return rc;
-    if (int rc = fft_tab_sent(f, slot, st)) return rc;
-    f->emit_all = nframes; f->emits_by_row = false;
+    f->emits.assign((size_t)f->channels, nframes);
     return CSDR_OK;
 }
 
@@ -418,44 +415,57 @@ int csdr_fft_batch_put_display(csdr_fft_batch *f, const float *d_in, long long i
 // launches, each over its table of active rows: the gathered frames (the frame that begins in the carry; every frame at
 // 16384 points, at the multi-launch sizes and behind a blanker), then the frames the stream loaders read where they lie,
 // with each row's start and step.  A row that uses no frame is in neither table: nothing of it is read or written.
+// the call's samples in front of the carried partial frame, as the gather and the carry read them
+static StreamSrc fft_stream_src(const csdr_fft_batch *f, const float *d_in, long long in_stride, const WireIn &wire,
+                                const double *d_dc, const DcBlank *blank)
+{
+    StreamSrc a;
+    a.in = d_in; a.in_stride = (long)in_stride; a.wire = wire; a.dc = d_dc;
+    a.carry = f->d_carry; a.pos = f->ds.pos; a.carry_stride = f->size; a.channels = f->channels;
+    a.nb_mask = blank ? blank->mask : nullptr; a.nb_mask_stride = blank ? blank->mask_stride : 0;
+    a.nb_state = blank ? (const NbChan *)blank->state : nullptr; a.nb_hist = blank ? blank->hist : nullptr;
+    return a;
+}
+// m_DataBuf after a call of n samples: they are appended when no frame completed, else it holds the last next_pos of them
+static int fft_carry(csdr_fft_batch *f, const StreamSrc &a, long long n, int next_pos, hipStream_t st)
+{
+    if (f->ds.pos + n < f->size) CSDR_HIP(display_carry_launch(a, f->d_carry, f->ds.pos, 0, (int)n, st));
+    else CSDR_HIP(display_carry_launch(a, f->d_carry, 0, n - next_pos, next_pos, st));
+    return CSDR_OK;
+}
+
 static int fft_put_stream_rows(csdr_fft_batch *f, const float *d_in, long long in_stride, const WireIn &wire, long long n,
                                const double *d_dc, void *stream, const DcBlank *blank)
 {
     const int N = f->size, l2 = log2_of(N), C = f->channels;
-    const bool loaders = !blank && l2 >= 11 && l2 <= 13;
+    const bool loaders = !blank && spectrum_stream_loaders_ok(l2);
     hipStream_t st = (hipStream_t)stream;
     if (!f->rows_disp) f->rs.assign((size_t)C, f->ds);
     if (!f->rows_ave) f->ave_r.assign((size_t)C, f->ave_size);
-    int slot;
-    if (int rc = fft_tab_slot(f, &slot)) return rc;
-    SpecRow *hg = f->h_tab[slot], *hl = hg + C;
-    SpecRow *dg = f->d_tab[slot], *dl = dg + C;
+    TabSlot slot(f, st);
+    if (int rc = slot.acquire()) return rc;
+    enum { GATH, LOAD };
     const DisplayRowsSplit d = display_rows_plan(f->rs.data(), f->ave_r.data(), C, f->ds.pos, n, N, loaders, 0,
-                                                 l2 < 11 || l2 > 14, f->rs_next.data(), f->emits_next.data(), hg, hl);
-    StreamSrc a;
-    a.in = d_in; a.in_stride = (long)in_stride; a.wire = wire; a.dc = d_dc;
-    a.carry = f->d_carry; a.pos = f->ds.pos; a.carry_stride = N; a.channels = C;
-    a.nb_mask = blank ? blank->mask : nullptr; a.nb_mask_stride = blank ? blank->mask_stride : 0;
-    a.nb_state = blank ? (const NbChan *)blank->state : nullptr; a.nb_hist = blank ? blank->hist : nullptr;
+                                                 !spectrum_single_launch(l2), f->rs_next.data(), f->emits_next.data(),
+                                                 slot.host(GATH), slot.host(LOAD));
+    const StreamSrc a = fft_stream_src(f, d_in, in_stride, wire, d_dc, blank);
     if (d.ngath > 0) {
         CSDR_HIP(fft_grow(f->d_stage, f->stage_cap, (size_t)C * d.max_gath * N * 2, st));
-        CSDR_HIP(hipMemcpyAsync(dg, hg, sizeof(SpecRow) * (size_t)d.ngath, hipMemcpyHostToDevice, st));
-        CSDR_HIP(display_gather_rows_launch(a, dg, d.ngath, d.max_gath, N, f->d_stage, st));
-        const RowTable tab{dg, hg, d.ngath};
+        CSDR_HIP(slot.send(GATH, d.ngath));
+        CSDR_HIP(display_gather_rows_launch(a, slot.dev(GATH), d.ngath, d.max_gath, N, f->d_stage, st));
+        const RowTable tab{slot.dev(GATH), slot.host(GATH), d.ngath};
         if (int rc = fft_put_frames(f, f->d_stage, (long long)d.max_gath * N, d.max_gath, stream, nullptr, &tab)) return rc;
     }
     if (d.nload > 0) {
-        CSDR_HIP(hipMemcpyAsync(dl, hl, sizeof(SpecRow) * (size_t)d.nload, hipMemcpyHostToDevice, st));
+        CSDR_HIP(slot.send(LOAD, d.nload));
         const FrameSrc src{0, 0, d_dc, wire.pk, wire.chan_stride, wire.pkt_len, nullptr};
-        const RowTable tab{dl, hl, d.nload};
+        const RowTable tab{slot.dev(LOAD), slot.host(LOAD), d.nload};
         if (int rc = fft_put_frames(f, d_in, in_stride, d.max_load, stream, &src, &tab)) return rc;
     }
-    if (d.ngath + d.nload > 0)
-        if (int rc = fft_tab_sent(f, slot, st)) return rc;
-    if (f->ds.pos + n < N) CSDR_HIP(display_carry_launch(a, f->d_carry, f->ds.pos, 0, (int)n, st));
-    else CSDR_HIP(display_carry_launch(a, f->d_carry, 0, n - d.next_pos, d.next_pos, st));
+    if (int rc = slot.done()) return rc;
+    if (int rc = fft_carry(f, a, n, d.next_pos, st)) return rc;
     f->rs.swap(f->rs_next);
-    f->emits.swap(f->emits_next); f->emits_by_row = true;
+    f->emits.swap(f->emits_next);
     if (!f->rows_disp) f->ds = f->rs[0];
     f->ds.pos = d.next_pos;
     return d.max_count;
@@ -464,22 +474,19 @@ static int fft_put_stream_rows(csdr_fft_batch *f, const float *d_in, long long i
 static int fft_put_stream(csdr_fft_batch *f, const float *d_in, long long in_stride, const WireIn &wire, long long n,
                           const double *d_dc, void *stream, const DcBlank *blank = nullptr)
 {
-    if (n == 0) { f->emit_all = 0; f->emits_by_row = false; return 0; }
+    if (n == 0) { f->emits.assign((size_t)f->channels, 0); return 0; }
     if (!device_ok(f->device)) return CSDR_EHIP;
     if (fft_row_form(f)) return fft_put_stream_rows(f, d_in, in_stride, wire, n, d_dc, stream, blank);
     const int N = f->size, l2 = log2_of(N);
     // (CSDR_DISPLAY_BLANKED_LOADERS=0: every used frame of a blanked call through the gather -- the A/B of
     // tools/bench_display_blanked.py; the words are the same)
     static const bool blanked_loaders = !(getenv("CSDR_DISPLAY_BLANKED_LOADERS") && atoi(getenv("CSDR_DISPLAY_BLANKED_LOADERS")) == 0);
-    const bool loaders = blank ? blanked_loaders && spectrum_stream_blanked_ok(l2, wire.pk ? wire.pkt_len : 0) : l2 >= 11 && l2 <= 13;
+    const bool loaders = blank ? blanked_loaders && spectrum_stream_blanked_ok(l2, wire.pk ? wire.pkt_len : 0)
+                               : spectrum_stream_loaders_ok(l2);
     const long long first_loaded = blank ? NB_MAX_WIDTH / 2 + 1 : 0;       // the loaders take frames from here on
     const DisplayPlan p = display_plan(f->ds, n, N);
     hipStream_t st = (hipStream_t)stream;
-    StreamSrc a;
-    a.in = d_in; a.in_stride = (long)in_stride; a.wire = wire; a.dc = d_dc;
-    a.carry = f->d_carry; a.pos = f->ds.pos; a.carry_stride = N; a.channels = f->channels;
-    a.nb_mask = blank ? blank->mask : nullptr; a.nb_mask_stride = blank ? blank->mask_stride : 0;
-    a.nb_state = blank ? (const NbChan *)blank->state : nullptr; a.nb_hist = blank ? blank->hist : nullptr;
+    const StreamSrc a = fft_stream_src(f, d_in, in_stride, wire, d_dc, blank);
     long long start = p.start;
     int left = p.count;
     auto in_place = [&](int k) { return !blank && !wire.pk && !d_dc && start >= 0 && (k == 1 || p.step == N); };
@@ -502,11 +509,9 @@ static int fft_put_stream(csdr_fft_batch *f, const float *d_in, long long in_str
         }
         if (rc) return rc;
     }
-    // m_DataBuf after the call: the call's samples appended when no frame completed, else the last next.pos of them
-    if (f->ds.pos + n < N) CSDR_HIP(display_carry_launch(a, f->d_carry, f->ds.pos, 0, (int)n, st));
-    else CSDR_HIP(display_carry_launch(a, f->d_carry, 0, n - p.next.pos, p.next.pos, st));
+    if (int rc = fft_carry(f, a, n, p.next.pos, st)) return rc;
     f->ds = p.next;
-    f->emit_all = p.count; f->emits_by_row = false;
+    f->emits.assign((size_t)f->channels, p.count);
     return p.count;
 }
 
@@ -629,6 +634,18 @@ int csdr_fft_batch_get_total_count(csdr_fft_batch *f, int channel)
     return c[1];
 }
 
+// the display bins of start_hz ... stop_hz (fft.cpp:336-349)
+static void fft_bin_range(const csdr_fft_batch *f, int start_hz, int stop_hz, int *bin_min, int *bin_max)
+{
+    const int n = f->size, maxbin = n - 1;
+    *bin_min = (int)((double)start_hz * (double)n / f->fs) + n / 2;
+    *bin_max = (int)((double)stop_hz * (double)n / f->fs) + n / 2;
+    if (*bin_min < 0) *bin_min = 0;
+    if (*bin_min >= maxbin) *bin_min = maxbin;
+    if (*bin_max < 0) *bin_max = 0;
+    if (*bin_max >= maxbin) *bin_max = maxbin;
+}
+
 /* CFft::GetScreenIntegerFFTData (fft.cpp:308-410) on the N-float read-back of one channel.
  * Returns 1 if the last PutInDisplayFFT saw an overload, 0 otherwise. */
 int csdr_fft_batch_get_screen(csdr_fft_batch *f, int channel, int max_h, int max_w, double max_db, double min_db,
@@ -645,14 +662,8 @@ int csdr_fft_batch_get_screen(csdr_fft_batch *f, int channel, int max_h, int max
     int i, x, y, ymax = 10000, xprev = -1;
     const double off = max_db / 10.0, gain = -10.0 / (max_db - min_db);
     if (f->start_hz != start_hz || f->stop_hz != stop_hz || f->plot_w != max_w) {
-        const int maxbin = n - 1;
         f->start_hz = start_hz; f->stop_hz = stop_hz; f->plot_w = max_w;
-        f->bin_min = (int)((double)start_hz * (double)n / f->fs) + n / 2;
-        f->bin_max = (int)((double)stop_hz * (double)n / f->fs) + n / 2;
-        if (f->bin_min < 0) f->bin_min = 0;
-        if (f->bin_min >= maxbin) f->bin_min = maxbin;
-        if (f->bin_max < 0) f->bin_max = 0;
-        if (f->bin_max >= maxbin) f->bin_max = maxbin;
+        fft_bin_range(f, start_hz, stop_hz, &f->bin_min, &f->bin_max);
         if ((f->bin_max - f->bin_min) > f->plot_w) {
             for (i = f->bin_min; i <= f->bin_max; i++)
                 f->xlat[i] = ((i - f->bin_min) * f->plot_w) / (f->bin_max - f->bin_min);
@@ -692,15 +703,9 @@ int csdr_fft_batch_get_screen_all(csdr_fft_batch *f, int max_h, int max_w, doubl
 {
     if (!f || !d_out || max_w < 0 || out_stride < max_w) return fail(CSDR_EINVAL, "bad argument");
     if (!device_ok(f->device)) return CSDR_EHIP;
-    const int n = f->size, maxbin = n - 1;
     ScreenArgs a;
-    a.ave = f->d_ave; a.out = d_out; a.out_stride = out_stride; a.n = n; a.channels = f->channels;
-    a.bin_min = (int)((double)start_hz * (double)n / f->fs) + n / 2;      // fft.cpp:336-349
-    a.bin_max = (int)((double)stop_hz * (double)n / f->fs) + n / 2;
-    if (a.bin_min < 0) a.bin_min = 0;
-    if (a.bin_min >= maxbin) a.bin_min = maxbin;
-    if (a.bin_max < 0) a.bin_max = 0;
-    if (a.bin_max >= maxbin) a.bin_max = maxbin;
+    a.ave = f->d_ave; a.out = d_out; a.out_stride = out_stride; a.n = f->size; a.channels = f->channels;
+    fft_bin_range(f, start_hz, stop_hz, &a.bin_min, &a.bin_max);
     a.plot_w = max_w; a.max_h = max_h; a.invert = f->invert;
     a.off = max_db / 10.0; a.gain = -10.0 / (max_db - min_db);
     CSDR_HIP(screen_launch(a, (hipStream_t)stream));
@@ -896,7 +901,7 @@ static int fft_plain(csdr_fft *f, double *inout, int sign)
     hipStream_t st = f->s;
     CSDR_HIP(hipMemcpyAsync(f->d_buf, f->pin.p, (size_t)N * 8, hipMemcpyHostToDevice, st));
     const int l2 = log2_of(N);
-    if (l2 >= 11 && l2 <= 14) CSDR_HIP(fft_plain_launch(l2, sign, f->d_buf, f->d_buf, f->b->d_tw1, f->b->d_tw2, st));
+    if (spectrum_single_launch(l2)) CSDR_HIP(fft_plain_launch(l2, sign, f->d_buf, f->d_buf, f->b->d_tw1, f->b->d_tw2, st));
     else CSDR_HIP(fft_generic_plain_launch(l2, sign, f->d_buf, f->d_buf, f->b->d_work, st));
     CSDR_HIP(hipMemcpyAsync(f->pin.p, f->d_buf, (size_t)N * 8, hipMemcpyDeviceToHost, st));
     CSDR_HIP(hipStreamSynchronize(st));

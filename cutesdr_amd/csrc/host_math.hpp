@@ -14,6 +14,14 @@ typedef std::complex<double> cd;
 constexpr double kTwoPi = 2.0 * 3.14159265358979323846;   // K_2PI, dsp/datatypes.h:44
 constexpr double kPi = 3.14159265358979323846;
 
+// log2 of a power of two, -1 of anything else
+inline int log2_of(int n)
+{
+    int l = 0;
+    while ((1 << l) < n) l++;
+    return ((1 << l) == n) ? l : -1;
+}
+
 // Tables a design reuses (round 6: a same-mode SetDemod is the control plane's whole cost -- 84 us per call, two thirds of it
 // the 2047 twiddles and the 3075 window cosines recomputed every time): cos / sin(2 pi j / n), j < n / 2, per transform size,
 // and CFastFIR's window per tap count.  A stage of length len uses every (n / len)-th entry: k / len and (k n / len) / n are

@@ -33,8 +33,37 @@ struct SpectrumArgs {
     // are not read.  part and alpha stay indexed by channel.  nullptr: the uniform form, every channel nframes frames.
     const SpecRow *rows = nullptr; int nrows = 0;
 };
-// which sizes have a blanked form of the stream loaders (pkt_len 0: fp32 rows); the others gather their frames
-bool spectrum_stream_blanked_ok(int log2n, int pkt_len);
+// The frame groups of a row of nframes frames in a launch with room for `room` workgroups per row: eight frames a group
+// at least.  The host sizes the launch with it (capi_fft.hip, from the longest row) and the kernels find each row's own
+// count with it, so what a row computes depends on its own frames alone.
+__host__ __device__ inline int spectrum_groups(int nframes, int room)
+{
+    const int g = nframes / 8;
+    return g < 1 ? 1 : (g < room ? g : room);
+}
+// The size classes, from the largest size that a kind of loader has a kernel for (the other sizes gather their frames,
+// capi_fft.hip).  The display stream's loaders run in the sixteen-point kernels only: at 16384 points
+// (spectrum_kernel<14>, 512 threads, at most 256 registers) the datagram loaders spilled 164 / 236 bytes and the DC row
+// loader 12 bytes of scratch per lane.  The blanked loaders exist at 2048 and 4096 points: at 8192 points
+// (spectrum32_kernel, 512 threads: at most 256 registers) the mask word per prefetched sample spilled -- 72 bytes of
+// scratch per lane on fp32 rows, 16 on 16-bit and 124 on 24-bit datagrams.
+constexpr int SPEC_MIN_LOG2N = 11, PLAIN_MAX_LOG2N = 14, STREAM_MAX_LOG2N = 13, BLANKED_MAX_LOG2N = 12;
+// one launch per call (spectrum_launch, fft_plain_launch); the other sizes go through HBM in several (spectrum_generic_launch)
+constexpr bool spectrum_single_launch(int log2n) { return log2n >= SPEC_MIN_LOG2N && log2n <= PLAIN_MAX_LOG2N; }
+// The workgroups of one round on the chip: 4 / 2 / 1 per CU at 4096 / 8192 / 16384 points (their LDS images; 2048 points
+// fit eight, and measure 2 % better with four).  (Until round 4 the target was 1024 workgroups for every size, as it still
+// is for the multi-launch ones: at 16384 points that was four rounds, and a workgroup's start -- tables, window, sums, the
+// first frame's latency -- costs five frames' time: 0.39 ms for 256 channels x 32 frames against 0.33; 8192 points -2 %.)
+constexpr int spectrum_round_slots(int log2n)
+{
+    return !spectrum_single_launch(log2n) ? 1024 : 256 * (log2n <= 12 ? 4 : (log2n == 13 ? 2 : 1));
+}
+// the stream loaders (spectrum_stream_launch), and their blanked form (pkt_len 0: fp32 rows)
+constexpr bool spectrum_stream_loaders_ok(int log2n) { return log2n >= SPEC_MIN_LOG2N && log2n <= STREAM_MAX_LOG2N; }
+constexpr bool spectrum_stream_blanked_ok(int log2n, int pkt_len)
+{
+    return log2n >= SPEC_MIN_LOG2N && log2n <= BLANKED_MAX_LOG2N && (pkt_len == 0 || pkt_len == 1028 || pkt_len == 1444);
+}
 hipError_t spectrum_launch(int log2n, const SpectrumArgs &a, hipStream_t stream);
 // 2048 ... 8192 points with the frame load of the display stream: fp32 rows (a.pk == nullptr) or datagrams of
 // pkt_len 1028 / 1444 decoded in the load, frames at frame_start + f frame_step, DC subtracted

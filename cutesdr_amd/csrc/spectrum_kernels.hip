@@ -7,13 +7,17 @@
 // the transform is a three-pass decimation-in-time FFT with the FMA butterflies of the overlap-save kernel
 // (fft_core.hpp), its output is scattered straight into display order.  8 B in + 4 B out per bin.
 // The file in the order it reads:
+//   SpecJob            what a workgroup works on -- channel, frame group of how many, frame count, averaging length, frame
+//                      positions, partial-sum slots -- filled from the block index (uniform form) or from the launch's
+//                      table of active rows (row form); everything below reads the job, not the form
 //   frame loaders      where sample i of frame f comes from: rows, rows + DC, datagrams, each behind a blanker's mask
 //   transforms         Passes32 (16384 points, 32 per thread) and Wide16<PassB...> (2048 / 4096 / 8192, 16 per thread:
 //                      passes A and C and the fence between B and C once, pass B per size)
 //   spectrum_frames    THE frame loop: prologue, frame load with window and overload test, counters, running sum,
 //                      epilogue with the display-order scatter -- each rule once, for every transform and loader
-//   the kernels        spectrum_kernel<14>, spectrum8 / 16 / 32_kernel: launch bounds around spectrum_frames
-//   fft_plain_kernel, the frame-group combine, and the launchers (one size switch, bounded by the loader's largest size)
+//   the kernels        spectrum_kernel<14>, spectrum8 / 16 / 32_kernel<loader, form>: launch bounds around job and loop
+//   fft_plain_kernel, the frame-group weights and combine, and the launcher (one size switch for both forms, bounded by
+//   the loader's largest size)
 #define CSDR_FMA_BFLY 1          // FMA-form decimation-in-time butterflies (fft_core.hpp)
 #define CSDR_PLAIN_CONST_FMA 1
 #include "launch_once.hpp"
@@ -25,6 +29,46 @@
 
 namespace csdr {
 
+// ---- what a workgroup works on: frame group `group` of the `groups` that the nframes frames of channel ch are cut
+// into.  With groups > 1 a group accumulates its frames from zero into its slot of `part` and the combine folds the
+// groups in order (the running sum is the linear map sum <- alpha_f sum + p_f).  The launch has `slots` slots per channel:
+// group g's partial sums are a.part + slot(g) N, its weight a.alpha[slot(g)].
+struct SpecJob {
+    int ch, group, groups;
+    int nframes, ave_size;            // the channel's frames in this launch and its m_AveSize
+    long start, step;                 // the stream loaders: frame f at sample start + f step of the call
+    int slots;
+    bool own_overload;                // no launcher cleared the channel's overload word: its last group does
+    __device__ __forceinline__ long slot(int g) const { return (long)ch * slots + g; }
+};
+// The job of entry `idx` of the launch and frame group `group`; false: that group has no frames, nothing to do.
+// Uniform form: entry = channel, every value the launch's.  Row form: the entry of the launch's table of active rows
+// (wave-uniform loads, once per workgroup).  A row cuts ITS frame count into groups, eight frames a group at least, and
+// takes the first of the launch's nparts workgroups per row; the others leave at once.  So what a row computes depends
+// on its own frames alone -- not on how many frames the other rows of the launch have -- and a row below sixteen frames
+// runs the one-group path, whose words are those of the frames in order.
+template <bool ROWS>
+__device__ __forceinline__ bool spec_job(const SpectrumArgs &a, int idx, int group, SpecJob &j)
+{
+    if constexpr (ROWS) {
+        const SpecRow e = a.rows[idx];
+        j = SpecJob{e.row, group, spectrum_groups(e.nframes, a.nparts), e.nframes, e.ave_size, (long)e.start, (long)e.step,
+                    a.nparts, true};
+    } else {
+        j = SpecJob{idx, group, a.nparts, a.nframes, a.ave_size, a.frame_start, a.frame_step, a.nparts, false};
+        return true;             // (group < nparts by the launch's grid: said outright, the compare cost the kernels SGPRs)
+    }
+    return group < j.groups;
+}
+// frames [group_frame(g), group_frame(g + 1)) are group g's
+__device__ __forceinline__ int group_frame(const SpecJob &j, int g) { return (int)((long)j.nframes * g / j.groups); }
+// the average count k frames after ave0: it saturates at ave_size (a count above it -- the average was shortened -- stays);
+// the total count is total0 + k
+__device__ __forceinline__ int ave_count_after(int ave0, int k, int ave_size)
+{
+    return ave0 + k < ave_size ? ave0 + k : (ave0 > ave_size ? ave0 : ave_size);
+}
+
 
 // ---- frame loaders: where sample i of a channel's frame f comes from.  fetch() issues the load and returns the raw
 // value, decode() turns it into the complex sample where it is consumed (a prefetched frame's decode must not make the
@@ -32,8 +76,8 @@ namespace csdr {
 struct RowLoad {                          // csdr_fft_batch_put_display: frames back to back from the row's start
     typedef v2f Raw;
     const v2f *in;
-    __device__ __forceinline__ RowLoad(const SpectrumArgs &a, int ch)
-        : in(reinterpret_cast<const v2f *>(a.in) + (long)ch * a.in_stride) {}
+    __device__ __forceinline__ RowLoad(const SpectrumArgs &a, const SpecJob &j)
+        : in(reinterpret_cast<const v2f *>(a.in) + (long)j.ch * a.in_stride) {}
     template <int N> __device__ __forceinline__ Raw fetch(int f, int i) const { return in[(long)f * N + i]; }
     __device__ __forceinline__ v2f decode(Raw r) const { return r; }
 };
@@ -50,8 +94,8 @@ struct StreamDc {
 struct RowDcLoad {                        // fp32 rows
     typedef v2f Raw;
     const v2f *in; long start, step; StreamDc dc;
-    __device__ __forceinline__ RowDcLoad(const SpectrumArgs &a, int ch)
-        : in(reinterpret_cast<const v2f *>(a.in) + (long)ch * a.in_stride), start(a.frame_start), step(a.frame_step), dc(a, ch) {}
+    __device__ __forceinline__ RowDcLoad(const SpectrumArgs &a, const SpecJob &j)
+        : in(reinterpret_cast<const v2f *>(a.in) + (long)j.ch * a.in_stride), start(j.start), step(j.step), dc(a, j.ch) {}
     template <int N> __device__ __forceinline__ Raw fetch(int f, int i) const { return in[start + (long)f * step + i]; }
     __device__ __forceinline__ v2f decode(Raw r) const { return dc.sub(r.x, r.y); }
 };
@@ -60,8 +104,8 @@ template <int PKT>                        // datagrams (wire_format.hpp): 1028 =
 struct WireLoad {
     typedef typename std::conditional<PKT == 1444, Raw24, unsigned>::type Raw;
     const unsigned char *chan; long start, step; StreamDc dc;
-    __device__ __forceinline__ WireLoad(const SpectrumArgs &a, int ch)
-        : chan(a.pk + (long)ch * a.pk_stride), start(a.frame_start), step(a.frame_step), dc(a, ch) {}
+    __device__ __forceinline__ WireLoad(const SpectrumArgs &a, const SpecJob &j)
+        : chan(a.pk + (long)j.ch * a.pk_stride), start(j.start), step(j.step), dc(a, j.ch) {}
     template <int N> __device__ __forceinline__ Raw fetch(int f, int i) const
     {
         const unsigned s = (unsigned)(start + (long)f * step) + (unsigned)i;      // < 2^31: a call stays below 2 GiB
@@ -98,11 +142,11 @@ template <class Inner>
 struct BlankedLoad {
     struct Raw { typename Inner::Raw r; unsigned m, sh; };
     Inner in; const unsigned *mrow; long start, step; v2f zero;
-    __device__ __forceinline__ BlankedLoad(const SpectrumArgs &a, int ch)
-        : in(a, ch), mrow(a.nb_mask + (long)ch * a.nb_mask_stride), start(a.frame_start), step(a.frame_step),
+    __device__ __forceinline__ BlankedLoad(const SpectrumArgs &a, const SpecJob &j)
+        : in(a, j), mrow(a.nb_mask + (long)j.ch * a.nb_mask_stride), start(j.start), step(j.step),
           zero(in.dc.sub(0.f, 0.f))
     {
-        const NbChan *nb = a.nb_state + ch;
+        const NbChan *nb = a.nb_state + j.ch;
         in.start -= nb->on ? nb->delay_n + 1 : 0;         // (off: the mask pass left the row all zero, as the down-converter relies on)
     }
     template <int N> __device__ __forceinline__ Raw fetch(int f, int i) const
@@ -323,31 +367,25 @@ struct Wide16 {
     static __device__ __forceinline__ int bin0(int t) { return (t >> PassB::LOG2B) + 16 * (t & (T / 16 - 1)); }
 };
 
-// ---- the frame loop: one workgroup walks the frames f0 ... f1 of its channel through transform X, loaded by Ld -------
-// ROWS: the row form -- the workgroup's channel, frame count, averaging length and frame positions come from its entry
-// of the launch's table (spectrum_frames_rows, below); the channel's overload word is written, set or clear, by the
-// workgroup that holds the row's last frame.
-template <class X, class Ld, bool ROWS = false>
-__device__ __forceinline__ void spectrum_frames(const SpectrumArgs &a, const int ch, const int part)
+// ---- the frame loop: one workgroup walks the frames f0 ... f1 of its job through transform X, loaded by Ld ----------
+template <class X, class Ld>
+__device__ __forceinline__ void spectrum_frames(const SpectrumArgs &a, const SpecJob &job)
 {
     constexpr int N = X::N, P = X::P;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     v2f *lds = reinterpret_cast<v2f *>(smem_raw);
-    // With nparts > 1 the frames of a channel are cut into nparts groups, one workgroup each: the
-    // running sum is the linear map sum <- alpha_f sum + p_f, so a group accumulates its frames from
-    // zero into `part` and spectrum_combine_kernel folds the groups in order.
-    const int t = threadIdx.x;
-    const int f0 = (int)((long)a.nframes * part / a.nparts), f1 = (int)((long)a.nframes * (part + 1) / a.nparts);
+    const int t = threadIdx.x, ch = job.ch;
+    const int f0 = group_frame(job, job.group), f1 = group_frame(job, job.group + 1);
     X xf(a, lds);
-    const Ld ld(a, ch);
+    const Ld ld(a, job);
     float *sum = a.sum + (long)ch * N, *pwr = a.pwr + (long)ch * N, *ave = a.ave + (long)ch * N;
     int ave_count = a.counters[2 * ch], total = a.counters[2 * ch + 1];
     total += f0;                                              // counters at this group's first frame
-    ave_count = ave_count + f0 < a.ave_size ? ave_count + f0 : (ave_count > a.ave_size ? ave_count : a.ave_size);
+    ave_count = ave_count_after(ave_count, f0, job.ave_size);
     int over = 0;
-    // (the row form: no launcher cleared the word -- the group that holds the row's last frame, never an empty one, does,
+    // (a word that no launcher cleared: the group that holds the channel's last frame, never an empty one, clears it,
     // and the barriers of that frame's transform lie between this store and the one at the end)
-    if constexpr (ROWS) if (t == 0 && part == a.nparts - 1) a.overload[ch] = 0;
+    if (job.own_overload && t == 0 && job.group == job.groups - 1) a.overload[ch] = 0;
     // every thread owns the same P bins in every frame: the running sum and mean stay in registers
     // for the whole call, only the last frame's bels are written
     int tt = t;
@@ -357,7 +395,7 @@ __device__ __forceinline__ void spectrum_frames(const SpectrumArgs &a, const int
     float sm[P];                              // the mean is sum / count: recomputed, not carried
     static_for<0, P>([&](auto Rr) {
         constexpr int r = Rr.value;
-        sm[r] = a.nparts == 1 ? sum[shown(r)] : 0.f;
+        sm[r] = job.groups == 1 ? sum[shown(r)] : 0.f;
         xf.keep_window(a.win, r);
     });
     xf.settle();
@@ -385,20 +423,20 @@ __device__ __forceinline__ void spectrum_frames(const SpectrumArgs &a, const int
         if (f + 1 < f1) fetch(f + 1);
         const float prev_count = (float)ave_count;
         total++;                                                  // CpxFFT counters, fft.cpp:515-517
-        if (ave_count < a.ave_size) ave_count++;
+        if (ave_count < job.ave_size) ave_count++;
         xf.run(x, lds);
         const float inv_prev = 1.0f / prev_count;                 // (one division per frame instead of one per bin: -10 %)
         static_for<0, P>([&](auto Rr) {
             constexpr int r = Rr.value;
             const float p = x[r].x * x[r].x + x[r].y * x[r].y;
-            if (total <= a.ave_size) sm[r] = sm[r] + p;
+            if (total <= job.ave_size) sm[r] = sm[r] + p;
             else sm[r] = sm[r] - sm[r] * inv_prev + p;            // minus the previous mean (fft.cpp:570-574)
         });
     }
-    if (a.nparts > 1) {
-        float *dst = a.part + ((long)ch * a.nparts + part) * N;
+    if (job.groups > 1) {
+        float *dst = a.part + job.slot(job.group) * N;
         static_for<0, P>([&](auto Rr) { dst[shown(Rr.value)] = sm[Rr.value]; });
-    } else if (a.nframes > 0) {
+    } else if (job.nframes > 0) {
         static_for<0, P>([&](auto Rr) {
             constexpr int r = Rr.value;
             const int j = shown(r);
@@ -408,66 +446,30 @@ __device__ __forceinline__ void spectrum_frames(const SpectrumArgs &a, const int
             if constexpr (P == 32 && (r & 7) == 7) __builtin_amdgcn_sched_barrier(0);   // (32 points: the bels eight at a time)
         });
     }
-    if (t == 0 && a.nparts == 1) { a.counters[2 * ch] = ave_count; a.counters[2 * ch + 1] = total; }
+    if (t == 0 && job.groups == 1) { a.counters[2 * ch] = ave_count; a.counters[2 * ch + 1] = total; }
     // the flag is the last put frame's: `over` is that of the group's last frame, and only the group that holds the
-    // call's last frame writes it (the launcher cleared the word)
-    if (over && part == a.nparts - 1) a.overload[ch] = 1;
+    // channel's last frame writes it
+    if (over && job.group == job.groups - 1) a.overload[ch] = 1;
 }
-// the uniform form: workgroup = (channel, frame group)
-template <class X, class Ld>
-__device__ __forceinline__ void spectrum_frames_uniform(const SpectrumArgs &a)
+// the kernels: workgroup = (entry, frame group) of the launch's nparts groups per entry
+template <class X, class Ld, bool ROWS>
+__device__ __forceinline__ void spectrum_kernel_body(const SpectrumArgs &a)
 {
-    spectrum_frames<X, Ld>(a, blockIdx.x / a.nparts, blockIdx.x % a.nparts);
+    SpecJob job;
+    if (spec_job<ROWS>(a, blockIdx.x / a.nparts, blockIdx.x % a.nparts, job)) spectrum_frames<X, Ld>(a, job);
 }
-// The row form: a copy of the arguments with the entry's values in the uniform form's fields (wave-uniform loads, once
-// per workgroup).  A row cuts ITS frame count into frame groups by the uniform form's rule, eight frames a group at
-// least, and takes the first row_groups() of the launch's nparts workgroups per row; the others leave at once.  So what a
-// row computes depends on its own frames alone -- not on how many frames the other rows of the launch have -- and a row
-// below sixteen frames runs the one-group path, whose words are those of the frames in order.  Its groups' partial sums
-// and weights lie in the row's own [nparts] slots.
-__device__ __forceinline__ int row_groups(int nframes, int nparts)
-{
-    const int g = nframes / 8;
-    return g < 1 ? 1 : (g < nparts ? g : nparts);
-}
-template <class X, class Ld>
-__device__ __forceinline__ void spectrum_frames_rows(const SpectrumArgs &a)
-{
-    const SpecRow e = a.rows[blockIdx.x / a.nparts];
-    const int part = blockIdx.x % a.nparts, groups = row_groups(e.nframes, a.nparts);
-    if (part >= groups) return;
-    SpectrumArgs b = a;
-    b.nframes = e.nframes; b.ave_size = e.ave_size;
-    b.frame_start = (long)e.start; b.frame_step = (long)e.step;
-    b.nparts = groups; b.part = a.part + (long)e.row * (a.nparts - groups) * X::N;     // [row][nparts][N] seen as [row][groups][N]
-    spectrum_frames<X, Ld, true>(b, e.row, part);
-}
-
-template <int LOG2N, class Ld = RowLoad>
+template <int LOG2N, class Ld = RowLoad, bool ROWS = false>
 __global__ __launch_bounds__(SpecCfg<LOG2N>::T) __attribute__((amdgpu_waves_per_eu(1)))
-void spectrum_kernel(SpectrumArgs a) { spectrum_frames_uniform<Passes32<LOG2N>, Ld>(a); }
-template <class Ld = RowLoad>
+void spectrum_kernel(SpectrumArgs a) { spectrum_kernel_body<Passes32<LOG2N>, Ld, ROWS>(a); }
+template <class Ld = RowLoad, bool ROWS = false>
 __global__ __launch_bounds__(128)
-void spectrum8_kernel(SpectrumArgs a) { spectrum_frames_uniform<Wide16<PassB2048>, Ld>(a); }
-template <class Ld = RowLoad>
+void spectrum8_kernel(SpectrumArgs a) { spectrum_kernel_body<Wide16<PassB2048>, Ld, ROWS>(a); }
+template <class Ld = RowLoad, bool ROWS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1)))
-void spectrum16_kernel(SpectrumArgs a) { spectrum_frames_uniform<Wide16<PassB4096>, Ld>(a); }
-template <class Ld = RowLoad>
+void spectrum16_kernel(SpectrumArgs a) { spectrum_kernel_body<Wide16<PassB4096>, Ld, ROWS>(a); }
+template <class Ld = RowLoad, bool ROWS = false>
 __global__ __launch_bounds__(512)
-void spectrum32_kernel(SpectrumArgs a) { spectrum_frames_uniform<Wide16<PassB8192>, Ld>(a); }
-// the same four behind a row table
-template <int LOG2N, class Ld = RowLoad>
-__global__ __launch_bounds__(SpecCfg<LOG2N>::T) __attribute__((amdgpu_waves_per_eu(1)))
-void spectrum_rows_kernel(SpectrumArgs a) { spectrum_frames_rows<Passes32<LOG2N>, Ld>(a); }
-template <class Ld = RowLoad>
-__global__ __launch_bounds__(128)
-void spectrum8_rows_kernel(SpectrumArgs a) { spectrum_frames_rows<Wide16<PassB2048>, Ld>(a); }
-template <class Ld = RowLoad>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1)))
-void spectrum16_rows_kernel(SpectrumArgs a) { spectrum_frames_rows<Wide16<PassB4096>, Ld>(a); }
-template <class Ld = RowLoad>
-__global__ __launch_bounds__(512)
-void spectrum32_rows_kernel(SpectrumArgs a) { spectrum_frames_rows<Wide16<PassB8192>, Ld>(a); }
+void spectrum32_kernel(SpectrumArgs a) { spectrum_kernel_body<Wide16<PassB8192>, Ld, ROWS>(a); }
 
 // plain transform: out[k] = sum_n in[n] e^{sign j 2 pi n k / N}; sign=-1 via conjugation
 template <int LOG2N>
@@ -511,78 +513,58 @@ void fft_plain_kernel(const v2f *in, v2f *out, const v2f *tw1g, const v2f *tw2g,
 // 40 us of the C1 call's 940 for its 512 sequential divisions).
 // One workgroup per channel (thread g = frame group g, in rounds of the block size): once every thread has read the
 // counters, thread 0 moves them -- what spectrum_count_kernel did in a launch of its own.
-// al: the channel's [nparts] weights; after: its average count after the call
-static __device__ __forceinline__ void spectrum_alpha(const SpectrumArgs &a, const int ch, const int nparts, float *al_out,
-                                                      float *after)
+// The job's `groups` weights go to its slots of a.alpha, the channel's average count after the call behind all slots.
+static __device__ __forceinline__ void spectrum_alpha(const SpectrumArgs &a, const SpecJob &job)
 {
+    const int ch = job.ch;
+    float *al_out = a.alpha + job.slot(0), *after = a.alpha + (long)a.channels * a.nparts + ch;
     const int ave0 = a.counters[2 * ch], total0 = a.counters[2 * ch + 1];
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int ave_count = ave0 + a.nframes;
-        a.counters[2 * ch] = ave_count < a.ave_size ? ave_count : (ave0 > a.ave_size ? ave0 : a.ave_size);
-        a.counters[2 * ch + 1] = total0 + a.nframes;
+        a.counters[2 * ch] = ave_count_after(ave0, job.nframes, job.ave_size);
+        a.counters[2 * ch + 1] = total0 + job.nframes;
     }
-    for (int g = threadIdx.x; g < nparts; g += blockDim.x) {
-        // after k frames: total0 + k, and the average count saturates at ave_size (a count above it -- the average was
-        // shortened -- stays)
-        auto ave_after = [&](int k) { return ave0 < a.ave_size ? (ave0 + k < a.ave_size ? ave0 + k : a.ave_size) : ave0; };
-        const int f0 = (int)((long)a.nframes * g / nparts), f1 = (int)((long)a.nframes * (g + 1) / nparts);
-        int ave_count = ave_after(f0), total = total0 + f0;
+    for (int g = threadIdx.x; g < job.groups; g += blockDim.x) {
+        const int f0 = group_frame(job, g), f1 = group_frame(job, g + 1);
+        int ave_count = ave_count_after(ave0, f0, job.ave_size), total = total0 + f0;
         float al = 1.f;                                                // product of the group's alpha_f
         for (int f = f0; f < f1; f++) {
             const float prev = (float)ave_count;
             total++;
-            if (ave_count < a.ave_size) ave_count++;
-            if (total > a.ave_size) al = al - al / prev;
+            if (ave_count < job.ave_size) ave_count++;
+            if (total > job.ave_size) al = al - al / prev;
             if (al == 0.f) break;                                      // (no averaging: the first frame already forgets everything)
         }
         al_out[g] = al;
-        if (g == 0) *after = (float)ave_after(a.nframes);
+        if (g == 0) *after = (float)ave_count_after(ave0, job.nframes, job.ave_size);
     }
 }
+// One workgroup per entry.  A channel of one group is finished by its frame loop, counters included: nothing here or in
+// the combine (the uniform form launches neither then; a row of one group can sit in a launch of several).  (A row
+// without a frame is in no table: the count after no frame of a fresh row is 0, and the combine would divide by it.)
+template <bool ROWS>
 __global__ void spectrum_alpha_kernel(SpectrumArgs a)
 {
-    spectrum_alpha(a, blockIdx.x, a.nparts, a.alpha + (long)blockIdx.x * a.nparts, a.alpha + (long)a.channels * a.nparts + blockIdx.x);
+    SpecJob job;
+    if (spec_job<ROWS>(a, blockIdx.x, 1, job)) spectrum_alpha(a, job);       // (a second group: not a channel of one)
 }
-// the row form: one workgroup per table entry, over the row's own groups.  A row of one group is finished by its frame
-// loop, counters included: nothing here or in the combine.  (A row without a frame is in no table: ave_after(0) of a
-// fresh row is 0, and the combine would divide by it.)
-__global__ void spectrum_alpha_rows_kernel(SpectrumArgs a)
-{
-    const SpecRow e = a.rows[blockIdx.x];
-    const int groups = row_groups(e.nframes, a.nparts);
-    if (groups == 1) return;
-    SpectrumArgs b = a;
-    b.nframes = e.nframes; b.ave_size = e.ave_size;
-    spectrum_alpha(b, e.row, groups, a.alpha + (long)e.row * a.nparts, a.alpha + (long)a.channels * a.nparts + e.row);
-}
-// folds the frame groups of spectrum_kernel (nparts > 1) into the running sum, writes mean and bels
+// folds the frame groups (groups > 1) into the running sum, writes mean and bels
+template <bool ROWS>
 __global__ void spectrum_combine_kernel(SpectrumArgs a, int n)
 {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x, ch = blockIdx.y;
-    if (j >= n) return;
+    SpecJob job;
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n || !spec_job<ROWS>(a, blockIdx.y, 1, job)) return;
+    const int ch = job.ch;
     float sm = a.sum[(long)ch * n + j];
-    for (int g = 0; g < a.nparts; g++)
-        sm = a.alpha[(long)ch * a.nparts + g] * sm + a.part[((long)ch * a.nparts + g) * n + j];
+    for (int g = 0; g < job.groups; g++)
+        sm = a.alpha[job.slot(g)] * sm + a.part[job.slot(g) * n + j];
     const float m = sm / a.alpha[(long)a.channels * a.nparts + ch];
     a.sum[(long)ch * n + j] = sm; a.pwr[(long)ch * n + j] = m;
     a.ave[(long)ch * n + j] = (float)((double)log10f(m + a.kc) + a.kb);
 }
-// the row form: the row's own groups, in its [nparts] slots; a row of one group was finished by its frame loop
-__global__ void spectrum_combine_rows_kernel(SpectrumArgs a, int n)
-{
-    const SpecRow e = a.rows[blockIdx.y];
-    const int j = blockIdx.x * blockDim.x + threadIdx.x, ch = e.row, groups = row_groups(e.nframes, a.nparts);
-    if (j >= n || groups == 1) return;
-    float sm = a.sum[(long)ch * n + j];
-    for (int g = 0; g < groups; g++)
-        sm = a.alpha[(long)ch * a.nparts + g] * sm + a.part[((long)ch * a.nparts + g) * n + j];
-    const float m = sm / a.alpha[(long)a.channels * a.nparts + ch];
-    a.sum[(long)ch * n + j] = sm; a.pwr[(long)ch * n + j] = m;
-    a.ave[(long)ch * n + j] = (float)((double)log10f(m + a.kc) + a.kb);
-}
-// (the kernel is a template argument: CSDR_MAX_LDS_ONCE keeps its flag per launch site, so per kernel)
-template <class X, auto Kernel, bool ROWS = false>
+// (the kernel is a template argument: CSDR_MAX_LDS_ONCE keeps its flag per launch site, so per kernel and form)
+template <class X, auto Kernel, bool ROWS>
 static hipError_t spec_launch_one(const SpectrumArgs &a, hipStream_t s)
 {
     if constexpr (X::LDS_BYTES > 64 * 1024) {             // more LDS than a kernel gets unasked
@@ -592,36 +574,21 @@ static hipError_t spec_launch_one(const SpectrumArgs &a, hipStream_t s)
     const int rows = ROWS ? a.nrows : a.channels;
     hipLaunchKernelGGL(Kernel, dim3(rows * a.nparts), dim3(X::T), X::LDS_BYTES, s, a);
     if (a.nparts > 1) {
-        hipLaunchKernelGGL(ROWS ? spectrum_alpha_rows_kernel : spectrum_alpha_kernel, dim3(rows), dim3(64), 0, s, a);
-        hipLaunchKernelGGL(ROWS ? spectrum_combine_rows_kernel : spectrum_combine_kernel, dim3(X::N / 256, rows), dim3(256), 0, s, a, (int)X::N);
+        hipLaunchKernelGGL(spectrum_alpha_kernel<ROWS>, dim3(rows), dim3(64), 0, s, a);
+        hipLaunchKernelGGL(spectrum_combine_kernel<ROWS>, dim3(X::N / 256, rows), dim3(256), 0, s, a, (int)X::N);
     }
     return hipGetLastError();
 }
-// The largest size that a kind of loader has a kernel for; above it the frames are gathered (capi_fft.hip).
-// The display stream's loaders run in the sixteen-point kernels only: at 16384 points (spectrum_kernel<14>, 512 threads,
-// at most 256 registers) the datagram loaders spilled 164 / 236 bytes and the DC row loader 12 bytes of scratch per lane.
-// The blanked loaders exist at 2048 and 4096 points: at 8192 points (spectrum32_kernel, 512 threads: at most 256
-// registers) the mask word per prefetched sample spilled -- 72 bytes of scratch per lane on fp32 rows, 16 on 16-bit and
-// 124 on 24-bit datagrams.
-constexpr int PLAIN_MAX_LOG2N = 14, STREAM_MAX_LOG2N = 13, BLANKED_MAX_LOG2N = 12;
-// (the tests against MAX_LOG2N are compile-time: a loader is instantiated in the kernels of ITS sizes only)
-template <int MAX_LOG2N, class Ld>
-static hipError_t spec_launch_rows(int log2n, const SpectrumArgs &a, hipStream_t s)
-{
-    if (a.nrows < 1) return hipErrorInvalidValue;
-    if (log2n == 11) return spec_launch_one<Wide16<PassB2048>, &spectrum8_rows_kernel<Ld>, true>(a, s);
-    if (log2n == 12) return spec_launch_one<Wide16<PassB4096>, &spectrum16_rows_kernel<Ld>, true>(a, s);
-    if constexpr (MAX_LOG2N >= 13) if (log2n == 13) return spec_launch_one<Wide16<PassB8192>, &spectrum32_rows_kernel<Ld>, true>(a, s);
-    if constexpr (MAX_LOG2N >= 14) if (log2n == 14) return spec_launch_one<Passes32<14>, &spectrum_rows_kernel<14, Ld>, true>(a, s);
-    return hipErrorInvalidValue;
-}
-template <int MAX_LOG2N, class Ld>
+// One size switch, bounded by the loader's largest size (spectrum_kernels.h; the tests against MAX_LOG2N are compile-time:
+// a loader is instantiated in the kernels of ITS sizes only)
+template <int MAX_LOG2N, class Ld, bool ROWS>
 static hipError_t spec_launch(int log2n, const SpectrumArgs &a, hipStream_t s)
 {
-    if (log2n == 11) return spec_launch_one<Wide16<PassB2048>, &spectrum8_kernel<Ld>>(a, s);
-    if (log2n == 12) return spec_launch_one<Wide16<PassB4096>, &spectrum16_kernel<Ld>>(a, s);
-    if constexpr (MAX_LOG2N >= 13) if (log2n == 13) return spec_launch_one<Wide16<PassB8192>, &spectrum32_kernel<Ld>>(a, s);
-    if constexpr (MAX_LOG2N >= 14) if (log2n == 14) return spec_launch_one<Passes32<14>, &spectrum_kernel<14, Ld>>(a, s);
+    if (ROWS && a.nrows < 1) return hipErrorInvalidValue;
+    if (log2n == 11) return spec_launch_one<Wide16<PassB2048>, &spectrum8_kernel<Ld, ROWS>, ROWS>(a, s);
+    if (log2n == 12) return spec_launch_one<Wide16<PassB4096>, &spectrum16_kernel<Ld, ROWS>, ROWS>(a, s);
+    if constexpr (MAX_LOG2N >= 13) if (log2n == 13) return spec_launch_one<Wide16<PassB8192>, &spectrum32_kernel<Ld, ROWS>, ROWS>(a, s);
+    if constexpr (MAX_LOG2N >= 14) if (log2n == 14) return spec_launch_one<Passes32<14>, &spectrum_kernel<14, Ld, ROWS>, ROWS>(a, s);
     return hipErrorInvalidValue;
 }
 template <int LOG2N>
@@ -637,32 +604,26 @@ static hipError_t plain_launch_one(int sign, const float *in, float *out, const 
 
 hipError_t spectrum_launch(int log2n, const SpectrumArgs &a, hipStream_t stream)
 {
-    if (a.rows) return spec_launch_rows<PLAIN_MAX_LOG2N, RowLoad>(log2n, a, stream);
-    return spec_launch<PLAIN_MAX_LOG2N, RowLoad>(log2n, a, stream);
+    if (a.rows) return spec_launch<PLAIN_MAX_LOG2N, RowLoad, true>(log2n, a, stream);
+    return spec_launch<PLAIN_MAX_LOG2N, RowLoad, false>(log2n, a, stream);
 }
-bool spectrum_stream_blanked_ok(int log2n, int pkt_len)
+template <bool ROWS>
+static hipError_t stream_launch(int log2n, const SpectrumArgs &a, int pkt_len, hipStream_t stream)
 {
-    return log2n >= 11 && log2n <= BLANKED_MAX_LOG2N && (pkt_len == 0 || pkt_len == 1028 || pkt_len == 1444);
+    if (!a.pk) return spec_launch<STREAM_MAX_LOG2N, RowDcLoad, ROWS>(log2n, a, stream);
+    if (pkt_len == 1444) return spec_launch<STREAM_MAX_LOG2N, WireLoad<1444>, ROWS>(log2n, a, stream);
+    if (pkt_len == 1028) return spec_launch<STREAM_MAX_LOG2N, WireLoad<1028>, ROWS>(log2n, a, stream);
+    return hipErrorInvalidValue;
 }
 hipError_t spectrum_stream_launch(int log2n, const SpectrumArgs &a, int pkt_len, hipStream_t stream)
 {
-    if (a.rows) {                // the row form has no blanked loaders: a blanked call's frames are gathered (capi_fft.hip)
-        if (a.nb_mask) return hipErrorInvalidValue;
-        if (!a.pk) return spec_launch_rows<STREAM_MAX_LOG2N, RowDcLoad>(log2n, a, stream);
-        if (pkt_len == 1444) return spec_launch_rows<STREAM_MAX_LOG2N, WireLoad<1444>>(log2n, a, stream);
-        if (pkt_len == 1028) return spec_launch_rows<STREAM_MAX_LOG2N, WireLoad<1028>>(log2n, a, stream);
-        return hipErrorInvalidValue;
+    if (a.nb_mask) {             // the row form has no blanked loaders: a blanked call's frames are gathered (capi_fft.hip)
+        if (a.rows || !spectrum_stream_blanked_ok(log2n, a.pk ? pkt_len : 0)) return hipErrorInvalidValue;
+        if (!a.pk) return spec_launch<BLANKED_MAX_LOG2N, BlankedLoad<RowDcLoad>, false>(log2n, a, stream);
+        if (pkt_len == 1444) return spec_launch<BLANKED_MAX_LOG2N, BlankedLoad<WireLoad<1444>>, false>(log2n, a, stream);
+        return spec_launch<BLANKED_MAX_LOG2N, BlankedLoad<WireLoad<1028>>, false>(log2n, a, stream);
     }
-    if (a.nb_mask) {
-        if (!spectrum_stream_blanked_ok(log2n, a.pk ? pkt_len : 0)) return hipErrorInvalidValue;
-        if (!a.pk) return spec_launch<BLANKED_MAX_LOG2N, BlankedLoad<RowDcLoad>>(log2n, a, stream);
-        if (pkt_len == 1444) return spec_launch<BLANKED_MAX_LOG2N, BlankedLoad<WireLoad<1444>>>(log2n, a, stream);
-        return spec_launch<BLANKED_MAX_LOG2N, BlankedLoad<WireLoad<1028>>>(log2n, a, stream);
-    }
-    if (!a.pk) return spec_launch<STREAM_MAX_LOG2N, RowDcLoad>(log2n, a, stream);
-    if (pkt_len == 1444) return spec_launch<STREAM_MAX_LOG2N, WireLoad<1444>>(log2n, a, stream);
-    if (pkt_len == 1028) return spec_launch<STREAM_MAX_LOG2N, WireLoad<1028>>(log2n, a, stream);
-    return hipErrorInvalidValue;
+    return a.rows ? stream_launch<true>(log2n, a, pkt_len, stream) : stream_launch<false>(log2n, a, pkt_len, stream);
 }
 hipError_t fft_plain_launch(int log2n, int sign, const float *in, float *out, const float *tw1,
                             const float *tw2, hipStream_t stream)
