@@ -639,9 +639,10 @@ __device__ __forceinline__ bool pll_scan(const Wg<NW> &g, const float *th, int n
     double c[LC], run = 0.0;
 #pragma unroll
     for (int j = 0; j < LC; j++) {
-        const float pv = j == 0 ? before : tv[j - 1];
-        const float d = tv[j] - pv;
-        if (j < cnt) run += (double)(d - rintf(d));
+        // (the difference in fp64: in fp32 it is rounded across the half-turn wrap, |d| near 1 being one bit coarser than the
+        // angles, and every wrap left up to 2^-25 turns in the unwrapped phase until the next tile dropped them as one step)
+        const double d = (double)tv[j] - (double)(j == 0 ? before : tv[j - 1]);
+        if (j < cnt) run += d - rint(d);
         c[j] = run;
     }
     const double ex = g.scan_sum_excl(run);
