@@ -2,6 +2,8 @@
 #include "capi_common.hpp"
 #include "spectrum_kernels.h"
 #include "display_stream_kernels.h"
+#include "fft_batch_plain64_kernels.h"
+#include "fft_tw64_host.hpp"
 #include "display_plan.hpp"
 #include "downconv_kernels.h"
 #include "capi_internal.hpp"
@@ -39,6 +41,12 @@ struct csdr_fft_batch {
     // tables and its intermediate, plain_group frames of every row; display calls never touch them
     float *d_twp = nullptr, *d_pwork = nullptr;
     int plain_group = 0;
+    // their fp64 form (csdr_fft_batch_fwd_f64 / _rev_f64): the table and, at the four-step sizes, the intermediate of
+    // plain_group64 frames of every row, for the object's present size.  Built by csdr_fft_batch_prepare_f64 or the
+    // first fp64 call, dropped by set_params: an object that never asks for fp64 holds none of it
+    double *d_tw64 = nullptr, *d_work64 = nullptr;
+    int plain_group64 = 0;
+    bool ready64 = false;
     // the row form: averaging length (rows_ave) and skip value, counter, gate and ready (rows_disp) per row; the frame
     // position ds.pos and the carry stay one per object.  While a flag is clear, its rows follow ave_size / ds (copied in
     // front of a row-form put).  rate_r: each row's m_MaxDisplayRate, for set_params.
@@ -84,6 +92,14 @@ static void fft_free_dev(csdr_fft_batch *f)
 {
     float **ps[] = {&f->d_win, &f->d_tw1, &f->d_tw2, &f->d_sum, &f->d_pwr, &f->d_ave, &f->d_work, &f->d_carry, &f->d_twp, &f->d_pwork};
     for (auto p : ps) { if (*p) (void)hipFree(*p); *p = nullptr; }
+}
+
+static void fft64_drop(csdr_fft_batch *f)
+{
+    if (f->d_tw64) (void)hipFree(f->d_tw64);
+    if (f->d_work64) (void)hipFree(f->d_work64);
+    f->d_tw64 = f->d_work64 = nullptr;
+    f->plain_group64 = 0; f->ready64 = false;
 }
 
 static int fft_reset(csdr_fft_batch *f)
@@ -169,6 +185,7 @@ static int fft_row_range(csdr_fft_batch *f, int row, int *lo, int *hi)
 static int fft_set_params(csdr_fft_batch *f, int size, int invert, double db_comp, double fs)
 {   // CFft::SetFFTParams (fft.cpp:118-243)
     if (size == 0) return CSDR_OK;
+    fft64_drop(f);
     f->bin_min = f->bin_max = 0; f->start_hz = f->stop_hz = 0; f->plot_w = 0;
     f->invert = invert; f->fs = fs;
     if (f->db_comp != db_comp) { f->last_size = 0; f->db_comp = db_comp; }
@@ -253,6 +270,7 @@ void csdr_fft_batch_destroy(csdr_fft_batch *f)
     if (!f) return;
     (void)hipSetDevice(f->device);
     fft_free_dev(f);
+    fft64_drop(f);
     if (f->d_cnt) (void)hipFree(f->d_cnt);
     if (f->d_over) (void)hipFree(f->d_over);
     if (f->d_scr) (void)hipFree(f->d_scr);
@@ -767,6 +785,78 @@ int csdr_fft_batch_rev(csdr_fft_batch *f, const float *d_in, long long in_stride
 { return fft_batch_plain(f, d_in, in_stride, d_out, out_stride, nframes, stream, -1); }
 int csdr_fft_batch_plain_group(csdr_fft_batch *f) { return f ? f->plain_group : fail(CSDR_EINVAL, "bad handle"); }
 
+/* ---- the same in fp64 (K3q): the reference's own precision, TYPECPX = two doubles ---- */
+// the table and the work buffer of the object's present size; allocates and waits, once per set_params
+static int fft64_group(const csdr_fft_batch *f)
+{   // as the fp32 form: 64 frames (a launch of 512 ... 1024 workgroups), and at least one of every row
+    if (log2_of(f->size) <= PLAIN64_MAX_LOG2N) return 0;
+    return f->channels < 64 ? 64 / f->channels : 1;
+}
+static int fft64_prepare(csdr_fft_batch *f)
+{
+    if (f->ready64) return CSDR_OK;
+    if (!device_ok(f->device)) return CSDR_EHIP;
+    fft64_drop(f);
+    const int n = f->size, l2 = log2_of(n);
+    const bool single = l2 <= PLAIN64_MAX_LOG2N;
+    std::vector<double> tw;
+    fft64_tables(n, single, tw);
+    CSDR_HIP(hipMalloc((void **)&f->d_tw64, tw.size() * sizeof(double)));
+    CSDR_HIP(hipMemcpy(f->d_tw64, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (!single) {
+        f->plain_group64 = fft64_group(f);
+        CSDR_HIP(hipMalloc((void **)&f->d_work64, (size_t)f->channels * f->plain_group64 * n * 16));
+    }
+    f->ready64 = true;
+    return CSDR_OK;
+}
+static int fft_batch_plain64(csdr_fft_batch *f, const double *d_in, long long in_stride, double *d_out, long long out_stride,
+                             int nframes, void *stream, int sign)
+{
+    if (!f || !d_in || !d_out || nframes < 0) return fail(CSDR_EINVAL, "bad argument");
+    if (nframes == 0) return CSDR_OK;
+    const long long need = (long long)nframes * f->size;
+    if (in_stride < need || out_stride < need) return fail(CSDR_EINVAL, "a row's stride must hold its %d frames of %d", nframes, f->size);
+    if (((uintptr_t)d_in | (uintptr_t)d_out) & 15) return fail(CSDR_EINVAL, "d_in and d_out must be 16-byte aligned");
+    if (!(d_in == d_out && in_stride == out_stride)) {
+        const uintptr_t a0 = (uintptr_t)d_in, a1 = a0 + (uintptr_t)((f->channels - 1) * in_stride + need) * 16;
+        const uintptr_t b0 = (uintptr_t)d_out, b1 = b0 + (uintptr_t)((f->channels - 1) * out_stride + need) * 16;
+        if (a0 < b1 && b0 < a1) return fail(CSDR_EINVAL, "d_out overlaps d_in (in place is d_out == d_in with equal strides)");
+    }
+    if ((long long)f->channels * nframes > 0x7fffffffll) return fail(CSDR_EINVAL, "channels * nframes must stay below 2^31");
+    if (fft64_group(f) > 0 && f->channels > 65535)           // (a grid dimension of the four-step launches)
+        return fail(CSDR_EINVAL, "the fp64 transforms of 8192 points and above take at most 65535 rows");
+    if (!device_ok(f->device)) return CSDR_EHIP;             // every call: the launch, its LDS attribute and a NULL stream are the current device's
+    if (int rc = fft64_prepare(f)) return rc;
+    PlainBatch64Args a;
+    a.in = d_in; a.in_stride = (long)in_stride; a.out = d_out; a.out_stride = (long)out_stride;
+    a.channels = f->channels; a.nframes = nframes; a.sign = sign;
+    a.tw = f->d_tw64; a.work = f->d_work64; a.group = f->plain_group64;
+    CSDR_HIP(fft_batch_plain64_launch(log2_of(f->size), a, (hipStream_t)stream));
+    return CSDR_OK;
+}
+int csdr_fft_batch_prepare_f64(csdr_fft_batch *f) { return f ? fft64_prepare(f) : fail(CSDR_EINVAL, "bad handle"); }
+int csdr_fft_batch_fwd_f64(csdr_fft_batch *f, const double *d_in, long long in_stride, double *d_out, long long out_stride,
+                           int nframes, void *stream)
+{ return fft_batch_plain64(f, d_in, in_stride, d_out, out_stride, nframes, stream, +1); }
+int csdr_fft_batch_rev_f64(csdr_fft_batch *f, const double *d_in, long long in_stride, double *d_out, long long out_stride,
+                           int nframes, void *stream)
+{ return fft_batch_plain64(f, d_in, in_stride, d_out, out_stride, nframes, stream, -1); }
+int csdr_fft_batch_plain_group_f64(csdr_fft_batch *f)
+{
+    return f ? fft64_group(f) : fail(CSDR_EINVAL, "bad handle");      // (of the present size, prepared or not)
+}
+// for the tests: the table csdr_fft_batch_prepare_f64 builds for an n-point transform, (cos, sin) pairs; returns the
+// number of doubles (at most cap are written); no device needed
+int csdr__host_fft_tw64(int n, double *out, int cap)
+{
+    if (log2_of(n) < 9 || log2_of(n) > 16 || (cap > 0 && !out)) return fail(CSDR_EINVAL, "bad argument");
+    std::vector<double> tw;
+    fft64_tables(n, log2_of(n) <= PLAIN64_MAX_LOG2N, tw);
+    for (int i = 0; i < cap && i < (int)tw.size(); i++) out[i] = tw[i];
+    return (int)tw.size();
+}
+
 // for the tests: one row's running sum [size] and {ave_count, total_count}, behind the object's last put
 int csdr__fft_batch_row_state(csdr_fft_batch *f, int row, float *sum, int *counters2)
 {
@@ -910,5 +1000,29 @@ static int fft_plain(csdr_fft *f, double *inout, int sign)
 }
 int csdr_fft_fwd(csdr_fft *f, double *inout_iq) { return fft_plain(f, inout_iq, +1); }
 int csdr_fft_rev(csdr_fft *f, double *inout_iq) { return fft_plain(f, inout_iq, -1); }
+
+/* the same in fp64: the caller's doubles as they are, the batch kernel on one row, and back */
+static int fft_plain64(csdr_fft *f, double *inout, int sign)
+{
+    if (!f || !inout) return fail(CSDR_EINVAL, "bad argument");
+    if (!device_ok(f->b->device)) return CSDR_EHIP;
+    const int N = f->b->size;
+    int rc = fft_host_buf(f, 2 * (size_t)N);                 // (in units of 8 bytes)
+    if (rc) return rc;
+    if (f->h2d_busy) { CSDR_HIP(hipEventSynchronize(f->ev_h2d)); f->h2d_busy = false; }
+    if ((rc = f->pin.reserve(4 * (size_t)N))) return rc;     // growing moves the buffer: nothing is in flight from it
+    double *const pin = reinterpret_cast<double *>(f->pin.p), *const dev = reinterpret_cast<double *>(f->d_buf);
+    memcpy(pin, inout, (size_t)N * 16);
+    hipStream_t st = f->s;
+    CSDR_HIP(hipMemcpyAsync(dev, pin, (size_t)N * 16, hipMemcpyHostToDevice, st));
+    rc = fft_batch_plain64(f->b, dev, N, dev, N, 1, (void *)st, sign);
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    CSDR_HIP(hipMemcpyAsync(pin, dev, (size_t)N * 16, hipMemcpyDeviceToHost, st));
+    CSDR_HIP(hipStreamSynchronize(st));
+    memcpy(inout, pin, (size_t)N * 16);
+    return CSDR_OK;
+}
+int csdr_fft_fwd_f64(csdr_fft *f, double *inout_iq) { return fft_plain64(f, inout_iq, +1); }
+int csdr_fft_rev_f64(csdr_fft *f, double *inout_iq) { return fft_plain64(f, inout_iq, -1); }
 
 }  // extern "C"

@@ -37,8 +37,14 @@ public:
         std::lock_guard<std::mutex> g(m_Mutex);
         return csdr_dropin_count(csdr_fft_put_display(m_h, n, &InBuf->re), "CFft::PutInDisplayFFT");
     }
+#ifdef CSDR_CFFT_FP64
+    // the reference's own precision: the caller's doubles transformed in fp64 on the device
+    void FwdFFT(TYPECPX *pInOutBuf) { CSDR_LOCK(); csdr_dropin_count(csdr_fft_fwd_f64(m_h, &pInOutBuf->re), "CFft::FwdFFT"); }
+    void RevFFT(TYPECPX *pInOutBuf) { CSDR_LOCK(); csdr_dropin_count(csdr_fft_rev_f64(m_h, &pInOutBuf->re), "CFft::RevFFT"); }
+#else
     void FwdFFT(TYPECPX *pInOutBuf) { CSDR_LOCK(); csdr_dropin_count(csdr_fft_fwd(m_h, &pInOutBuf->re), "CFft::FwdFFT"); }
     void RevFFT(TYPECPX *pInOutBuf) { CSDR_LOCK(); csdr_dropin_count(csdr_fft_rev(m_h, &pInOutBuf->re), "CFft::RevFFT"); }
+#endif
 
 private:
     csdr_fft *m_h;

@@ -955,6 +955,14 @@ class CFft(_Obj):
     def RevFFT(self, x):
         a = _c128(x).copy(); check(lib().csdr_fft_rev(self.h, _vp(a))); return a
 
+    def fwd64(self, x):
+        """FwdFFT of `size` complex doubles, transformed in fp64 as they are"""
+        a = _c128(x).copy(); check(lib().csdr_fft_fwd_f64(self.h, _vp(a)), "csdr_fft_fwd_f64"); return a
+
+    def rev64(self, x):
+        """RevFFT, as fwd64"""
+        a = _c128(x).copy(); check(lib().csdr_fft_rev_f64(self.h, _vp(a)), "csdr_fft_rev_f64"); return a
+
 
 class FftBatch(_Obj):
     """Batched display spectra over [channels][frames*size] fp32 I/Q on the device."""
@@ -1004,8 +1012,34 @@ class FftBatch(_Obj):
         """frames per row that one pass of the 32768 / 65536-point transforms takes through the work buffer (else 0)"""
         return check(lib().csdr_fft_batch_plain_group(self.h))
 
-    def _plain(self, call, x):
-        x = np.ascontiguousarray(x, dtype=np.complex64)
+    # ---- the same in fp64: complex128 rows, 16-byte aligned bases
+    def prepare64(self):
+        """build the fp64 tables and work buffer of the present size now (else the first fp64 call does)"""
+        check(lib().csdr_fft_batch_prepare_f64(self.h), "csdr_fft_batch_prepare_f64")
+
+    def fwd64_ptr(self, d_in, in_stride, d_out, out_stride, nframes, stream=None):
+        """fwd_ptr on complex fp64 rows"""
+        self._plain_ptr("csdr_fft_batch_fwd_f64", d_in, in_stride, d_out, out_stride, nframes, stream)
+
+    def rev64_ptr(self, d_in, in_stride, d_out, out_stride, nframes, stream=None):
+        """rev_ptr on complex fp64 rows"""
+        self._plain_ptr("csdr_fft_batch_rev_f64", d_in, in_stride, d_out, out_stride, nframes, stream)
+
+    def plain_group64(self):
+        """frames per row that one pass of the fp64 four-step form (8192 points and above) takes through its work
+        buffer (else 0)"""
+        return check(lib().csdr_fft_batch_plain_group_f64(self.h))
+
+    def fwd64(self, x):
+        """x complex [channels, frames*size] (host) -> FwdFFT of every frame in fp64, complex128"""
+        return self._plain(self.fwd64_ptr, x, np.complex128)
+
+    def rev64(self, x):
+        """x complex [channels, frames*size] (host) -> RevFFT of every frame in fp64, complex128"""
+        return self._plain(self.rev64_ptr, x, np.complex128)
+
+    def _plain(self, call, x, dtype=np.complex64):
+        x = np.ascontiguousarray(x, dtype=dtype)
         n = self.size()
         assert x.ndim == 2 and x.shape[0] == self.channels and x.shape[1] % n == 0, x.shape
         if x.shape[1] == 0:
@@ -1015,7 +1049,7 @@ class FftBatch(_Obj):
         try:
             call(d.ptr, x.shape[1], d.ptr, x.shape[1], x.shape[1] // n)
             sync(self.device)
-            return d.download(np.complex64, x.size).reshape(x.shape)
+            return d.download(dtype, x.size).reshape(x.shape)
         finally:
             d.free()
 

@@ -452,6 +452,9 @@ int csdr_fft_get_ave(csdr_fft *f, float *out);
 /* CFft::FwdFFT / RevFFT (:416-426): in-place, unnormalised, FwdFFT has the POSITIVE exponent */
 int csdr_fft_fwd(csdr_fft *f, double *inout_iq);
 int csdr_fft_rev(csdr_fft *f, double *inout_iq);
+/* the same with the caller's doubles transformed as they are, in fp64 (csdr_fft_batch_fwd_f64 on one row) */
+int csdr_fft_fwd_f64(csdr_fft *f, double *inout_iq);
+int csdr_fft_rev_f64(csdr_fft *f, double *inout_iq);
 
 /* batched spectra: [channels][in_stride] complex fp32 on the device, nframes frames per row */
 typedef struct csdr_fft_batch csdr_fft_batch;
@@ -484,6 +487,23 @@ int csdr_fft_batch_rev(csdr_fft_batch *f, const float *d_in, long long in_stride
  * (sized in csdr_fft_batch_set_params); a longer call runs in groups of this many on the stream.  0 at the other sizes.
  * Calls on one object share that buffer: keep them on one stream, or order them. */
 int csdr_fft_batch_plain_group(csdr_fft_batch *f);
+/* The same transforms in fp64, the reference's own precision (TYPECPX = two doubles): complex fp64 rows in and out.
+ * The contract is the one above with double pairs: strides in complex samples, bases 16-byte aligned.
+ * d_out == d_in with equal strides transforms in place; any other overlap is CSDR_EINVAL before anything is written.
+ * nframes == 0: CSDR_OK, no launch.  Asynchronous on `stream`; nothing of the display state is read or written.
+ * The fp64 tables (every entry rounded once from long double) and, at 8192 points and above, the fp64 work buffer
+ * belong to the object's present size: csdr_fft_batch_prepare_f64 builds them (it may allocate and wait),
+ * csdr_fft_batch_set_params drops them, and a transform call on an unprepared object prepares it first.
+ * After that a call allocates nothing and waits for nothing.  An object that never asks for fp64 holds none of it.
+ * At 8192 points and above an object of more than 65535 rows is CSDR_EINVAL (before anything is allocated). */
+int csdr_fft_batch_prepare_f64(csdr_fft_batch *f);
+int csdr_fft_batch_fwd_f64(csdr_fft_batch *f, const double *d_in, long long in_stride, double *d_out,
+                           long long out_stride, int nframes, void *stream);
+int csdr_fft_batch_rev_f64(csdr_fft_batch *f, const double *d_in, long long in_stride, double *d_out,
+                           long long out_stride, int nframes, void *stream);
+/* frames of every row that one pass of the fp64 four-step form (8192 ... 65536 points) takes through its work buffer;
+ * 0 at the other sizes.  Calls on one object share that buffer: keep them on one stream, or order them. */
+int csdr_fft_batch_plain_group_f64(csdr_fft_batch *f);
 int csdr_fft_batch_get_ave(csdr_fft_batch *f, int channel, float *out);
 int csdr_fft_batch_get_total_count(csdr_fft_batch *f, int channel);
 int csdr_fft_batch_get_screen(csdr_fft_batch *f, int channel, int max_h, int max_w, double max_db,
