@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import testgen_ref as R
+from k9_words import exact_turns      # the exact rational phase, shared with the K9 word rule
 
 RATES = [2.0e6, 10.0e6, 500.0e3, 615384.6, 48000.0]
 TOL_RAD = 1e-5                 # the GPU tolerance's phase share: 1e-5 of full scale is 1e-5 rad at 0 dB
@@ -241,21 +242,6 @@ def test_state_machine_is_cut_invariant(L):
 
 
 # ------------------------------------------------------------------------------------------------- 3 the premise
-def exact_turns(freq, fs, at):
-    """exact phase in turns (Fraction, modulo 1) before samples `at` of the frequency sequence freq over fs"""
-    m, e = np.frexp(freq)
-    mant = (m * 2.0 ** 53).astype(np.int64)
-    shift = 1200
-    s, out, at = 0, {}, set(int(a) for a in at)
-    for j in range(len(freq) + 1):
-        if j in at:
-            t = Fraction(s, 1 << shift) / Fraction(fs)
-            out[j] = t - math.floor(t)
-        if j < len(freq):
-            s += int(mant[j]) << (int(e[j]) - 53 + shift)
-    return out
-
-
 @pytest.mark.parametrize("c", [0, 1, 2, 4])
 def test_tolerance_premise_restatement_and_library_against_exact_phase(L, c):
     """Over 2^21 samples at 2 MSPS: the restatement in 256-sample calls stays within 1 % of the tolerance's phase share
